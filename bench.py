@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- sagittal slices/sec of one full HealthiVert-GAN train step (G + 3xD) at 256x256, per-GPU bs=16.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Launched by `python -m torch.distributed.run` (the driver's form) the ranks are
 already there; from a plain shell this script starts them itself -- as CHILD processes, before anything in the parent
@@ -9,9 +9,14 @@ has touched the GPU -- and exits with their status.  A run whose rank count diff
 
 One "step" = Pix2PixModel.optimize_parameters on one synthetic batch already resident in HBM: generator forward,
 three discriminator updates (fake + real pass each, Adam), generator backward through D_1/D_3 + losses, Adam.
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, measured live with HIP
-events on the launch stream), `fine_generator_forward` (the north-star's secondary gate), `inference` (BASELINE
-config #4) and `cpu_baseline` (the CPU oracle timed on this box's host cores, rank 0, N=1 only).
+A plain run sets up, warms up (W steps), times ONE region of exactly K steps and prints ONE JSON line (rank 0) with the
+contract fields (`ms_per_step` = that region / K).  --dump-outputs DIR writes what the last timed step computed
+(tensors as float32, losses as float64 .npy files, 64 MB at most; see dump_outputs).
+
+--full adds everything else the benchmark measures: the timed region run three times (the MEDIAN is the headline), `roofline`
+(dominant kernel, measured live with HIP events on the launch stream), `fine_generator_forward` (the north-star's secondary
+gate), `inference` (BASELINE config #4), `device_loader` / `fp32` / `config5` and `cpu_baseline` (the CPU oracle timed on
+this box's host cores, rank 0, N=1 only); --no-cpu-baseline / --no-inference / --no-extra leave parts of it out.
 
     python bench.py --gpus 2 --dry-run      # CPU-only rehearsal of the multi-rank plumbing (gloo): launcher, rendezvous,
                                             # flat-gradient exchange of the real networks' sizes, MAX-over-ranks clock
@@ -32,7 +37,7 @@ GFLOP_PER_SLICE = 195.9          # SURVEY.md section 8d / BASELINE.md section 2:
 GFLOP_FINE_FWD = 10.23           # FineGenerator forward per slice, the north-star's MFMA gate
 GFLOP_G_FWD = 17.56              # whole Generator forward per slice
 MB_FINE_FWD = 48.9               # FineGenerator forward per slice: compulsory bytes of its convolutions at fp16 storage, unfused
-MFMA_PEAK_TFLOPS = {'fp16': 2500.0, 'fp32': 157.3}   # MI355X dense peaks, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_PEAK_TFLOPS = {'fp16': 2500.0, 'fp32': 157.3}   # MI355X dense matrix-core peaks (CDNA4)
 
 
 def make_opt(precision):
@@ -51,9 +56,12 @@ def parse():
     ap.add_argument('--batch', type=int, default=16, help='per-GPU batch (slices)')
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--precision', default=os.environ.get('HV_PRECISION', 'fp16'), choices=['fp16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-inference', action='store_true', help='skip the config-#4 inference sub-record')
-    ap.add_argument('--no-extra', action='store_true', help='skip the device-loader and fp32-mode sub-records')
+    ap.add_argument('--full', action='store_true', help='also the three-region median, roofline, refinement-generator, inference, device-loader, fp32, '
+                    '512x512 and CPU-baseline records (a plain run times the K steps once and reports only the headline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write what the last one computed as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU-baseline sub-record')
+    ap.add_argument('--no-inference', action='store_true', help='--full: skip the config-#4 inference sub-record')
+    ap.add_argument('--no-extra', action='store_true', help='--full: skip the device-loader and fp32-mode sub-records')
     ap.add_argument('--serial', action='store_true', help='one HIP stream for the whole run (profiling: per-kernel durations without stream-level overlap)')
     ap.add_argument('--no-graph', action='store_true', help='launch kernels eagerly instead of replaying captured hipGraphs')
     ap.add_argument('--dry-run', action='store_true', help='CPU-only rehearsal of the multi-rank path over gloo (no GPU, no kernels)')
@@ -308,6 +316,46 @@ def inference_record(dev, precision):
             'stage_batch_tflops': round(GFLOP_G_FWD * max(nz, 1) / ms, 1), 'includes': 'host slicing, PCIe in/out, device preparation, 3 generator stages'}
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
+DUMP_MAX_ELEMS = 1 << 20         # per array: a larger one is written as a fixed, seeded sample of its flattened elements
+DUMP_SEED = 20240601
+INPUT_VISUALS = ('real_A', 'real_B', 'mask', 'CAM', 'normal_vert', 'real_B_mask')      # set_input's tensors, not computed by the step
+
+
+def dump_outputs(model, d):
+    """What the timed path's last step handed its caller, as DIR/<name>.npy: the computed visuals of get_current_visuals() and the two height
+    predictions (float32), every loss of get_current_losses() (float64 scalars) and the four networks' parameters after the step's Adam updates
+    (float32, flattened in parameters() order).  An array of more than DUMP_MAX_ELEMS elements is written as the elements at a sorted, seeded
+    sample of flat indices (the same for the same shape in every run), so the same arguments give files that compare output for output."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_initialized():
+        torch.cuda.synchronize()
+    arrays = {}
+    for n, t in model.get_current_visuals().items():
+        if n not in INPUT_VISUALS and isinstance(t, torch.Tensor):
+            arrays['visual_' + n] = t
+    arrays['pred1_h'], arrays['pred2_h'] = model.pred1_h, model.pred2_h
+    for n in model.model_names:
+        arrays['params_' + n] = torch.cat([p.detach().reshape(-1).float() for p in getattr(model, 'net' + n).parameters()])
+    out = {}
+    for n, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        out[n] = np.ascontiguousarray(a, dtype=np.float32)
+    for n, v in model.get_current_losses().items():
+        out['loss_' + n] = np.asarray(v, dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(d, n + '.npy'), a)
+    return total
+
+
 def main():
     args = parse()
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -361,79 +409,83 @@ def main():
     barrier()
     if model.use_graph and not model._graphs:
         raise SystemExit('bench.py: the step was not captured as hipGraphs')
-    prof = profiler.KernelTimer()
-    prof.calibrate()                  # what an event pair reads around NOTHING on this box: taken off every kernel's event duration below
     serial0 = engine.SERIAL
-    engine.SERIAL = True              # per-kernel HIP-event timing: one stream, the kernel has the GPU to itself
-    prof.enable()                     # untimed eager survey step: time every conv launch, pick the dominant kernel class
-    step()
-    dom = prof.dominant()
-    dom_mfma = prof.dominant_mfma(MFMA_PEAK_TFLOPS[args.precision])      # the largest MFMA-bound instantiation (the PatchGAN 4x4 layers), timed beside it
-    prof.disable()
-    engine.SERIAL = serial0
-    # the timed region: K steps (graph replays unless --no-graph) between barrier + synchronize on both sides -- run three times back to back,
-    # the MEDIAN region is reported (all three are on the record: `regions_ms_per_step`)
+    prof = dom = dom_mfma = None
+    if args.full:
+        prof = profiler.KernelTimer()
+        prof.calibrate()                  # what an event pair reads around NOTHING on this box: taken off every kernel's event duration below
+        engine.SERIAL = True              # per-kernel HIP-event timing: one stream, the kernel has the GPU to itself
+        prof.enable()                     # untimed eager survey step: time every conv launch, pick the dominant kernel class
+        step()
+        dom = prof.dominant()
+        dom_mfma = prof.dominant_mfma(MFMA_PEAK_TFLOPS[args.precision])      # the largest MFMA-bound instantiation (the PatchGAN 4x4 layers), timed beside it
+        prof.disable()
+        engine.SERIAL = serial0
+    # the timed region: K steps (graph replays unless --no-graph) between barrier + synchronize on both sides; --full runs it three times back
+    # to back and reports the MEDIAN region (all three are on the record: `regions_ms_per_step`)
     region_dt = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 1):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         barrier()
         region_dt.append(time.perf_counter() - t0)
-    # roofline leg: the same K steps once more, launched eagerly on ONE stream with HIP events around the dominant
-    # kernel's launches (a captured graph cannot carry timing events, and with other streams busy an event pair would
-    # also time the wait for free CUs); `bench.py --serial` under rocprofv3 gives the matching per-kernel averages.
-    # The same eager single-stream steps carry the event pair around the refinement generator's forward.
-    engine.SERIAL = True
-    prof.enable(only=(list(dom[1]) + (list(dom_mfma[1]) if dom_mfma else [])) if dom else None)
-    model.netG.time_fine = []
-    for _ in range(args.steps):
-        step()
-    barrier()
-    prof.disable()
-    fine = model.netG.time_fine
-    model.netG.time_fine = None
-    engine.SERIAL = serial0
-    # the same event pair with the step's real stream structure (the refinement generator's dilated-conv branch and attention branch on two
-    # streams, as inside the captured graphs): a few eager steps with the side streams on
-    fine2 = None
-    if not args.serial:
-        ug, model.use_graph = model.use_graph, False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
+    fine = fine2 = fine_graph = None
+    if args.full:
+        # roofline leg: the same K steps once more, launched eagerly on ONE stream with HIP events around the dominant
+        # kernel's launches (a captured graph cannot carry timing events, and with other streams busy an event pair would
+        # also time the wait for free CUs); `bench.py --serial` under rocprofv3 gives the matching per-kernel averages.
+        # The same eager single-stream steps carry the event pair around the refinement generator's forward.
+        engine.SERIAL = True
+        prof.enable(only=(list(dom[1]) + (list(dom_mfma[1]) if dom_mfma else [])) if dom else None)
         model.netG.time_fine = []
-        for _ in range(5):
+        for _ in range(args.steps):
             step()
         barrier()
-        fine2 = model.netG.time_fine
+        prof.disable()
+        fine = model.netG.time_fine
         model.netG.time_fine = None
-        model.use_graph = ug
-    # ... and the refinement generator's forward ALONE as the product launches it: one captured hipGraph (both branches on their two streams),
-    # replayed with nothing else on the GPU.  The two event pairs above are taken around eager launches (one Python / ctypes call per kernel:
-    # the host can be the bound); this one is the device time of the ~65 kernels
-    fine_graph = None
-    if world == 1 and not args.serial and model.use_graph and getattr(model, '_gplan', None) is not None:
-        try:
-            torch.cuda.synchronize()
-            cam_t = model._buf('cam_temp', model.CAM)
-            g = model.netG.fine_forward_graph(model._gplan, model.real_A, model.mask, model.slice_ratio)
-            for _ in range(3):
-                g.replay()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            nrep = 50
-            e0.record()
-            for _ in range(nrep):
-                g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            fine_graph = e0.elapsed_time(e1) / nrep
-            del g, cam_t
-        except Exception as exc:       # noqa: BLE001 -- a diagnostic leg: the headline numbers do not depend on it
-            sys.stderr.write('bench.py: fine-generator graph replay leg skipped (%s)\n' % str(exc).splitlines()[0])
+        engine.SERIAL = serial0
+        # the same event pair with the step's real stream structure (the refinement generator's dilated-conv branch and attention branch on two
+        # streams, as inside the captured graphs): a few eager steps with the side streams on
+        if not args.serial:
+            ug, model.use_graph = model.use_graph, False
+            model.netG.time_fine = []
+            for _ in range(5):
+                step()
+            barrier()
+            fine2 = model.netG.time_fine
+            model.netG.time_fine = None
+            model.use_graph = ug
+        # ... and the refinement generator's forward ALONE as the product launches it: one captured hipGraph (both branches on their two streams),
+        # replayed with nothing else on the GPU.  The two event pairs above are taken around eager launches (one Python / ctypes call per kernel:
+        # the host can be the bound); this one is the device time of the ~65 kernels
+        if world == 1 and not args.serial and model.use_graph and getattr(model, '_gplan', None) is not None:
+            try:
+                torch.cuda.synchronize()
+                cam_t = model._buf('cam_temp', model.CAM)
+                g = model.netG.fine_forward_graph(model._gplan, model.real_A, model.mask, model.slice_ratio)
+                for _ in range(3):
+                    g.replay()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                nrep = 50
+                e0.record()
+                for _ in range(nrep):
+                    g.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                fine_graph = e0.elapsed_time(e1) / nrep
+                del g, cam_t
+            except Exception as exc:       # noqa: BLE001 -- a diagnostic leg: the headline numbers do not depend on it
+                sys.stderr.write('bench.py: fine-generator graph replay leg skipped (%s)\n' % str(exc).splitlines()[0])
     if world > 1:      # MAX over ranks, region by region
         t = torch.tensor(region_dt, device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         region_dt = [float(v) for v in t.tolist()]
-    dt = sorted(region_dt)[1]
+    dt = sorted(region_dt)[len(region_dt) // 2]
     ms = dt / args.steps * 1e3
     value = world * args.batch * args.steps / dt
 
@@ -461,86 +513,87 @@ def main():
                  'preflight': getattr(model, 'dp_preflight_record', None)},
     }
     if rank == 0:
-        out['roofline'] = prof.roofline(args.precision, MFMA_PEAK_TFLOPS[args.precision], name=dom[0] if dom else None)
-        if out['roofline'] is None:
-            raise SystemExit('bench.py: the roofline leg timed no kernel launch')
-        # the dominant instantiation by total time is an HBM-side generator kernel since round 2; the largest MFMA-bound one (same events, same
-        # steps) keeps the matrix-core kernels of the step on the record
-        if dom_mfma and dom_mfma[0] != dom[0]:
-            out['roofline_mfma'] = prof.roofline(args.precision, MFMA_PEAK_TFLOPS[args.precision], name=dom_mfma[0])
-        # HBM bytes per launch from the committed PMC passes of this round (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate
-        # passes over a serial bench run; mean per launch of this instantiation)
-        pdir = os.path.join(ROOT, 'profiles')
-
-        import glob
-        traffic_files = sorted(glob.glob(os.path.join(pdir, 'r*_traffic_step.json')), reverse=True)      # newest round / tag first
-
-        def add_traffic(rec):
-            for fp in traffic_files:
-                try:
-                    e = json.load(open(fp))['kernels'].get(rec['kernel'])
-                except (OSError, ValueError, KeyError):
-                    e = None
-                if e:
-                    rec['traffic'] = int(e['traffic_bytes'])
-                    rec['traffic_source'] = 'profiles/%s (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, serial bench run)' % os.path.basename(fp)
-                    break
-        add_traffic(out['roofline'])
-        if out.get('roofline_mfma'):
-            add_traffic(out['roofline_mfma'])
-        out['roofline']['timed_in'] = ('eager single-stream re-run of the K steps after the timed region (HIP events on the launch stream); avg_us is net of the '
-                                       'event pair\'s own reading around nothing (event_pair_overhead_us, measured in this run), avg_us_events is the raw reading')
-        # the whole step against both roofs: algorithmic FLOPs of the step and the HBM bytes the committed PMC passes measured per step
-        step_rec = {'achieved_tflops': round(GFLOP_PER_SLICE * args.batch * (args.size / 256.0) ** 2 / ms, 1)}
-        step_rec['frac_mfma'] = round(step_rec['achieved_tflops'] / MFMA_PEAK_TFLOPS[args.precision], 4)
-        for fp in traffic_files:
-            try:
-                doc = json.load(open(fp))
-                tot = doc.get('step_total_bytes')
-                if not tot:      # (files written before round 4: steps of the profiled run = launches of the once-per-step compositing kernel)
-                    once = doc['kernels'].get('post_generator_kernel', {}).get('launches')
-                    tot = int(sum(v['traffic_bytes'] * v['launches'] for v in doc['kernels'].values()) / once) if once else None
-            except (OSError, ValueError, KeyError):
-                tot = None
-            if tot and args.size == 256 and args.batch == 16 and args.precision == 'fp16':
-                step_rec.update(hbm_gb_per_step=round(tot / 1e9, 2), hbm_gbs=round(tot / 1e9 / (ms * 1e-3), 1), frac_hbm=round(tot / 1e9 / (ms * 1e-3) / profiler.HBM_PEAK_GBS, 4),
-                                traffic_source='profiles/%s (sum over every kernel of the step, PMC passes)' % os.path.basename(fp))
-                break
-        out['step_roofline'] = step_rec
-        if fine:
-            torch.cuda.synchronize()
-            fms = sum(s.elapsed_time(e) for s, e in fine) / len(fine)
-            tf = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / fms
-            out['fine_generator_forward'] = {'ms': round(fms, 3), 'gflop': round(GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2, 1),
-                                             'tflops': round(tf, 1), 'frac_of_mfma_peak': round(tf / MFMA_PEAK_TFLOPS[args.precision], 4),
-                                             'algorithmic_mb': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 * (1 if args.precision == 'fp16' else 2), 1),
-                                             'frac_of_hbm_peak': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 * (1 if args.precision == 'fp16' else 2) / 1e3 / fms / profiler.HBM_PEAK_GBS * 1e3, 4),
-                                             'timed_in': 'the same eager single-stream steps: HIP events around FineGenerator (training forward, '
-                                                         'both branches + contextual attention in line), mean of %d' % len(fine)}
-        if fine2:
-            f2 = sum(s_.elapsed_time(e_) for s_, e_ in fine2) / len(fine2)
-            tf2 = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / f2
-            out['fine_generator_forward']['two_streams'] = {'ms': round(f2, 3), 'tflops': round(tf2, 1), 'frac_of_mfma_peak': round(tf2 / MFMA_PEAK_TFLOPS[args.precision], 4),
-                                                            'timed_in': 'eager steps with the step\'s own streams (the two branches concurrent, discriminator streams busy beside them), mean of %d' % len(fine2)}
-        if fine_graph and 'fine_generator_forward' in out:
-            tfg = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / fine_graph
-            out['fine_generator_forward']['graph_replay'] = {'ms': round(fine_graph, 3), 'tflops': round(tfg, 1), 'frac_of_mfma_peak': round(tfg / MFMA_PEAK_TFLOPS[args.precision], 4),
-                                                             'frac_of_hbm_peak': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / 1e3 / fine_graph / profiler.HBM_PEAK_GBS * 1e3, 4),
-                                                             'timed_in': 'the refinement generator\'s training forward alone as one captured hipGraph (two branch streams), mean of 50 back-to-back replays, GPU otherwise idle'}
         ngraphs = len(model._graphs or ())
         out['config']['launch'] = ('hipGraph replay (%d graphs/step)' % ngraphs if model.use_graph else 'eager') + \
                                   (', one stream' if args.serial else ', %d streams' % (5 if (world > 1 or model.grad_sync.active()) else 4))
         out['losses'] = {k: round(v, 4) for k, v in model.get_current_losses().items()}
-        if world == 1 and not args.no_inference and args.size == 256:
-            out['inference'] = inference_record(dev, args.precision)
-        if world == 1 and not args.no_extra and args.precision == 'fp16':
-            out['device_loader'] = device_loader_record(model, args, dev)
-            out['fp32'] = fp32_record(args, dev, local_rank)
-            if args.size == 256:
-                out['config5'] = config5_record(args, dev, local_rank)
-                out['config5']['per_pixel_rate_vs_256'] = round(out['config5']['pixels_per_s'] / (value * 256 * 256 / 1e6), 3)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(model, args.size, 1234)
+        if args.full:
+            out['roofline'] = prof.roofline(args.precision, MFMA_PEAK_TFLOPS[args.precision], name=dom[0] if dom else None)
+            if out['roofline'] is None:
+                raise SystemExit('bench.py: the roofline leg timed no kernel launch')
+            # the dominant instantiation by total time is an HBM-side generator kernel since round 2; the largest MFMA-bound one (same events, same
+            # steps) keeps the matrix-core kernels of the step on the record
+            if dom_mfma and dom_mfma[0] != dom[0]:
+                out['roofline_mfma'] = prof.roofline(args.precision, MFMA_PEAK_TFLOPS[args.precision], name=dom_mfma[0])
+            # HBM bytes per launch from the committed PMC passes of this round (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate
+            # passes over a serial bench run; mean per launch of this instantiation)
+            pdir = os.path.join(ROOT, 'profiles')
+
+            import glob
+            traffic_files = sorted(glob.glob(os.path.join(pdir, 'r*_traffic_step.json')), reverse=True)      # newest round / tag first
+
+            def add_traffic(rec):
+                for fp in traffic_files:
+                    try:
+                        e = json.load(open(fp))['kernels'].get(rec['kernel'])
+                    except (OSError, ValueError, KeyError):
+                        e = None
+                    if e:
+                        rec['traffic'] = int(e['traffic_bytes'])
+                        rec['traffic_source'] = 'profiles/%s (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, serial bench run)' % os.path.basename(fp)
+                        break
+            add_traffic(out['roofline'])
+            if out.get('roofline_mfma'):
+                add_traffic(out['roofline_mfma'])
+            out['roofline']['timed_in'] = ('eager single-stream re-run of the K steps after the timed region (HIP events on the launch stream); avg_us is net of the '
+                                           'event pair\'s own reading around nothing (event_pair_overhead_us, measured in this run), avg_us_events is the raw reading')
+            # the whole step against both roofs: algorithmic FLOPs of the step and the HBM bytes the committed PMC passes measured per step
+            step_rec = {'achieved_tflops': round(GFLOP_PER_SLICE * args.batch * (args.size / 256.0) ** 2 / ms, 1)}
+            step_rec['frac_mfma'] = round(step_rec['achieved_tflops'] / MFMA_PEAK_TFLOPS[args.precision], 4)
+            for fp in traffic_files:
+                try:
+                    doc = json.load(open(fp))
+                    tot = doc.get('step_total_bytes')
+                    if not tot:      # (files written before round 4: steps of the profiled run = launches of the once-per-step compositing kernel)
+                        once = doc['kernels'].get('post_generator_kernel', {}).get('launches')
+                        tot = int(sum(v['traffic_bytes'] * v['launches'] for v in doc['kernels'].values()) / once) if once else None
+                except (OSError, ValueError, KeyError):
+                    tot = None
+                if tot and args.size == 256 and args.batch == 16 and args.precision == 'fp16':
+                    step_rec.update(hbm_gb_per_step=round(tot / 1e9, 2), hbm_gbs=round(tot / 1e9 / (ms * 1e-3), 1), frac_hbm=round(tot / 1e9 / (ms * 1e-3) / profiler.HBM_PEAK_GBS, 4),
+                                    traffic_source='profiles/%s (sum over every kernel of the step, PMC passes)' % os.path.basename(fp))
+                    break
+            out['step_roofline'] = step_rec
+            if fine:
+                torch.cuda.synchronize()
+                fms = sum(s.elapsed_time(e) for s, e in fine) / len(fine)
+                tf = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / fms
+                out['fine_generator_forward'] = {'ms': round(fms, 3), 'gflop': round(GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2, 1),
+                                                 'tflops': round(tf, 1), 'frac_of_mfma_peak': round(tf / MFMA_PEAK_TFLOPS[args.precision], 4),
+                                                 'algorithmic_mb': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 * (1 if args.precision == 'fp16' else 2), 1),
+                                                 'frac_of_hbm_peak': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 * (1 if args.precision == 'fp16' else 2) / 1e3 / fms / profiler.HBM_PEAK_GBS * 1e3, 4),
+                                                 'timed_in': 'the same eager single-stream steps: HIP events around FineGenerator (training forward, '
+                                                             'both branches + contextual attention in line), mean of %d' % len(fine)}
+            if fine2:
+                f2 = sum(s_.elapsed_time(e_) for s_, e_ in fine2) / len(fine2)
+                tf2 = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / f2
+                out['fine_generator_forward']['two_streams'] = {'ms': round(f2, 3), 'tflops': round(tf2, 1), 'frac_of_mfma_peak': round(tf2 / MFMA_PEAK_TFLOPS[args.precision], 4),
+                                                                'timed_in': 'eager steps with the step\'s own streams (the two branches concurrent, discriminator streams busy beside them), mean of %d' % len(fine2)}
+            if fine_graph and 'fine_generator_forward' in out:
+                tfg = GFLOP_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / fine_graph
+                out['fine_generator_forward']['graph_replay'] = {'ms': round(fine_graph, 3), 'tflops': round(tfg, 1), 'frac_of_mfma_peak': round(tfg / MFMA_PEAK_TFLOPS[args.precision], 4),
+                                                                 'frac_of_hbm_peak': round(MB_FINE_FWD * args.batch * (args.size / 256.0) ** 2 / 1e3 / fine_graph / profiler.HBM_PEAK_GBS * 1e3, 4),
+                                                                 'timed_in': 'the refinement generator\'s training forward alone as one captured hipGraph (two branch streams), mean of 50 back-to-back replays, GPU otherwise idle'}
+            if world == 1 and not args.no_inference and args.size == 256:
+                out['inference'] = inference_record(dev, args.precision)
+            if world == 1 and not args.no_extra and args.precision == 'fp16':
+                out['device_loader'] = device_loader_record(model, args, dev)
+                out['fp32'] = fp32_record(args, dev, local_rank)
+                if args.size == 256:
+                    out['config5'] = config5_record(args, dev, local_rank)
+                    out['config5']['per_pixel_rate_vs_256'] = round(out['config5']['pixels_per_s'] / (value * 256 * 256 / 1e6), 3)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(model, args.size, 1234)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -305,11 +305,11 @@ def test_rccl_exchange_path_single_rank(tmp_path, schedule, precision):
             assert torch.equal(outs[0][n][k], outs[1][n][k]), (n, k)
 
 
-def _bench(extra_env, args, launcher=None):
+def _bench(extra_env, args, launcher=None, full=True):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'HV_DDP_FORCE', 'HV_DDP_BACKEND')}
     env.update(extra_env)
-    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, 'bench.py')] + args + ['--no-cpu-baseline', '--no-inference', '--no-extra']
+    cmd = (launcher or [sys.executable]) + [os.path.join(ROOT, 'bench.py')] + args + (['--full', '--no-cpu-baseline', '--no-inference', '--no-extra'] if full else [])
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -325,7 +325,7 @@ def test_bench_two_ranks_rehearsal_over_gloo():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(HV_DDP_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '3', '--no-cpu-baseline'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '3', '--full', '--no-cpu-baseline'],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]
@@ -366,3 +366,25 @@ def test_bench_data_parallel_dress_rehearsal_on_one_device():
     assert two['n_gpus'] == 2 and two['config']['global_batch'] == 32 and two['config']['parallelism'] == 'dp2', two['config']
     assert two['comm']['backend'] == 'gloo' and two['comm']['world_size'] == 2, two['comm']
     assert two['value'] > 0 and two['scaling'] == 'weak' and '3 graphs' in two['config']['launch']
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times ONE region of exactly K steps (ms_per_step = that region / K) and adds none of --full's
+    records; --dump-outputs writes what the last timed step computed: the generator's composited outputs and heights and the updated weights
+    as float32, the losses as float64 scalars, 64 MB at most."""
+    import numpy as np
+    d = tmp_path / 'out'
+    rec = _bench({}, ['--steps', '3', '--warmup', '1', '--dump-outputs', str(d)], full=False)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in rec, k
+    assert rec['steps'] == 3 and rec['n_gpus'] == 1 and rec['unit'] == 'slices/s' and rec['higher_is_better'] is True and rec['dtype'] == 'f16'
+    assert rec['regions_ms_per_step'] == [rec['ms_per_step']] and abs(rec['value'] - 16 * 1e3 / rec['ms_per_step']) <= 1e-3 * rec['value'] + 0.01
+    assert not {'roofline', 'step_roofline', 'fine_generator_forward', 'inference', 'device_loader', 'fp32', 'config5', 'cpu_baseline'} & set(rec), sorted(rec)
+    files = {f.name: np.load(str(f)) for f in d.iterdir()}
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    assert files['visual_fake_B.npy'].shape == (16, 1, 256, 256) and files['visual_fake_B.npy'].dtype == np.float32
+    for n in ('G', 'D_1', 'D_2', 'D_3'):
+        assert files['params_%s.npy' % n].dtype == np.float32 and files['params_%s.npy' % n].ndim == 1
+    losses = {n[5:-4]: float(a) for n, a in files.items() if n.startswith('loss_')}
+    assert all(files['loss_%s.npy' % n].dtype == np.float64 for n in losses) and losses == pytest.approx(rec['losses'], abs=1e-4)
+    assert all(np.isfinite(a).all() for a in files.values())

@@ -180,6 +180,50 @@ def test_bench_starts_its_own_ranks_dry_run():
     assert q.returncode != 0 and b'--gpus 2' in q.stderr
 
 
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs on a host stand-in for the trained model: computed visuals, heights and flattened parameters as float32, losses as
+    float64, set_input's tensors left out; an array larger than DUMP_MAX_ELEMS is written as the SAME seeded sample in every run, and the whole
+    dump stays within 64 MB even at 512 x 512."""
+    import numpy as np
+    import bench
+
+    class Net(torch.nn.Module):
+        def __init__(self, n):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.arange(n, dtype=torch.float32))
+            self.b = torch.nn.Parameter(torch.ones(3))
+
+    class Model:
+        model_names = ['G', 'D_1']
+        netG, netD_1 = Net(10), Net(3 << 20)
+        pred1_h, pred2_h = torch.full((1, 16), 0.25), torch.full((1, 16), 0.5)
+
+        def get_current_visuals(self):
+            g = torch.Generator().manual_seed(3)
+            return {n: torch.rand(16, 1, 512, 512, generator=g).half() for n in bench.INPUT_VISUALS + ('fake_B', 'fake_B_raw', 'real_edges')}
+
+        def get_current_losses(self):
+            return {'G_GAN': 0.75, 'h': 1.0 / 3.0}
+
+    files = []
+    for run in ('a', 'b'):
+        total = bench.dump_outputs(Model(), str(tmp_path / run))
+        assert total <= bench.DUMP_MAX_BYTES and total == sum(f.stat().st_size - 128 for f in (tmp_path / run).iterdir())
+        files.append({f.name: np.load(str(f)) for f in (tmp_path / run).iterdir()})
+    a, b = files
+    assert sorted(a) == sorted(['visual_fake_B.npy', 'visual_fake_B_raw.npy', 'visual_real_edges.npy', 'pred1_h.npy', 'pred2_h.npy', 'params_G.npy',
+                                'params_D_1.npy', 'loss_G_GAN.npy', 'loss_h.npy'])
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+        assert a[n].dtype == (np.float64 if n.startswith('loss_') else np.float32), n
+    assert float(a['loss_h.npy']) == 1.0 / 3.0 and a['pred2_h.npy'].shape == (1, 16)
+    assert np.array_equal(a['params_G.npy'], np.r_[np.arange(10), np.ones(3)].astype(np.float32))
+    big = a['params_D_1.npy']            # w = arange(3 << 20), then the 3-element bias: a sorted sample without repeats, in w's part increasing
+    assert big.shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(big[:-3]) > 0) and big.max() < (3 << 20)
+    assert a['visual_fake_B.npy'].shape == (bench.DUMP_MAX_ELEMS,) and not np.array_equal(a['visual_fake_B.npy'], a['visual_fake_B_raw.npy'])
+
+
 def test_oracle_data_parallel_step_is_the_mean_of_rank_gradients():
     """oracle.restate.pix2pix_step_data_parallel (the spec the GPU ranks are compared with): with the SAME batch on
     both ranks it must reproduce the single-process step bit for bit (the mean of two equal gradients); with different batches both

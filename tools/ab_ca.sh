@@ -14,4 +14,4 @@ for r in csv.DictReader(open('gpurun_out/cb_$v/p_kernel_stats.csv')):
 PY
 done
 unset HV_CA_GS_XCD HV_CA_PBWD_VEC
-for v in 0 1 0 1; do HV_CA_GS_XCD=$v HV_CA_PBWD_VEC=$v python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$v', d['ms_per_step'], d['fine_generator_forward']['graph_replay']['ms'])"; done
+for v in 0 1 0 1; do HV_CA_GS_XCD=$v HV_CA_PBWD_VEC=$v python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-extra 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$v', d['ms_per_step'], d['fine_generator_forward']['graph_replay']['ms'])"; done
