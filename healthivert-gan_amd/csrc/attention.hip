@@ -110,8 +110,7 @@ __global__ __launch_bounds__(256) void ca_patch_tile_kernel(const ST_* __restric
     }
 }
 static bool ca_tile_ok(const float* src, int C, int s_ld, const float* lt) {
-    static const int enabled = getenv("HV_CA_TILE") ? atoi(getenv("HV_CA_TILE")) : 1;   // A/B knob
-    return enabled && (C & 3) == 0 && (s_ld & 3) == 0 && !((uintptr_t)src & 15) && !((uintptr_t)lt & 15);
+    return (C & 3) == 0 && (s_ld & 3) == 0 && !((uintptr_t)src & 15) && !((uintptr_t)lt & 15);
 }
 
 static int ca_patches_impl(const void* f, int f_f16, int B, int H, int W, int C, int f_ld, float* fd, float* wp, float* wpT, float* norm,
@@ -419,9 +418,8 @@ static bool at_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 extern "C" int hv_ca_fuse(const float* S, float* out, int B, int h, int w, int adjoint, void* stream) {
     if (!S || !out || S == out || B <= 0 || h <= 0 || w <= 0) return HV_ERR_ARG;
     if (at_pow2(h) && at_pow2(w) && (long long)h * w <= 32768) {
-        static const int tile32 = getenv("HV_CA_FUSE_TILE") ? atoi(getenv("HV_CA_FUSE_TILE")) : 1;      // A/B knob
-        if (tile32 && h == 32 && w == 32 && B <= 65535 && !((uintptr_t)out & 15)) {
-            static const int xcd_order = getenv("HV_CA_FUSE_XCD") ? atoi(getenv("HV_CA_FUSE_XCD")) : 1;      // A/B knob (same bits either way)
+        if (h == 32 && w == 32 && B <= 65535 && !((uintptr_t)out & 15)) {
+            const int xcd_order = 1;      // (the plain tile order gives the same bits)
             if (adjoint) hipLaunchKernelGGL(ca_fuse_adj_tile32_kernel, dim3(1024 * B), dim3(256), 0, (hipStream_t)stream, S, out, xcd_order);
             else hipLaunchKernelGGL(ca_fuse_tile32_kernel, dim3(1024 * B), dim3(256), 0, (hipStream_t)stream, S, out, xcd_order);
             HV_LAUNCH_CHECK();
@@ -618,10 +616,9 @@ __global__ __launch_bounds__(256) void ca_softmax_bwd_wave_kernel(const float* _
             make_float4(scale * mv[k].x * av[k].x * (gv[k].x - dot), scale * mv[k].y * av[k].y * (gv[k].y - dot), scale * mv[k].z * av[k].z * (gv[k].z - dot),
                         scale * mv[k].w * av[k].w * (gv[k].w - dot));
 }
-static const int ca_sm_wave = getenv("HV_CA_SOFTMAX_WAVE") ? atoi(getenv("HV_CA_SOFTMAX_WAVE")) : 1;      // A/B knob
 template <typename AT>
 static bool ca_softmax_wave_launch(const float* S, const float* mm, long long mm_bs, AT* A, int B, int L, float scale, int* argmax, hipStream_t s) {
-    if (!ca_sm_wave || (((uintptr_t)S | (uintptr_t)mm | (uintptr_t)A) & 15) || (mm_bs & 3)) return false;
+    if ((((uintptr_t)S | (uintptr_t)mm | (uintptr_t)A) & 15) || (mm_bs & 3)) return false;
     const long long rows = (long long)B * L;
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (L == 1024) hipLaunchKernelGGL((ca_softmax_wave_kernel<AT, 4>), grid, dim3(256), 0, s, S, mm, A, scale, argmax, mm_bs, rows);
@@ -632,7 +629,7 @@ static bool ca_softmax_wave_launch(const float* S, const float* mm, long long mm
 }
 template <typename AT>
 static bool ca_softmax_bwd_wave_launch(const float* dA, const AT* A, const float* mm, float* dS, int B, int L, float scale, hipStream_t s) {
-    if (!ca_sm_wave || (((uintptr_t)dA | (uintptr_t)mm | (uintptr_t)A | (uintptr_t)dS) & 15)) return false;
+    if ((((uintptr_t)dA | (uintptr_t)mm | (uintptr_t)A | (uintptr_t)dS) & 15)) return false;
     const long long rows = (long long)B * L;
     const dim3 grid((unsigned)((rows + 3) / 4));
     if (L == 1024) hipLaunchKernelGGL((ca_softmax_bwd_wave_kernel<AT, 4>), grid, dim3(256), 0, s, dA, A, mm, dS, scale, rows);
@@ -745,8 +742,7 @@ __global__ __launch_bounds__(256) void transpose64_h_kernel(const IT* __restrict
 }
 template <typename IT>
 static bool transpose64_launch(const IT* src, _Float16* dst, int B, int R, int C, hipStream_t s) {
-    static const int on = getenv("HV_TRANSPOSE64") ? atoi(getenv("HV_TRANSPOSE64")) : 1;      // A/B knob
-    if (!on || (R & 7) || (C & 7) || (((uintptr_t)src | (uintptr_t)dst) & 15) || B > 65535) return false;
+    if ((R & 7) || (C & 7) || (((uintptr_t)src | (uintptr_t)dst) & 15) || B > 65535) return false;
     hipLaunchKernelGGL(transpose64_h_kernel<IT>, dim3(hv_cdiv(C, 64), hv_cdiv(R, 64), B), dim3(256), 0, s, src, dst, R, C);
     return true;
 }
@@ -840,8 +836,7 @@ extern "C" int hv_ca_score_backward_prep(const float* dS, const float* S0, const
                                          int B, int L, void* stream) {
     if (!dS || !S0 || !norm || !rnorm || !Gs || !coef || B <= 0 || L <= 0 || (L & 31)) return HV_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    static const int gs_xcd = getenv("HV_CA_GS_XCD") ? atoi(getenv("HV_CA_GS_XCD")) : 1;      // A/B knob (same bits either way)
-    if (gs_xcd && (L / 32) % 8 == 0 && (long long)(L / 32) * (L / 32) * B < (1ll << 31))
+    if ((L / 32) % 8 == 0 && (long long)(L / 32) * (L / 32) * B < (1ll << 31))
         hipLaunchKernelGGL(ca_gs_kernel, dim3((L / 32) * (L / 32) * B), dim3(256), 0, s, dS, rnorm, Gs, L, 1);
     else
         hipLaunchKernelGGL(ca_gs_kernel, dim3(L / 32, L / 32, B), dim3(256), 0, s, dS, rnorm, Gs, L, 0);
@@ -1065,9 +1060,8 @@ __global__ __launch_bounds__(256) void ca_patches_bwd_vec_kernel(const float* __
 extern "C" int hv_ca_patches_backward(const float* dwp, const float* wp, const float* coef, float* df, int B, int H, int W, int C, int df_ld,
                                       int accumulate, void* stream) {
     if (!dwp || !wp || !coef || !df || B <= 0 || H <= 0 || W <= 0 || C <= 0 || ((H | W) & 1) || df_ld < C) return HV_ERR_ARG;
-    static const int pb_vec = getenv("HV_CA_PBWD_VEC") ? atoi(getenv("HV_CA_PBWD_VEC")) : 1;      // A/B knob (same bits either way)
     const long long n4 = (long long)B * (H / 2) * (W / 2) * (C / 4);
-    if (pb_vec && accumulate && !(C & 3) && !(df_ld & 3) && !(((uintptr_t)dwp | (uintptr_t)wp | (uintptr_t)df) & 15) && n4 < (1ll << 31)) {
+    if (accumulate && !(C & 3) && !(df_ld & 3) && !(((uintptr_t)dwp | (uintptr_t)wp | (uintptr_t)df) & 15) && n4 < (1ll << 31)) {
         long long blocks = (n4 + 255) / 256;
         if (blocks > 65536) blocks = 65536;
         hipLaunchKernelGGL(ca_patches_bwd_vec_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, dwp, wp, coef, df, H, W, C, df_ld, (int)n4);

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void ca_gram_norm_kernel(const float* __restri
 // NLB grid rows of l per round: a row of S0 then leaves as NLB * w * 4 bytes contiguous per store instruction (128-byte segments 4 KB apart held the kernel at
 // 1.2 TB/s: 52-62 us whatever the round structure)
 template <int BW, int NLB>
-__global__ __launch_bounds__(256) void ca_gram_scores_kernel(const _Float16* __restrict__ fd_h, const float* __restrict__ rnorm, int h, int lg, float* __restrict__ S0, int diag) {
+__global__ __launch_bounds__(256) void ca_gram_scores_kernel(const _Float16* __restrict__ fd_h, const float* __restrict__ rnorm, int h, int lg, float* __restrict__ S0, int /*unused*/) {
     constexpr int C = 64, NT = BW / 16, KS = C / 32, SW = NLB * BW;      // SW: strip width (columns per round)
     constexpr int TILES = NT * NT * NLB, TPW = TILES / 4;                  // MFMA tiles per wave and round: tile t -> (block j, mi, ni)
     __shared__ float Gt[2][NLB][BW][BW + 1];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void ca_gram_scores_kernel(const _Float16* __r
     for (int rd = 0; rd < rounds; ++rd, buf ^= 1) {
         const int ly = lw0 + rd;                 // this wave's grid row of l in this round
         load_row(3, rd + 1 < rounds ? ly + 2 : -1);
-        if (!(diag & 2)) {
+        {
 #pragma unroll
             for (int m = 0; m < NMI; ++m)
 #pragma unroll
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void ca_gram_scores_kernel(const _Float16* __r
         for (int k = 0; k < NIT; ++k) {
             const int it = threadIdx.x + k * 256, r = it / (SW / 4), c = (it - r * (SW / 4)) * 4, j = c / BW, c0 = c - j * BW;
             const int lyj = ly0 + (NLB == 4 ? j * rounds : 0) + rd;
-            if (lyj < ly1 && !(diag & 1))
+            if (lyj < ly1)
                 *reinterpret_cast<float4*>(Sb + (long long)(py * w + r) * L + lyj * w + c0) =
                     make_float4(gram_box<BW>(Gt[buf][j], r, c0) * rn[k].x, gram_box<BW>(Gt[buf][j], r, c0 + 1) * rn[k].y, gram_box<BW>(Gt[buf][j], r, c0 + 2) * rn[k].z,
                                 gram_box<BW>(Gt[buf][j], r, c0 + 3) * rn[k].w);
@@ -184,14 +184,12 @@ extern "C" int hv_ca_gram_scores(const void* fd_h, const float* q, int B, int h,
     const long long n = (long long)B * h * w;
     hipLaunchKernelGGL(ca_gram_norm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, h, w, n, norm, rnorm);
     HV_LAUNCH_CHECK();
-    static const int lg_env = getenv("HV_CA_GRAM_LG") ? atoi(getenv("HV_CA_GRAM_LG")) : 0;      // tuning knob: grid rows of l per workgroup
-    static const int diag = getenv("HV_GRAM_DIAG") ? atoi(getenv("HV_GRAM_DIAG")) : 0;      // timing-only: 1 no stores, 2 no operand loads / MFMAs
-    int lg = lg_env > 0 ? lg_env : 16;
+    int lg = 16;      // grid rows of l per workgroup
     while (lg > 4 && (long long)B * h * ((h + lg - 1) / lg) < 1024) lg >>= 1;      // keep >= 4 workgroups per CU in flight
     lg = (lg + 3) / 4 * 4;
     const dim3 grid((unsigned)(B * h * ((h + lg - 1) / lg)));
-    if (w == 32) hipLaunchKernelGGL((ca_gram_scores_kernel<32, 4>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(fd_h), rnorm, h, lg, S0, diag);
-    else hipLaunchKernelGGL((ca_gram_scores_kernel<64, 1>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(fd_h), rnorm, h, lg, S0, diag);
+    if (w == 32) hipLaunchKernelGGL((ca_gram_scores_kernel<32, 4>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(fd_h), rnorm, h, lg, S0, 0);
+    else hipLaunchKernelGGL((ca_gram_scores_kernel<64, 1>), grid, dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(fd_h), rnorm, h, lg, S0, 0);
     HV_LAUNCH_CHECK();
     return HV_OK;
 }
@@ -310,10 +308,8 @@ extern "C" int hv_ca_gram_backward(const float* Gs, const void* fd_h, const void
     if (!Gs || !fd_h || !fdT_h || !coef || !df || B <= 0 || h <= 0 || w <= 0 || df_ld < C) return HV_ERR_ARG;
     if (C != 64 || (w != 32 && w != 64) || ((uintptr_t)Gs & 15) || ((uintptr_t)fdT_h & 15) || (long long)B * h >= (1ll << 31)) return HV_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(B * h));
-    static const int nby = getenv("HV_CA_GRAM_NBY") ? atoi(getenv("HV_CA_GRAM_NBY")) : 2;      // A/B knob
-    static const int xcd_env = getenv("HV_CA_GRAM_BWD_XCD") ? atoi(getenv("HV_CA_GRAM_BWD_XCD")) : 1;      // A/B knob (same bits either way)
-    const int xcd_rows = xcd_env && !(h & 7);
-    if (w == 32 && nby == 2 && !(h & 1))
+    const int xcd_rows = !(h & 7);
+    if (w == 32 && !(h & 1))
         hipLaunchKernelGGL((ca_gram_backward_kernel<32, 2>), grid, dim3(256), 0, (hipStream_t)stream, Gs, reinterpret_cast<const _Float16*>(fd_h),
                            reinterpret_cast<const _Float16*>(fdT_h), coef, h, df, df_ld, xcd_rows);
     else if (w == 32)

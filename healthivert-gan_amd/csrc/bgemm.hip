@@ -306,15 +306,13 @@ static int bgemm_impl(const void* A, int a_f16, int lda, long long strideA, cons
     k.A = A; k.B = B; k.C = C; k.colscale = colscale;
     k.sA = strideA; k.sB = strideB; k.sC = strideC; k.sS = strideS;
     k.lda = lda; k.ldb = ldb; k.ldc = ldc; k.M = M; k.N = N; k.K = K; k.batch = batch; k.alpha = alpha; k.b_split = b_split; k.c_f16 = c_f16 ? 1 : 0;
-    static const int xcd = getenv("HV_XCD") ? atoi(getenv("HV_XCD")) : 1;
     hipStream_t s = (hipStream_t)stream;
     {   // fp16 x fp16 with whole 64-deep stages and enough 256 x 256 tiles to go round: the LDS-DMA form
-        static const int dma = getenv("HV_BGEMM_DMA") ? atoi(getenv("HV_BGEMM_DMA")) : 1;      // A/B knob
         const long long t256 = (long long)hv_cdiv(M, 256) * hv_cdiv(N, 256) * batch;
-        if (dma && a_f16 && b_f16 && !(K & 63) && M >= 256 && N >= 256 && t256 >= 128 && t256 < (1ll << 31) && (size_t)M * lda * 2 < (1ull << 31) &&
+        if (a_f16 && b_f16 && !(K & 63) && M >= 256 && N >= 256 && t256 >= 128 && t256 < (1ll << 31) && (size_t)M * lda * 2 < (1ull << 31) &&
             (size_t)N * ldb * 2 < (1ull << 31)) {
             k.tiles_m = hv_cdiv(M, 256); k.tiles_n = hv_cdiv(N, 256);
-            k.swizzle = (xcd && batch % 8 == 0) ? 1 : 0;
+            k.swizzle = batch % 8 == 0 ? 1 : 0;
             static bool raised = false;
             if (!raised) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bgemm_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -330,7 +328,7 @@ static int bgemm_impl(const void* A, int a_f16, int lda, long long strideA, cons
     k.tiles_m = hv_cdiv(M, 128); k.tiles_n = hv_cdiv(N, BN);
     const long long tiles = (long long)k.tiles_m * k.tiles_n * batch;
     if (tiles >= (1ll << 31)) return HV_ERR_UNSUPPORTED;
-    k.swizzle = (xcd && batch % 8 == 0) ? 1 : 0;
+    k.swizzle = batch % 8 == 0 ? 1 : 0;
     const dim3 grid((unsigned)tiles);
 #define HV_BG(BN_)                                                                                                       \
     do {                                                                                                                 \
@@ -455,9 +453,8 @@ __global__ __launch_bounds__(256) void ca_fold_vec_kernel(const void* __restrict
 static int ca_fold_impl(const void* src, int src_f16, void* dst, int dst_f16, int B, int H, int W, int C, int dst_ld, float alpha, int accumulate, void* stream) {
     if (!src || !dst || B <= 0 || H <= 0 || W <= 0 || C <= 0 || ((H | W) & 1) || dst_ld < C) return HV_ERR_ARG;
     const long long n8 = (long long)B * H * W * (C / 8);
-    static const int vec = getenv("HV_CA_FOLD_VEC") ? atoi(getenv("HV_CA_FOLD_VEC")) : 1;      // A/B knob
     const bool vec_ok = !(C & 7) && !(dst_ld & 7) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15) && n8 < (1ll << 31);
-    if ((vec || src_f16) && vec_ok) {
+    if (vec_ok) {
         long long blocks = (n8 + 255) / 256;
         if (blocks > 65536) blocks = 65536;
         const dim3 grid((unsigned)blocks);

@@ -440,7 +440,7 @@ __global__ __launch_bounds__(512, 2) void conv_g4_kernel(const G4K p) {
 // a ring of three buffers, the (TH + 3) x 20-pixel patch of a 32-channel chunk arrives ONCE for its four filter rows (two buffers).  conv_halo2_kernel
 // fetched 1 MB of filters per 128-pixel x 64/128-channel tile straight into registers (537 MB of L2 -> CU traffic per launch, 2x the tensors'
 // HBM bytes); a 256-pixel x 128-channel tile halves that and both operands come from LDS.
-template <int DG, int MT, bool SPREAD>
+template <int DG, int MT>
 __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
     constexpr int TW = 16, TH = 4 * MT, PH = TH + 3, PW = 20;                // patch rows of 20 pixels (19 used): a row shift moves the swizzle phase by its parity only
     constexpr int NBP = (PH * PW + 15) / 16, BPW = (NBP + 7) / 8;
@@ -487,7 +487,7 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
             lds_dma16(wsrc, (lds_ptr)(As + ab * ABUF + f * 512), (unsigned)lane * 16u, rb * (int)p.w_rb + ((kh * 4 + kw) * Cin + kc * 32) * 32);
         }
     };
-    // SPREAD: one piece at a time, in front of each tap's MFMAs (below); `live` = false sends the piece out of range (zeros into a free buffer), so that the
+    // one piece at a time, in front of each tap's MFMAs (below); `live` = false sends the piece out of range (zeros into a free buffer), so that the
     // instruction count a wave's vmcnt waits rely on is the same for every sub-chunk
     auto issueA1 = [&](int kc, int kh, int ab, int i, bool live) __attribute__((always_inline)) {
         const int f = wave + 8 * i, rbw = f >> 2, kw = f & 3;
@@ -535,10 +535,6 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
         const int kc2 = kc + (kh >= 2 ? 1 : 0);
         const int ab2 = ab == 0 ? 2 : ab - 1;                                 // (s + 2) % 3
         const bool live = s_ + 2 < NS;
-        if (!SPREAD && live) {
-            issueA(kc2, kh2, ab2);
-            if (kh == 2) issueB(kc + 1, (kc + 1) & 1);
-        }
         const _Float16* Ab = As + ab * ABUF + aoff;
         const _Float16* Bb = Bs + (kc & 1) * BBUF + rs * PW * 32;
         auto frags = [&](int kw, int buf) __attribute__((always_inline)) {
@@ -551,11 +547,10 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
 #pragma unroll
         for (int kw = 0; kw < 4; ++kw) {
             __builtin_amdgcn_sched_barrier(0);
-            if (SPREAD) {      // eight waves issuing their 4 (+ BPW) pieces at once stall in the issue: the texture path takes one wave-instruction at a time
-                issueA1(kc2, kh2, ab2, kw, live);
-                if (kh == 2 && kw < BPW) issueB1(kc + 1, (kc + 1) & 1, kw, live);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            // eight waves issuing their 4 (+ BPW) pieces at once stall in the issue: the texture path takes one wave-instruction at a time
+            issueA1(kc2, kh2, ab2, kw, live);
+            if (kh == 2 && kw < BPW) issueB1(kc + 1, (kc + 1) & 1, kw, live);
+            __builtin_amdgcn_sched_barrier(0);
             if (kw + 1 < 4) frags(kw + 1, (kw + 1) & 1);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
@@ -571,12 +566,8 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
             __builtin_amdgcn_sched_barrier(0);
         }
         // newest DMA instructions of this wave that may stay in flight: those of sub-chunk s + 2 (issued above)
-        if (SPREAD || live) {
-            if (kh == 2) __builtin_amdgcn_s_waitcnt(0x0070 | ((4 + BPW) & 15));
-            else __builtin_amdgcn_s_waitcnt(0x0070 | 4);
-        } else {
-            __builtin_amdgcn_s_waitcnt(0x0070);
-        }
+        if (kh == 2) __builtin_amdgcn_s_waitcnt(0x0070 | ((4 + BPW) & 15));
+        else __builtin_amdgcn_s_waitcnt(0x0070 | 4);
         __builtin_amdgcn_s_barrier();
     };
     // prologue: sub-chunks 0 and 1 (+ the patch of chunk 0) in flight; wait for sub-chunk 0's
@@ -595,7 +586,7 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
         sub(kc, std::integral_constant<int, 2>(), ab); ab = ab == 2 ? 0 : ab + 1;
         sub(kc, std::integral_constant<int, 3>(), ab); ab = ab == 2 ? 0 : ab + 1;
     }
-    if (SPREAD) __builtin_amdgcn_s_waitcnt(0x0F70);      // the last sub-chunks' out-of-range pieces (zeros) land before the epilogue reuses the buffers
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // the last sub-chunks' out-of-range pieces (zeros) land before the epilogue reuses the buffers
     __syncthreads();
 #ifdef G4_STAMPS
     st[2] = __builtin_amdgcn_s_memrealtime();
@@ -612,11 +603,8 @@ __device__ __forceinline__ void conv_g4s1_body(const G4K& p) {
 #endif
 }
 
-// (two kernels over one body so that the profiled name of the production form stays conv_g4s1_kernel<DG, MT>)
 template <int DG, int MT>
-__global__ __launch_bounds__(512, 2) void conv_g4s1_kernel(const G4K p) { conv_g4s1_body<DG, MT, true>(p); }
-template <int DG, int MT>
-__global__ __launch_bounds__(512, 2) void conv_g4s1_headissue_kernel(const G4K p) { conv_g4s1_body<DG, MT, false>(p); }      // HV_G4S1_SPREAD=0: every piece at the sub-chunk's head
+__global__ __launch_bounds__(512, 2) void conv_g4s1_kernel(const G4K p) { conv_g4s1_body<DG, MT>(p); }
 
 template <int DG, int MT>
 static int launch_g4s1(G4K& k, int ny, hipStream_t s) {
@@ -626,8 +614,7 @@ static int launch_g4s1(G4K& k, int ny, hipStream_t s) {
     static_assert(lds <= 160 * 1024, "LDS");
     k.tiles_x = hv_cdiv(k.Wc, 16);
     k.tiles = k.tiles_x * hv_cdiv(k.Hc, TH);
-    static const int spread = getenv("HV_G4S1_SPREAD") ? atoi(getenv("HV_G4S1_SPREAD")) : 1;      // A/B knob (same bits): LDS-DMA pieces issued tap by tap
-    auto kern = spread ? conv_g4s1_kernel<DG, MT> : conv_g4s1_headissue_kernel<DG, MT>;
+    auto kern = conv_g4s1_kernel<DG, MT>;
     static bool raised = false;
     if (!raised) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -667,8 +654,6 @@ static int launch_g4(G4K& k, int ny, hipStream_t s) {
 
 // workgroups of a launch and floats of its statistics output (hv_conv2d_stats_floats)
 static int g4_tile_rows(int B, int Hc, int Wc, int ny) {
-    static const int force = getenv("HV_G4_MT") ? atoi(getenv("HV_G4_MT")) : 0;
-    if (force == 2 || force == 4) return 4 * force;
     return (long long)B * hv_cdiv(Hc, 16) * hv_cdiv(Wc, 16) * ny >= 200 ? 16 : 8;
 }
 
@@ -676,13 +661,10 @@ static int g4_tile_rows(int B, int Hc, int Wc, int ny) {
 // fragment-ordered filters.  hv_conv2d_g4 launches exactly when it holds, and hv_conv2d_g4_stats_floats promises a statistics epilogue only then.
 size_t hv_conv2d_g4_bstats_parts(const hv_conv_desc* d);
 static bool g4_eligible(const hv_conv_desc* d) {
-    static const int on = getenv("HV_CONV_G4") ? atoi(getenv("HV_CONV_G4")) : 3;      // bit 0: forward, bit 1: data gradient
-    if (!(on & (d->transposed ? 2 : 1))) return false;
     if (d->KH != 4 || d->KW != 4 || (d->stride != 2 && d->stride != 1) || d->pad != 1 || d->dil != 1 || d->in_shift || d->w_bstride || d->ch_scale) return false;
     if (d->precision != HV_F16 || !d->w_f16_tiled || !d->x_f16 || !d->y_f16 || d->accumulate > 1) return false;
     if (d->stride == 1) {
-        static const int s1 = getenv("HV_CONV_G4S1") ? atoi(getenv("HV_CONV_G4S1")) : 3;      // bit 0: forward, bit 1: data gradient
-        if (!(s1 & (d->transposed ? 2 : 1)) || (d->Cout & 127) || (d->Cin & 31)) return false;
+        if ((d->Cout & 127) || (d->Cin & 31)) return false;
     }
     if ((d->Cin & 31) || (d->Cout & 63) || (!d->transposed && (d->Cout & 127))) return false;
     if ((d->x_ld & 7) || (d->x_coff & 7) || ((uintptr_t)d->x & 15) || (d->y_ld & 7) || (d->y_coff & 7) || ((uintptr_t)d->y & 15) || ((uintptr_t)d->w_f16_tiled & 15))
@@ -698,7 +680,10 @@ static bool g4_eligible(const hv_conv_desc* d) {
 int hv_conv2d_g4(const hv_conv_desc* d, hipStream_t s) {
     if (!g4_eligible(d)) return HV_ERR_UNSUPPORTED;
     G4K k;
-    k.dbg = getenv("HV_G4_DBG") ? atoi(getenv("HV_G4_DBG")) : 0;
+    k.dbg = 0;
+#ifdef G4_STAMPS
+    if (getenv("HV_G4_DBG")) k.dbg = atoi(getenv("HV_G4_DBG"));
+#endif
     k.x = d->x; k.w = reinterpret_cast<const _Float16*>(d->w_f16_tiled); k.bias = d->bias; k.y = d->y; k.mul_src = d->mul_src;
     k.stats = d->transposed ? nullptr : d->stats;
     k.bn_x = nullptr; k.bn_stats = nullptr; k.bstats = nullptr; k.bn_x_ld = k.bn_x_coff = 0; k.bn_ipg = 1;

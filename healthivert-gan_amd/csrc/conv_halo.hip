@@ -292,9 +292,8 @@ static int launch_halo_t(const HaloK& k, int tiles, int maxpatch, hipStream_t s)
     hv_path_note = 2;
     HV_KNAME("conv_halo_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s>", TH, TW, BN, WM, WN, TG, CK, PMAX, XH ? "true" : "false");
     HaloK kk = k;
-    {   // coalesced fp16 epilogue through LDS (HV_HALO2_EP16=0: direct 8-byte stores)
-        static const int ep16 = getenv("HV_HALO2_EP16") ? atoi(getenv("HV_HALO2_EP16")) : 1;
-        kk.ep16 = (ep16 && kk.y_half && kk.accumulate <= 1 && !(kk.Cout & 7) && !(kk.y_ld & 7) && !(kk.y_coff & 7) && !((uintptr_t)kk.y & 15) &&
+    {   // coalesced fp16 epilogue through LDS
+        kk.ep16 = (kk.y_half && kk.accumulate <= 1 && !(kk.Cout & 7) && !(kk.y_ld & 7) && !(kk.y_coff & 7) && !((uintptr_t)kk.y & 15) &&
                    lds >= (size_t)TH * TW * (BN + 8) * sizeof(_Float16)) ? 1 : 0;
         if (kk.ep16 && kk.mul_src && kk.mul_half && !(kk.mul_ld & 7) && !(kk.mul_coff & 7) && !((uintptr_t)kk.mul_src & 15)) kk.ep16 = 2;
     }
@@ -321,8 +320,6 @@ static int dispatch_halo_bn(HaloK& k, int maxpatch, hipStream_t s) {
     int bn = k.Cout <= 16 ? 16 : k.Cout <= 32 ? 32 : k.Cout <= 64 ? 64 : 128;
     // one wave per SIMD cannot hide the staging latency: prefer >= 2 workgroups per CU over the widest tile
     if (bn == 128 && (long long)tiles * hv_cdiv(k.Cout, 128) < 512) bn = 64;
-    static const char* force = getenv("HV_HALO_BN");   // tuning knob (tools/bench_conv.py)
-    if (force && k.Cout > 64) bn = atoi(force) == 64 ? 64 : 128;
     // stride-2 patches are 4x larger: prefetch them with more registers and halve the weight tile so that two
     // workgroups still fit in a CU's LDS
     constexpr int PM = S2 ? 20 : 11, TD = S2 ? 2 : 1;
@@ -343,8 +340,7 @@ int hv_conv2d_halo(const hv_conv_desc* d, const void* w_f16, hipStream_t s) {
     hv_conv_desc dd;
     const int Hf = d->H, Wf = d->W, Hof = d->Ho, Wof = d->Wo;
     if (dil != 1) {
-        static const int dilated = getenv("HV_HALO_DILATED") ? atoi(getenv("HV_HALO_DILATED")) : 1;      // A/B knob
-        if (!dilated || (dil != 2 && dil != 4 && dil != 8 && dil != 16) || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != dil || d->in_shift) return HV_ERR_UNSUPPORTED;
+        if ((dil != 2 && dil != 4 && dil != 8 && dil != 16) || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != dil || d->in_shift) return HV_ERR_UNSUPPORTED;
         if (d->H % dil || d->W % dil || d->Ho != d->H || d->Wo != d->W || (d->Cin & 31) || d->Cout > 64 || d->Cout <= 32) return HV_ERR_UNSUPPORTED;
         dd = *d;
         dd.H /= dil; dd.W /= dil; dd.Ho /= dil; dd.Wo /= dil; dd.pad = 1; dd.dil = 1;
@@ -355,9 +351,8 @@ int hv_conv2d_halo(const hv_conv_desc* d, const void* w_f16, hipStream_t s) {
     if (!d->x_f16) return HV_ERR_UNSUPPORTED;      // halo-tiled kernels are built for fp16 storage (an fp32 input with fp16 operands: gather kernel)
     HaloK k;
     k.x_half = d->x_f16 ? 1 : 0; k.y_half = d->y_f16 ? 1 : 0; k.mul_half = d->mul_f16 ? 1 : 0;
-    {   // fragment-ordered filters (A/B knob HV_W_TILED=0: plain rows)
-        static const int tiled = getenv("HV_W_TILED") ? atoi(getenv("HV_W_TILED")) : 1;
-        k.wt = (tiled && d->w_f16_tiled && !((uintptr_t)d->w_f16_tiled & 15)) ? reinterpret_cast<const _Float16*>(d->w_f16_tiled) : nullptr;
+    {   // fragment-ordered filters
+        k.wt = (d->w_f16_tiled && !((uintptr_t)d->w_f16_tiled & 15)) ? reinterpret_cast<const _Float16*>(d->w_f16_tiled) : nullptr;
         k.wt_bytes = (unsigned)((size_t)hv_cdiv(d->Cout, 16) * 16 * d->KH * d->KW * d->Cin * sizeof(_Float16));
     }
     const size_t xs = k.x_half ? 2 : 4;
@@ -417,13 +412,10 @@ int hv_conv2d_halo(const hv_conv_desc* d, const void* w_f16, hipStream_t s) {
         if (wgs < 400) small_tile = true;
     }
     // 3x3 layers with whole 32-channel chunks: the 8x16-pixel conv_halo2 instantiations (twice the workgroups, half the accumulators)
-    // measured faster than 8x32 on the 128x128 and 256x256 maps as well (53 vs 65, 22 vs 29, 36 vs 51 us); HV_HALO_TW16=0 restores 8x32
-    static const int tw16 = getenv("HV_HALO_TW16") ? atoi(getenv("HV_HALO_TW16")) : 1;
-    static const int tw16r = getenv("HV_HALO_TW16R") ? atoi(getenv("HV_HALO_TW16R")) : 1;   // also for 16-channel chunks (measured: 49 vs 54, 31 vs 42, 65 vs 81, 115 vs 105 us)
-    if (tw16 && k.bstep == 1 && d->KH == 3 && d->KW == 3 && ((d->Cin & 31) == 0 || (tw16r && d->Cout <= 64))) small_tile = true;
-    static const int tw16x = getenv("HV_HALO_TW16X") ? atoi(getenv("HV_HALO_TW16X")) : 1;   // bit 1 = stride-2 data gradient classes (54 vs 61 us), bit 2 = 5x5 (no gain)
-    if ((tw16x & 1) && d->transposed && d->stride == 2 && d->KH == 4) small_tile = true;
-    if ((tw16x & 2) && d->KH == 5 && k.bstep == 1) small_tile = true;
+    // measured faster than 8x32 on the 128x128 and 256x256 maps as well (53 vs 65, 22 vs 29, 36 vs 51 us); also for 16-channel chunks up to
+    // 64 output channels (49 vs 54, 31 vs 42, 65 vs 81, 115 vs 105 us) and for the stride-2 data gradient classes (54 vs 61 us); 5x5 layers: no gain
+    if (k.bstep == 1 && d->KH == 3 && d->KW == 3 && ((d->Cin & 31) == 0 || d->Cout <= 64)) small_tile = true;
+    if (d->transposed && d->stride == 2 && d->KH == 4) small_tile = true;
     const int TH = 8, TW = small_tile ? 16 : 32;
     int maxpatch = 0;
     for (int c = 0; c < k.ncls; ++c) {
@@ -447,21 +439,17 @@ int hv_conv2d_halo(const hv_conv_desc* d, const void* w_f16, hipStream_t s) {
         if ((long long)d->B * k.img_stride >= (1ll << 29)) return HV_ERR_UNSUPPORTED;
         k.x_bytes = (unsigned)((size_t)d->B * k.img_stride * xs);
         {   // filters-in-LDS form: residue sub-grids of at least a tile, or whole residue classes packed into a tile (conv_lfd_kernel)
-            static const int lf8 = getenv("HV_LF_DIL8") ? atoi(getenv("HV_LF_DIL8")) : 1;      // A/B knob: 0 = round 3's rule (d <= 4 only)
-            if (dil <= 4 || lf8) {
-                const int rc = hv_convlf_launch(k, d->KH, d->KW, s);
-                if (rc != HV_ERR_UNSUPPORTED) return rc;
-            }
+            const int rc = hv_convlf_launch(k, d->KH, d->KW, s);
+            if (rc != HV_ERR_UNSUPPORTED) return rc;
         }
         if (dil > 8) return HV_ERR_UNSUPPORTED;      // (d = 16 elsewhere: the gather kernel, as before)
         return hv_halo2_launch(k, TW, d->KH, d->KW, maxpatch, s);      // (conv_halo_kernel has no pixel step)
     }
-    static const bool halo2 = !(getenv("HV_HALO2") && atoi(getenv("HV_HALO2")) == 0);   // A/B knob
     {   // filters-in-LDS form (3x3 stride-1 layers with whole-chunk channel counts)
         const int rc = hv_convlf_launch(k, d->KH, d->KW, s);
         if (rc != HV_ERR_UNSUPPORTED || d->pool2 || d->x1) return rc;
     }
-    if (halo2) {   // weights-in-registers form where an instantiation exists
+    {   // weights-in-registers form where an instantiation exists
         const int rc = hv_halo2_launch(k, TW, d->KH, d->KW, maxpatch, s);
         if (rc != HV_ERR_UNSUPPORTED) return rc;
     }

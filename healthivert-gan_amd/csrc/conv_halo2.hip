@@ -365,9 +365,8 @@ static int launch2(HaloK& k, hipStream_t s, int th0 = 8, int tw0 = TW) {
     hv_path_note = 3;
     HV_KNAME("conv_halo2_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %s>", TH, TW, BN, WM, WN, CK, BSTEP, SPAN, D, k.x_half ? "true" : "false");
     HaloK kk = k;       // the kernel's view: the tiled table IS its filter table (k itself stays as it is for a fallback kernel)
-    {   // coalesced fp16 epilogue through LDS (HV_HALO2_EP16=0: direct 8-byte stores)
-        static const int ep16 = getenv("HV_HALO2_EP16") ? atoi(getenv("HV_HALO2_EP16")) : 1;
-        kk.ep16 = (ep16 && kk.y_half && kk.accumulate <= 1 && !(kk.Cout & 7) && !(kk.y_ld & 7) && !(kk.y_coff & 7) && !((uintptr_t)kk.y & 15) &&
+    {   // coalesced fp16 epilogue through LDS
+        kk.ep16 = (kk.y_half && kk.accumulate <= 1 && !(kk.Cout & 7) && !(kk.y_ld & 7) && !(kk.y_coff & 7) && !((uintptr_t)kk.y & 15) &&
                    lds >= (size_t)TH * TW * (BN + 8) * sizeof(_Float16)) ? 1 : 0;
         // the act' multiplier read as 16-byte pieces in the second stage (a lane's own 8-byte loads are 32-byte fragments of the rows, like its stores)
         if (kk.ep16 && kk.mul_src && kk.mul_half && !(kk.mul_ld & 7) && !(kk.mul_coff & 7) && !((uintptr_t)kk.mul_src & 15)) kk.ep16 = 2;
@@ -394,28 +393,22 @@ int hv_halo2_launch(HaloK& k, int TW, int KH, int KW, int maxpatch, hipStream_t 
         // 64-channel blocks when 128-channel blocks would leave a CU with a single workgroup (512 -> 256 data gradient: 102 vs 112 us)
         const long long wgs128 = (long long)k.B * hv_cdiv(k.cls[0].Hc, 8) * hv_cdiv(k.cls[0].Wc, 16) * hv_cdiv(k.Cout, 128);
         // weight-ring depth (taps in flight): vmcnt retires in order, so the first wait on a filter row issued AFTER the next chunk's patch
-        // prefetch also waits for that prefetch (an HBM round trip); a deeper ring moves that wait further behind the prefetch.  HV_HALO2_RING
-        // (alone a ring of 8 is 3-4 % faster than 4; inside the step, three discriminators in flight: 11.47 vs 11.54 ms -- default stays 4)
-        static const int ring = getenv("HV_HALO2_RING") ? atoi(getenv("HV_HALO2_RING")) : 4;
-        // wave arrangement (HV_HALO2_WM: bit 0 -> 64-channel blocks as 2 x 2 waves, bit 1 -> 128-channel blocks as 2 x 2).  With 1 x 4 waves every
-        // wave reads the whole 128-pixel patch for its 16 channels: at 64-channel blocks that is 8 LDS fragment reads per 8 MFMAs, the LDS peak.
+        // prefetch also waits for that prefetch (an HBM round trip); a deeper ring moves that wait further behind the prefetch
+        // (alone a ring of 8 is 3-4 % faster than 4; inside the step, three discriminators in flight: 11.47 vs 11.54 ms -- ring of 4 kept)
+        constexpr int kRing = 4;
+        // wave arrangement: 64-channel blocks as 2 x 2 waves, 128-channel blocks as 1 x 4.  With 1 x 4 waves every wave reads the whole
+        // 128-pixel patch for its 16 channels: at 64-channel blocks that is 8 LDS fragment reads per 8 MFMAs, the LDS peak.
         // Measured with fragment-ordered filters (256 -> 512 forward @32^2 / 512 -> 256 data gradient @31^2): ring 4: 74.9 / 82.2 us (2 x 2; 85.7 as
         // 1 x 4), ring 8: 72.0 / 79.9 us, ring 16 (64-channel blocks, 1 x 4): 78.0 us; 128-channel blocks as 2 x 2: no difference
-        static const int wm = getenv("HV_HALO2_WM") ? atoi(getenv("HV_HALO2_WM")) : 1;
         // (4x16-pixel tiles for these layers: 75.6 -> 87.3 us forward, 80.0 -> 102.9 us data gradient -- twice the filter fetches per MFMA.  Not kept)
-        static const int thr128 = getenv("HV_HALO2_THR128") ? atoi(getenv("HV_HALO2_THR128")) : 512;     // (256: 128-channel blocks for the 512 -> 256 data gradient: alone 89 -> 97 us, step 10.71 vs 10.69 ms)
-        if (wgs128 < thr128) {
-            if (wm & 1) return ring >= 8 ? launch2<8, 16, 64, 2, 2, 32, 1, 4, 8>(k, s) : launch2<8, 16, 64, 2, 2, 32, 1, 4, 4>(k, s);
-            if (ring == 16) return launch2<8, 16, 64, 1, 4, 32, 1, 4, 16>(k, s);
-            return ring == 8 ? launch2<8, 16, 64, 1, 4, 32, 1, 4, 8>(k, s) : launch2<8, 16, 64, 1, 4, 32, 1, 4, 4>(k, s);
-        }
-        if (wm & 2) return launch2<8, 16, 128, 2, 2, 32, 1, 4, 4>(k, s);
-        return ring >= 8 ? launch2<8, 16, 128, 1, 4, 32, 1, 4, 8>(k, s) : launch2<8, 16, 128, 1, 4, 32, 1, 4, 4>(k, s);
+        // (a threshold of 256: 128-channel blocks for the 512 -> 256 data gradient: alone 89 -> 97 us, step 10.71 vs 10.69 ms)
+        constexpr long long kWgs128Min = 512;
+        if (wgs128 < kWgs128Min) return launch2<8, 16, 64, 2, 2, 32, 1, 4, kRing>(k, s);
+        return launch2<8, 16, 128, 1, 4, 32, 1, 4, kRing>(k, s);
     }
     // 4x4 stride-2 forward with a single-buffered patch (see the kernel).  Measured alone, same device: 128 -> 256 @64^2 41.8 -> 34.9 us,
-    // 64 -> 128 @128^2 47.5 -> 49.3 us: taken from 128 input channels (HV_HALO2_S2F: 0 never, 2 always)
-    static const int s2f = getenv("HV_HALO2_S2F") ? atoi(getenv("HV_HALO2_S2F")) : 1;
-    if (s2f && ntaps == 16 && KH == 4 && KW == 4 && TW == 16 && k.bstep == 2 && k.Cin % 32 == 0 && k.Cout >= 64 && (k.Cin >= 128 || s2f == 2))
+    // 64 -> 128 @128^2 47.5 -> 49.3 us: taken from 128 input channels
+    if (ntaps == 16 && KH == 4 && KW == 4 && TW == 16 && k.bstep == 2 && k.Cin % 32 == 0 && k.Cout >= 64 && k.Cin >= 128)
         return launch2<8, 16, 64, 1, 4, 32, 2, 4, 4>(k, s);      // (128-channel blocks spill: 10 prefetch items + 64 accumulators + the weight ring)
     // PatchGAN logits layer (512 -> 1): the single output channel rides in a 16-channel MFMA tile, the input is staged once
     if (ntaps == 16 && KH == 4 && KW == 4 && TW == 16 && k.Cout <= 16 && k.bstep == 1 && k.Cin % 32 == 0) {
@@ -425,39 +418,25 @@ int hv_halo2_launch(HaloK& k, int TW, int KH, int KW, int maxpatch, hipStream_t 
     }
     // (4x4 stride-2 FORWARD stays on conv_halo_kernel: its 18 x 34-pixel patch leaves this kernel either 16-channel chunks or 4-row tiles
     // to keep two workgroups per CU -- measured 60-76 us against 48 us on 64 -> 128 @128^2 and 48-66 us against 43 us on 128 -> 256 @64^2)
-    // data gradient of the 4x4 stride-2 layers: four output-parity classes of 2x2 taps each
-    static const int m4 = getenv("HV_HALO2_S2T") ? atoi(getenv("HV_HALO2_S2T")) : 1;
-    if (m4 && ntaps == 4 && KH == 4 && KW == 4 && k.bstep == 1 && k.Cin % 32 == 0 && k.Cout > 32) {
-        // Tile and wave arrangement, measured alone (HV_HALO2_T2=0: 8x16 tiles with 1 x 4 waves everywhere; 2: also the 4x16 tiles below -- inside the
-        // step the three discriminators' kernels share the GPU, the small grids are filled anyway and the 4x16 tiles' doubled filter traffic shows no
-        // gain there: 11.17 vs 11.22 ms, so only the LDS-saving 2 x 2 arrangement is on by default):
+    // data gradient of the 4x4 stride-2 layers: four output-parity classes of 2x2 taps each (hv_conv2d_halo always plans them on 8x16 tiles)
+    if (ntaps == 4 && KH == 4 && KW == 4 && k.bstep == 1 && k.Cin % 32 == 0 && k.Cout > 32) {
+        if (TW != 16) return HV_ERR_UNSUPPORTED;
+        // Tile and wave arrangement, measured alone (8x16 tiles with 1 x 4 waves everywhere: the form before; 4x16 tiles for the 128-channel
+        // blocks of small grids: inside the step the three discriminators' kernels share the GPU, the small grids are filled anyway and the 4x16
+        // tiles' doubled filter traffic shows no gain there: 11.17 vs 11.22 ms, so only the LDS-saving 2 x 2 arrangement is kept):
         //   64 <- 128 @64^2 (64-channel blocks): 8x16 tiles, 2 x 2 waves 42.7 -> 36.3 us (1 x 4 waves read 8 LDS fragments per 8 MFMAs)
         //   128 <- 256 @64^2 (512 workgroups of 8x16 pixels): 4x16 tiles 36.3 -> 27.7 us (64-channel blocks as 2 x 2: 28.5 us); 256 <- 512 @32^2: 47.3 -> 32.0 us
-        static const int t2 = getenv("HV_HALO2_T2") ? atoi(getenv("HV_HALO2_T2")) : 1;
-        if (TW == 16 && t2) {
-            if (k.Cout <= 64) return launch2<8, 16, 64, 2, 2, 32, 1, 2, 4>(k, s);
-            long long wgs = 0;
-            for (int c = 0; c < k.ncls; ++c) wgs += (long long)k.B * hv_cdiv(k.cls[c].Hc, 8) * hv_cdiv(k.cls[c].Wc, 16) * hv_cdiv(k.Cout, 128);
-            if (wgs < 1024 && t2 == 2) return launch2<4, 16, 128, 1, 4, 32, 1, 2, 4>(k, s, 8, 16);
-        }
-        if (TW == 32) return k.Cout <= 64 ? launch2<8, 32, 64, 1, 4, 32, 1, 2, 4>(k, s) : launch2<8, 32, 128, 1, 4, 32, 1, 2, 4>(k, s);
-        return k.Cout <= 64 ? launch2<8, 16, 64, 1, 4, 32, 1, 2, 4>(k, s) : launch2<8, 16, 128, 1, 4, 32, 1, 2, 4>(k, s);
+        return k.Cout <= 64 ? launch2<8, 16, 64, 2, 2, 32, 1, 2, 4>(k, s) : launch2<8, 16, 128, 1, 4, 32, 1, 2, 4>(k, s);
     }
     // 3x3 layers of the generator.  Waves split the output channels (WN = 4) wherever a wave still gets 16 of them, so
-    // no two waves fetch the same filter rows.  HV_HALO2_MASK (bit per Cout class 16/32/64/128) is an A/B knob.
-    static const int mask = getenv("HV_HALO2_MASK") ? atoi(getenv("HV_HALO2_MASK")) : 15;
+    // no two waves fetch the same filter rows.
     if (ntaps == 9 && KH == 3 && KW == 3 && k.bstep == 1) {
         const bool ck32 = k.Cin % 32 == 0;
         const int cls = k.Cout <= 16 ? 1 : k.Cout <= 32 ? 2 : k.Cout <= 64 ? 4 : 8;
-        if (!(mask & cls)) return HV_ERR_UNSUPPORTED;
-        if (TW == 32) {
-            if (cls == 1) return ck32 ? launch2<8, 32, 16, 4, 1, 32, 1, 3, 3>(k, s) : launch2<8, 32, 16, 4, 1, 16, 1, 3, 3>(k, s);
-            if (cls == 2) return ck32 ? launch2<8, 32, 32, 2, 2, 32, 1, 3, 3>(k, s) : launch2<8, 32, 32, 2, 2, 16, 1, 3, 3>(k, s);
-            if (cls == 4) return ck32 ? launch2<8, 32, 64, 1, 4, 32, 1, 3, 3>(k, s) : launch2<8, 32, 64, 1, 4, 16, 1, 3, 3>(k, s);
-            // 128 channels x 256 pixels per workgroup needs 128 accumulator registers per lane and wastes half of them on the
-            // 68-channel layer of this model (measured 2.5x slower than conv_halo_kernel): not taken
-            return HV_ERR_UNSUPPORTED;
-        }
+        // 8x32 tiles reach here only for ragged channel counts with more than 64 output channels (hv_conv2d_halo takes 8x16 tiles for every other
+        // 3x3 layer).  128 channels x 256 pixels per workgroup needs 128 accumulator registers per lane and wastes half of them on the
+        // 68-channel layer of this model (measured 2.5x slower than conv_halo_kernel): not taken
+        if (TW == 32) return HV_ERR_UNSUPPORTED;
         if (!ck32) {   // 16-channel chunks (whole or ragged) on 8x16 tiles
             if (cls == 1) return launch2<8, 16, 16, 4, 1, 16, 1, 3, 3>(k, s);
             if (cls == 2) return launch2<8, 16, 32, 2, 2, 16, 1, 3, 3>(k, s);
@@ -466,15 +445,11 @@ int hv_halo2_launch(HaloK& k, int TW, int KH, int KW, int maxpatch, hipStream_t 
         }
         if (cls == 1) return launch2<8, 16, 16, 4, 1, 32, 1, 3, 3>(k, s);
         if (cls == 2) return launch2<8, 16, 32, 2, 2, 32, 1, 3, 3>(k, s);
-        // 64-channel blocks: 4x16-pixel tiles (HV_HALO2_T3=0: 8x16; 2: 8x16 with 2 x 2 waves; 3: 4x16 with 2 x 2).  Alone: 64 -> 64 @64^2 15.0 -> 12.9 us (2: 14.6,
-        // 3: 13.6), 128 -> 64 @64^2 20.7 -> 18.2 us, 32 -> 64 @128^2 33.4 -> 29.9 us: these layers are latency chains of 1-4 chunks, more and smaller
-        // workgroups overlap them better
-        static const int t3 = getenv("HV_HALO2_T3") ? atoi(getenv("HV_HALO2_T3")) : 1;
+        // 64-channel blocks: 4x16-pixel tiles (against 8x16: 2 x 2 waves on 8x16 or 4x16 tiles measured between).  Alone: 64 -> 64 @64^2 15.0 -> 12.9 us
+        // (8x16 as 2 x 2: 14.6, 4x16 as 2 x 2: 13.6), 128 -> 64 @64^2 20.7 -> 18.2 us, 32 -> 64 @128^2 33.4 -> 29.9 us: these layers are latency chains
+        // of 1-4 chunks, more and smaller workgroups overlap them better
         // (64-channel chunks -- the whole K of a 64-channel layer behind one barrier -- measured 16.9 -> 21.6 us: not kept)
-        if (cls == 4 && t3 == 1) return launch2<4, 16, 64, 1, 4, 32, 1, 3, 3>(k, s, 8, 16);
-        if (cls == 4 && t3 == 2) return launch2<8, 16, 64, 2, 2, 32, 1, 3, 3>(k, s);
-        if (cls == 4 && t3 == 3) return launch2<4, 16, 64, 2, 2, 32, 1, 3, 3>(k, s, 8, 16);
-        if (cls == 4) return launch2<8, 16, 64, 1, 4, 32, 1, 3, 3>(k, s);
+        if (cls == 4) return launch2<4, 16, 64, 1, 4, 32, 1, 3, 3>(k, s, 8, 16);
         return launch2<8, 16, 128, 1, 4, 32, 1, 3, 3>(k, s);
     }
     return HV_ERR_UNSUPPORTED;

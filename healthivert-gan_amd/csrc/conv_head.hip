@@ -219,8 +219,7 @@ __global__ __launch_bounds__(256) void head_tapsum_fixed_kernel(const TapSumK p)
 }
 
 static bool head_ok(const hv_conv_desc* d) {
-    static const int enabled = getenv("HV_HEAD") ? atoi(getenv("HV_HEAD")) : 1;   // A/B knob
-    return enabled && d->Cout == 1 && d->precision == HV_F16 && d->w_f16 && d->dil == 1 && !d->w_bstride && !d->ch_scale && !d->in_shift &&
+    return d->Cout == 1 && d->precision == HV_F16 && d->w_f16 && d->dil == 1 && !d->w_bstride && !d->ch_scale && !d->in_shift &&
            d->KH * d->KW <= 16 && (d->Cin & 31) == 0 && d->Cin >= 64 && d->Cin <= 1024 && d->stride <= 2 && !(d->x_ld & 3) && !(d->x_coff & 3) &&
            !((uintptr_t)d->x & 15) && !((uintptr_t)d->w_f16 & 7);
 }
@@ -270,8 +269,6 @@ int hv_conv2d_head(const hv_conv_desc* d, hipStream_t s) {
     int tpw = (8 + chunks - 1) / chunks;
     int blocks = hv_cdiv(k.tiles, 4 * tpw);
     if (blocks < 256) blocks = hv_cdiv(k.tiles, 4);
-    static const int xn_tpw = getenv("HV_HEAD_XN_TPW") ? atoi(getenv("HV_HEAD_XN_TPW")) : 0;      // tuning knob: tiles per wave of the XN form (0: as the plain form)
-    if (k.xn_stats && xn_tpw > 0) blocks = hv_cdiv(k.tiles, 4 * xn_tpw);
     hv_path_note = 5;
     HV_KNAME("head_gemm_kernel<%d, %s>", ch, d->x_f16 ? "true" : "false");
     if (k.xn_stats) {

@@ -340,8 +340,8 @@ static int dispatch_conv(ConvK& k, hipStream_t s) {
     else { BN = 128; BM = 128; }
     if (BN >= 64) {
         long long tiles = ((M + BM - 1) / BM) * ((k.Cout + BN - 1) / BN);
-        static const int small_thr = getenv("HV_IGEMM_SMALL") ? atoi(getenv("HV_IGEMM_SMALL")) : 600;   // tuning knob (step-level A/B: 15.05 ms at 600 vs 15.16 at 160)
-        if (tiles < small_thr) { BM = 64; BN = 64; }
+        constexpr long long kSmallTiles = 600;   // (step-level A/B: 15.05 ms at 600 vs 15.16 at 160)
+        if (tiles < kSmallTiles) { BM = 64; BN = 64; }
     } else if (BN == 16 && (M + 255) / 256 < 256) {
         BM = 64;   // narrow outputs on small feature maps (PatchGAN logits): more, smaller workgroups
     }
@@ -362,10 +362,9 @@ static int dispatch_conv(ConvK& k, hipStream_t s) {
         mt += hv_cdiv(k.cls[c].mcount, BM);
     }
     if (mt <= 0) return HV_OK;
-    {   // XCD-contiguous tile ranges when the linear workgroup id modulo 8 is blockIdx.x modulo 8 (HV_XCD=0: A/B knob)
-        static const int xcd = getenv("HV_XCD") ? atoi(getenv("HV_XCD")) : 1;
+    {   // XCD-contiguous tile ranges when the linear workgroup id modulo 8 is blockIdx.x modulo 8
         const int gy = (k.Cout + BN - 1) / BN;
-        k.xcd_swizzle = (xcd && mt >= 64 && (gy == 1 || (mt & 7) == 0)) ? 1 : 0;
+        k.xcd_swizzle = (mt >= 64 && (gy == 1 || (mt & 7) == 0)) ? 1 : 0;
     }
     if (BM == 256 && BN == 16) return launch_conv<T, 256, 16, 4, 1, ASC>(k, mt, s);
     if (BM == 64 && BN == 16) return launch_conv<T, 64, 16, 4, 1, ASC>(k, mt, s);
@@ -425,13 +424,13 @@ static int conv2d_dispatch(const hv_conv_desc* d, void* stream) {
     }
     // single-channel heads / logits: VALU kernels (conv_narrow.hip), except where the halo-tiled MFMA kernel stages the input
     // once instead of once per tap (many input channels, fp16 mode)
-    static const int narrow_max_cin = getenv("HV_NARROW_MAX_CIN") ? atoi(getenv("HV_NARROW_MAX_CIN")) : 15;   // A/B knob
+    constexpr int kNarrowMaxCin = 15;
     const bool halo_ok = d->precision == HV_F16 && d->w_f16 && d->dil == 1 && (d->Cin & 15) == 0 && !d->w_bstride && !d->ch_scale;
     if (d->Cout == 1 && d->workspace) {   // many input channels: taps as the GEMM's second dimension (conv_head.hip)
         const int rc = hv_conv2d_head(d, (hipStream_t)stream);
         if (rc != HV_ERR_UNSUPPORTED) return rc;
     }
-    if (d->Cout == 1 && !d->transposed && !d->mul_src && !(halo_ok && d->Cin > narrow_max_cin)) {
+    if (d->Cout == 1 && !d->transposed && !d->mul_src && !(halo_ok && d->Cin > kNarrowMaxCin)) {
         const int rc = hv_conv2d_narrow(d, (hipStream_t)stream);
         if (rc != HV_ERR_UNSUPPORTED) return rc;
     }
@@ -911,8 +910,6 @@ extern "C" int hv_wgrad_fold_now(const hv_wgrad_fold* f, void* stream) {
 }
 static int launch_wgrad_reduce(const float* slabs, float* dw, long long n, int splits, int accumulate, const float* bslabs, float* dbias, int nb,
                                 int bias_accumulate, hipStream_t s) {
-    static const int skip_red = getenv("HV_DIAG_SKIP") && strstr(getenv("HV_DIAG_SKIP"), "wgrad_reduce") ? 1 : 0;     // timing-only diagnostic (wrong results)
-    if (skip_red) return HV_OK;
 #define HV_RED(G_)                                                                                                                          \
     hipLaunchKernelGGL(wgrad_reduce_kernel<G_>, dim3(hv_cdiv(n / 4, 256 / G_) + (dbias ? hv_cdiv(nb, 256 / G_) : 0)), dim3(256), 0, s, slabs, dw, n, splits, \
                        accumulate, bslabs, dbias, nb, bias_accumulate)
@@ -928,18 +925,16 @@ struct WgradPlan { int BN, BC, KT, splits, chunk; };
 static int wgrad_plan(const hv_wgrad_desc* d, WgradPlan* pl) {
     const int J = d->KH * d->KW * d->Cin;
     const long long M = (long long)d->B * d->Ho * d->Wo;
-    static const bool wide64 = !(getenv("HV_WGRAD_WIDE") && atoi(getenv("HV_WGRAD_WIDE")) == 0);   // A/B knob
-    static const int bc128_minj = getenv("HV_WGRAD_BC128_MINJ") ? atoi(getenv("HV_WGRAD_BC128_MINJ")) : 4096;   // tuning knob
+    constexpr int kBc128MinJ = 4096;
     int BN, BC;
     if (d->Cout <= 16) { BN = 16; BC = 128; }
     else if (d->Cout <= 32) { BN = 32; BC = 128; }
-    else if (d->Cout <= 64) { BN = 64; BC = (J >= 512 && wide64) ? 256 : 64; }   // wide J tile: G is re-read J/256 instead of J/64 times
-    else { BN = 128; BC = J >= bc128_minj ? 128 : 64; }
+    else if (d->Cout <= 64) { BN = 64; BC = J >= 512 ? 256 : 64; }   // wide J tile: G is re-read J/256 instead of J/64 times
+    else { BN = 128; BC = J >= kBc128MinJ ? 128 : 64; }
     const long long tiles = (long long)hv_cdiv(d->Cout, BN) * hv_cdiv(J, BC);
     // ~2 workgroups per CU; layers whose dW already has many tiles get few splits (slab traffic grows with splits)
-    static const int want_wg = getenv("HV_WGRAD_WANT") ? atoi(getenv("HV_WGRAD_WANT")) : 512;   // tuning knob (step time 15.13 ms at 512 vs 15.33 at 384, 15.46 at 640, 15.56 at 768+)
-    static const int want_big = getenv("HV_WGRAD_WANT_BIG") ? atoi(getenv("HV_WGRAD_WANT_BIG")) : 512;   // tuning knob (layers with >= 128 tiles)
-    long long want = tiles >= 128 ? (want_big + tiles - 1) / tiles : (want_wg + tiles - 1) / tiles;
+    constexpr int kWantWg = 512;   // workgroups (step time 15.13 ms at 512 vs 15.33 at 384, 15.46 at 640, 15.56 at 768+; the same for layers with >= 128 tiles)
+    long long want = (kWantWg + tiles - 1) / tiles;
     if (want > 256) want = 256;
     long long maxs = (M + 255) / 256;                     // at least 256 pixels per split
     long long splits = want < 1 ? 1 : want;
@@ -1016,9 +1011,8 @@ extern "C" int hv_conv2d_wgrad(const hv_wgrad_desc* d, void* stream) {
     const hv_wgrad_fold* c = d->carry;
     if (c && c->nslabs > 0) {
         if (!c->slabs || !c->dw || c->numel <= 0 || (c->numel & 3)) return HV_ERR_ARG;
-        static const int carry_on = getenv("HV_FOLD_CARRY") ? atoi(getenv("HV_FOLD_CARRY")) : 1;      // A/B knob (0: every carried fold as its own launch)
         const bool overlap = (c->slabs == d->workspace);      // (a caller that did not alternate its slab buffers: the fold must be done before this call writes)
-        if (carry_on && !overlap && c->dw != d->dw) {
+        if (!overlap && c->dw != d->dw) {
             hv_carry = HvFold{c->slabs, c->dw, c->numel, c->nslabs, c->accumulate, c->dbias ? c->bias_slabs : nullptr, c->dbias, c->Cout, c->dbias_accumulate};
         } else {
             rc = hv_wgrad_fold_now(c, stream);

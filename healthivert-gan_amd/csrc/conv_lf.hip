@@ -903,19 +903,16 @@ static int launch_lf2(HaloK& k, hipStream_t s) {
 // NHWC views with 16-byte aligned channel rows.  Returns HV_ERR_UNSUPPORTED for everything else (the caller goes on to conv_halo2_kernel).
 int hv_convlf_launch(HaloK& k, int KH, int KW, hipStream_t s) {
     static const int on = getenv("HV_CONV_LF") ? atoi(getenv("HV_CONV_LF")) : 1;
-    static const int s2on = getenv("HV_LF_S2") ? atoi(getenv("HV_LF_S2")) : 1;      // A/B knob: stride-2 forward layers (conv_lf2_kernel)
-    if (!on || KH != 3 || KW != 3 || k.ncls != 1 || (k.bstep != 1 && !(k.bstep == 2 && s2on)) || k.cls[0].ntaps != 9) return HV_ERR_UNSUPPORTED;
+    if (!on || KH != 3 || KW != 3 || k.ncls != 1 || (k.bstep != 1 && k.bstep != 2) || k.cls[0].ntaps != 9) return HV_ERR_UNSUPPORTED;
     if (!k.wt || ((uintptr_t)k.wt & 15) || !k.x_half || !k.y_half || k.accumulate > 1) return HV_ERR_UNSUPPORTED;
     if ((k.x_ld & 7) || (k.x_coff & 7) || ((uintptr_t)k.x & 15) || (k.Cout & 7) || (k.y_ld & 7) || (k.y_coff & 7) || ((uintptr_t)k.y & 15)) return HV_ERR_UNSUPPORTED;
     if (k.mul_src && (!k.mul_half || (k.mul_ld & 7) || (k.mul_coff & 7) || ((uintptr_t)k.mul_src & 15))) return HV_ERR_UNSUPPORTED;
     // the 3x3 taps must span dh, dw in 0..2 around (dh_min, dw_min) -- true for pad-1 forward and its data gradient
     const int Cin = k.Cin, Cout = k.Cout;
-    // HV_CONV_LF_MASK: bit per (Cin class 16 / 32 / 64) x (Cout class <= 16 / <= 32 / > 32), an A/B knob
-    static const int mask = getenv("HV_CONV_LF_MASK") ? atoi(getenv("HV_CONV_LF_MASK")) : 0x1ff;
     // (Measured and not kept, round 3: the two concat layers (32 + 1 / 64 + 1 input channels) with their buffers widened to 48 / 80 channels and
     // <48, 32, 16> / <80, 64, 8> instantiations on 16-channel planes: step 8.76 vs 8.78 ms -- no gain over conv_halo2's ragged 16-channel chunks.)
     const int ci = Cin == 16 ? 0 : Cin == 32 ? 1 : Cin == 64 ? 2 : -1, co = Cout <= 16 ? 0 : Cout <= 32 ? 1 : 2;
-    if (ci < 0 || !((mask >> (ci * 3 + co)) & 1)) return HV_ERR_UNSUPPORTED;
+    if (ci < 0) return HV_ERR_UNSUPPORTED;
     if (k.bstep == 2) {      // stride-2 forward (a stride-2 data gradient has four tap classes: never here)
         if (k.dil != 1 || k.x1 || k.pool2 || k.in_shift || k.mul_src) return HV_ERR_UNSUPPORTED;
         switch (ci * 3 + co) {
@@ -930,9 +927,8 @@ int hv_convlf_launch(HaloK& k, int KH, int KW, hipStream_t s) {
         // residue sub-grids smaller than a tile: the packed form, where the sub-grid is the whole residue class (sub-grid edge x dilation = the map) -- the
         // generators' d = 8 / d = 16 layers on 64 x 64 maps.  Other small sub-grids: d <= 4 as partly filled tiles below (as before), d >= 8 on to
         // conv_halo2_kernel / the gather kernel
-        static const int packed = getenv("HV_LF_PACKED") ? atoi(getenv("HV_LF_PACKED")) : 1;      // A/B knob
         const HaloCls& C = k.cls[0];
-        const bool fits = packed && !k.x1 && !k.pool2 && !k.in_shift && k.Hl == k.Wl && k.boff + C.dh_min == -1 && k.boff + C.dw_min == -1 && C.Hc == k.Hl && C.Wc == k.Wl &&
+        const bool fits = !k.x1 && !k.pool2 && !k.in_shift && k.Hl == k.Wl && k.boff + C.dh_min == -1 && k.boff + C.dw_min == -1 && C.Hc == k.Hl && C.Wc == k.Wl &&
                           Cin == 64 && Cout == 64;
         if (fits && k.Hl == 8 && k.dil % 2 == 0) return launch_lfd<64, 64, 2, 8>(k, s);
         if (fits && k.Hl == 4 && k.dil % 4 == 0) return launch_lfd<64, 64, 2, 4>(k, s);

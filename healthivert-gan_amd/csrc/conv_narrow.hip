@@ -440,8 +440,7 @@ __global__ __launch_bounds__(256) void stem5_dgrad_kernel(const Stem5K p) {
 
 // 4 -> 16 channels, 5x5, stride 1, 'same' padding, fp16 filter copy [16][25][4]
 int hv_conv2d_stem5(const hv_conv_desc* d, hipStream_t s) {
-    static const int enabled = getenv("HV_STEM5") ? atoi(getenv("HV_STEM5")) : 1;   // A/B knob
-    if (!enabled || d->precision != HV_F16 || !d->w_f16 || d->transposed || d->in_shift || d->w_bstride || d->ch_scale || d->mul_src || d->dil != 1 ||
+    if (d->precision != HV_F16 || !d->w_f16 || d->transposed || d->in_shift || d->w_bstride || d->ch_scale || d->mul_src || d->dil != 1 ||
         d->Cin != 4 || d->Cout != 16 || d->KH != 5 || d->KW != 5 || d->stride != 1 || d->pad != 2 || d->Ho != d->H || d->Wo != d->W)
         return HV_ERR_UNSUPPORTED;
     if ((d->x_ld & 3) || (d->x_coff & 3) || ((uintptr_t)d->x & 15) || ((uintptr_t)d->w_f16 & 7) || (long long)d->B * d->H >= (1ll << 31)) return HV_ERR_UNSUPPORTED;
@@ -453,8 +452,7 @@ int hv_conv2d_stem5(const hv_conv_desc* d, hipStream_t s) {
     k.epi.mul_act = 0; k.epi.mul_vec = 0; k.epi.y_half = d->y_f16 ? 1 : 0; k.epi.mul_half = 0;
     k.epi.vec_store = ((d->y_ld & 3) == 0 && (d->y_coff & 3) == 0 && ((uintptr_t)d->y & 15) == 0) ? 1 : 0;
     hv_path_note = 4;
-    static const int lds5 = getenv("HV_STEM5_LDS") ? atoi(getenv("HV_STEM5_LDS")) : 1;       // A/B knob
-    if (lds5 && k.x_half && (long long)d->B * d->H <= 65535) {
+    if (k.x_half && (long long)d->B * d->H <= 65535) {
         HV_KNAME("stem5_lds_kernel");
         hipLaunchKernelGGL(stem5_lds_kernel, dim3(hv_cdiv(d->W, 256), d->B * d->H), dim3(256), 0, s, k);
         HV_LAUNCH_CHECK();
@@ -468,8 +466,7 @@ int hv_conv2d_stem5(const hv_conv_desc* d, hipStream_t s) {
 
 // data gradient of those stems: 16 -> 4 channels, transposed, fp16 filter copy [4][25][16], fp16 gradient input
 int hv_conv2d_stem5_dgrad(const hv_conv_desc* d, hipStream_t s) {
-    static const int enabled = getenv("HV_STEM5_DGRAD") ? atoi(getenv("HV_STEM5_DGRAD")) : 1;   // A/B knob
-    if (!enabled || d->precision != HV_F16 || !d->w_f16 || !d->transposed || d->in_shift || d->w_bstride || d->ch_scale || d->mul_src || d->dil != 1 ||
+    if (d->precision != HV_F16 || !d->w_f16 || !d->transposed || d->in_shift || d->w_bstride || d->ch_scale || d->mul_src || d->dil != 1 ||
         d->Cin != 16 || d->Cout != 4 || d->KH != 5 || d->KW != 5 || d->stride != 1 || d->pad != 2 || d->Ho != d->H || d->Wo != d->W || !d->x_f16 || d->bias)
         return HV_ERR_UNSUPPORTED;
     if ((d->x_ld & 7) || (d->x_coff & 7) || ((uintptr_t)d->x & 15) || ((uintptr_t)d->w_f16 & 15) || (long long)d->B * hv_cdiv(d->H, 8) > 65535) return HV_ERR_UNSUPPORTED;
@@ -506,8 +503,7 @@ int hv_conv2d_narrow(const hv_conv_desc* d, hipStream_t s) {
         hv_path_note = 1;
         if (lpp == 1 && !d->transposed && d->KH == 3 && d->KW == 3 && (c4 == 2 || c4 == 3)) {
             const dim3 g3(hv_cdiv(d->Wo, 256), d->B * d->Ho);
-            static const int lds3 = getenv("HV_NARROW3_LDS") ? atoi(getenv("HV_NARROW3_LDS")) : 1;      // A/B knob
-            if (lds3 && d->stride == 1 && d->pad == 1 && d->in_shift == 0 && d->Ho == d->H && d->Wo == d->W) {
+            if (d->stride == 1 && d->pad == 1 && d->in_shift == 0 && d->Ho == d->H && d->Wo == d->W) {
                 HV_KNAME("narrow3_lds_kernel<%d>", c4);
                 if (k.x_half) {
                     if (c4 == 2) hipLaunchKernelGGL((narrow3_lds_kernel<2, true>), g3, dim3(256), 0, s, k);
@@ -551,14 +547,12 @@ int hv_conv2d_thin_in(const hv_conv_desc* d, hipStream_t s) {
     k.KH = d->KH; k.KW = d->KW; k.stride = d->stride; k.pad = d->pad; k.transposed = 0;
     k.Ho = d->Ho; k.Wo = d->Wo; k.y_ld = d->y_ld; k.y_coff = d->y_coff; k.Cout = d->Cout;
     k.alpha = d->alpha; k.act = d->act; k.accumulate = d->accumulate;
-    static const int stem_mfma = getenv("HV_STEM_MFMA") ? atoi(getenv("HV_STEM_MFMA")) : 1;   // A/B knob
-    if (stem_mfma && d->precision == HV_F16 && d->w_f16 && (d->Cout & 15) == 0 && !((uintptr_t)d->w_f16 & 7) && (long long)d->B * d->Ho < (1ll << 31)) {
+    if (d->precision == HV_F16 && d->w_f16 && (d->Cout & 15) == 0 && !((uintptr_t)d->w_f16 & 7) && (long long)d->B * d->Ho < (1ll << 31)) {
         hv_path_note = 4;
-        static const int stem_st = getenv("HV_STEM_ST") ? atoi(getenv("HV_STEM_ST")) : 1;   // A/B knob
-        if (stem_st && d->y_f16 && d->Cout == 64 && !d->accumulate && !(d->y_ld & 7) && !(d->y_coff & 7) && !((uintptr_t)d->y & 15)) {
+        if (d->y_f16 && d->Cout == 64 && !d->accumulate && !(d->y_ld & 7) && !(d->y_coff & 7) && !((uintptr_t)d->y & 15)) {
             HV_KNAME("stem1_mfma_kernel<true>");
-            static const int rpw = getenv("HV_STEM1_ROWS") ? atoi(getenv("HV_STEM1_ROWS")) : 1;      // tuning knob: output rows per workgroup (B32 / B16 at 256^2, us: 1 row 23.9 / 12.5, 2 rows 23.4 / 12.3, 4 rows 22.3 / 15.1, 8 rows 28.7 / 22.2)
-            hipLaunchKernelGGL(stem1_mfma_kernel<true>, dim3(hv_cdiv(d->B * d->Ho, rpw > 0 ? rpw : 1)), dim3(256), 0, s, k, reinterpret_cast<const _Float16*>(d->w_f16));
+            constexpr int kRows = 1;      // output rows per workgroup (B32 / B16 at 256^2, us: 1 row 23.9 / 12.5, 2 rows 23.4 / 12.3, 4 rows 22.3 / 15.1, 8 rows 28.7 / 22.2)
+            hipLaunchKernelGGL(stem1_mfma_kernel<true>, dim3(hv_cdiv(d->B * d->Ho, kRows)), dim3(256), 0, s, k, reinterpret_cast<const _Float16*>(d->w_f16));
             HV_LAUNCH_CHECK();
             return HV_OK;
         }

@@ -189,8 +189,8 @@ static int launch_px(PxK& k, hipStream_t s) {
     constexpr int NKQ = KS * KS * (CI / 4);
     const size_t lds = (size_t)CQ * NKQ * 32 + (size_t)(TH + KS - 1) * (256 + KS - 1) * CI * 2;
     k.segs = hv_cdiv(k.W, 256); k.rblocks = hv_cdiv(k.H, TH); k.tiles = k.B * k.rblocks * k.segs;
-    static const int want = getenv("HV_PX_WGS") ? atoi(getenv("HV_PX_WGS")) : 4096;      // tuning knob: workgroups (each walks tiles of TH rows x 256 pixels)
-    int blocks = k.tiles < want ? k.tiles : want;
+    constexpr int kWgs = 4096;      // workgroups (each walks tiles of TH rows x 256 pixels)
+    int blocks = k.tiles < kWgs ? k.tiles : kWgs;
     HV_KNAME("conv_px_kernel<%d, %d, %d, %s, %s, %d>", KS, CI, CQ, TR ? "true" : "false", Y1 ? "true" : "false", TH);
     if (hv_probe_only) return HV_OK;
     hipLaunchKernelGGL((conv_px_kernel<KS, CI, CQ, TR, Y1, TH>), dim3(blocks), dim3(256), lds, s, k);
@@ -201,12 +201,11 @@ static int launch_px(PxK& k, hipStream_t s) {
 // hv_conv2d: KH = KW in {3, 5}, stride 1, dilation 1, fp16 operands and fp16 filter rows; the operand's pixel row holds CI = 4 / 8 / 12 / 16 channels (x_ld a
 // multiple of 4, the view starting on a multiple of 4), Cout <= 16 stored as fp16 rows of whole quads, or ONE fp32 output channel (the heads)
 int hv_conv2d_px(const hv_conv_desc* d, hipStream_t s) {
-    // A/B knob, bits: 1 heads forward (13.4 / 9.4 us against 22.0 / 15.3 for 12 / 8 channels at 256^2, bs 16), 2 heads' data gradient (16.6 / 12.8 against 38.7 / 26.7),
-    // 4 the 8 <-> 16 channel 3x3 layer (26.9 against 39.9 us data gradient, 27.4 against 38.8 forward).  Measured and not kept (the tiled kernels are as fast or
+    // Taken for: the heads forward (13.4 / 9.4 us against 22.0 / 15.3 for 12 / 8 channels at 256^2, bs 16), 2 heads' data gradient (16.6 / 12.8 against 38.7 / 26.7),
+    // the 8 <-> 16 channel 3x3 layer (26.9 against 39.9 us data gradient, 27.4 against 38.8 forward).  Measured and not kept (the tiled kernels are as fast or
     // faster there): the 16 -> 8 channel 3x3 layer and its data gradient (28.1 / 29.4 against 25.9 / 26.3 us), the 5x5 stems (30.5 against 30.3 us) and their data
     // gradient (16 -> 4: 34.5 against 34.0 us -- 25 taps x 32 B of window plus as many bytes of filter fragments per pixel: LDS-read bound either way)
-    static const int on = getenv("HV_CONV_PX") ? atoi(getenv("HV_CONV_PX")) : 7;
-    if (!on || d->precision != HV_F16 || !d->w_f16 || !d->x_f16 || d->KH != d->KW || (d->KH != 3 && d->KH != 5) || d->stride != 1 || d->dil != 1 || d->in_shift ||
+    if (d->precision != HV_F16 || !d->w_f16 || !d->x_f16 || d->KH != d->KW || (d->KH != 3 && d->KH != 5) || d->stride != 1 || d->dil != 1 || d->in_shift ||
         d->w_bstride || d->ch_scale || d->x1 || d->pool2 || d->stats || d->bstats || d->xn_stats)
         return HV_ERR_UNSUPPORTED;
     if (d->Ho != d->H || d->Wo != d->W || 2 * d->pad != d->KH - 1) return HV_ERR_UNSUPPORTED;      // 'same' layers only
@@ -231,9 +230,9 @@ int hv_conv2d_px(const hv_conv_desc* d, hipStream_t s) {
     HV_WUSE(2);
 #define PX(KS_, CI_, CQ_, TR_, Y1_) return launch_px<KS_, CI_, CQ_, TR_, Y1_, (CI_ >= 12 ? 2 : 4)>(k, s)
     if (d->KH == 3) {
-        if (y1 && !tr && (on & 1)) { if (CI == 12) PX(3, 12, 1, false, true); if (CI == 8) PX(3, 8, 1, false, true); }
-        if (!y1 && tr && CI == 4 && (on & 2)) { if (cq == 3) PX(3, 4, 3, true, false); if (cq == 2) PX(3, 4, 2, true, false); if (cq == 4) PX(3, 4, 4, true, false); }
-        if (!y1 && CI == 8 && cq == 4 && (on & 4)) { if (tr) PX(3, 8, 4, true, false); PX(3, 8, 4, false, false); }
+        if (y1 && !tr) { if (CI == 12) PX(3, 12, 1, false, true); if (CI == 8) PX(3, 8, 1, false, true); }
+        if (!y1 && tr && CI == 4) { if (cq == 3) PX(3, 4, 3, true, false); if (cq == 2) PX(3, 4, 2, true, false); if (cq == 4) PX(3, 4, 4, true, false); }
+        if (!y1 && CI == 8 && cq == 4) { if (tr) PX(3, 8, 4, true, false); PX(3, 8, 4, false, false); }
     }
 #undef PX
     return HV_ERR_UNSUPPORTED;

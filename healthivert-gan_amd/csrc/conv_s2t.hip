@@ -216,9 +216,8 @@ static int launch_s2t(S2TK& k, hipStream_t s) {
     k.tiles_x = hv_cdiv(k.Wi, 16);
     k.tiles = k.tiles_x * hv_cdiv(k.Hi, TH);
     size_t lds = (size_t)2 * (TH + 2) * 18 * LDP * sizeof(_Float16);
-    {   // coalesced fp16 epilogue through LDS (HV_HALO2_EP16=0: direct stores); the output tile may need more LDS than the two patch buffers
-        static const int ep16 = getenv("HV_HALO2_EP16") ? atoi(getenv("HV_HALO2_EP16")) : 1;
-        k.ep16 = (ep16 && k.y_half && k.accumulate == 0 && !(k.Cout & 7) && !(k.y_ld & 7) && !(k.y_coff & 7) && !((uintptr_t)k.y & 15) && k.Ho == 2 * k.Hi &&
+    {   // coalesced fp16 epilogue through LDS; the output tile may need more LDS than the two patch buffers
+        k.ep16 = (k.y_half && k.accumulate == 0 && !(k.Cout & 7) && !(k.y_ld & 7) && !(k.y_coff & 7) && !((uintptr_t)k.y & 15) && k.Ho == 2 * k.Hi &&
                   k.Wo == 2 * k.Wi) ? 1 : 0;
         if (k.ep16 && k.mul_src && k.mul_half && !(k.mul_ld & 7) && !(k.mul_coff & 7) && !((uintptr_t)k.mul_src & 15)) k.ep16 = 2;
         const size_t need = (size_t)2 * TH * 32 * (BN + 8) * sizeof(_Float16);
@@ -240,19 +239,18 @@ static int launch_s2t(S2TK& k, hipStream_t s) {
     return HV_OK;
 }
 
-static int s2t_mode = -1;
+// 0 off, 1 the 3x3 filters (2 - 3.6x faster than the per-class kernels at the generators' shapes), 2 also the 4x4 filters
+// (measured SLOWER than conv_halo2's classes at the PatchGAN shapes: 64.3 vs 47.1 us for 64<-128 @64^2, 50.7 vs 40.4 us for 128<-256 @32^2)
+static int s2t_mode = 1;
 extern "C" int hv_set_s2t_mode(int mode) {
-    const int prev = s2t_mode < 0 ? (getenv("HV_S2T") ? atoi(getenv("HV_S2T")) : 1) : s2t_mode;
+    const int prev = s2t_mode;
     s2t_mode = mode;
     return prev;
 }
 
 // Called by hv_conv2d for transposed (data-gradient) stride-2 3x3 / 4x4 convolutions in the fp16 mode; HV_ERR_UNSUPPORTED: other kernels.
 int hv_conv2d_s2t(const hv_conv_desc* d, hipStream_t s) {
-    // A/B knob: 0 off, 1 the 3x3 filters (2 - 3.6x faster than the per-class kernels at the generators' shapes), 2 also the 4x4 filters
-    // (measured SLOWER than conv_halo2's classes at the PatchGAN shapes: 64.3 vs 47.1 us for 64<-128 @64^2, 50.7 vs 40.4 us for 128<-256 @32^2)
-    if (s2t_mode < 0) s2t_mode = getenv("HV_S2T") ? atoi(getenv("HV_S2T")) : 1;
-    const int enabled = s2t_mode;
+    const int enabled = s2t_mode;      // hv_set_s2t_mode
     if (!enabled || (d->KH == 4 && enabled < 2) || !d->transposed || d->stride != 2 || d->pad != 1 || d->dil != 1 || d->KH != d->KW || (d->KH != 3 && d->KH != 4)) return HV_ERR_UNSUPPORTED;
     if (d->precision != HV_F16 || !d->w_f16 || !d->x_f16 || d->w_bstride || d->ch_scale || d->in_shift) return HV_ERR_UNSUPPORTED;
     if (d->Ho != 2 * d->H || d->Wo != 2 * d->W) return HV_ERR_UNSUPPORTED;
@@ -271,8 +269,7 @@ int hv_conv2d_s2t(const hv_conv_desc* d, hipStream_t s) {
     k.w_bytes = (unsigned)((size_t)d->Cout * k.w_row * sizeof(_Float16));
     const bool ck32 = (d->Cin & 31) == 0;
     {   // the tiled table needs whole chunks (Cin % 16 == 0; fragments of 32 channels exactly when Cin % 32 == 0, as the CK choice below)
-        static const int tiled = getenv("HV_W_TILED") ? atoi(getenv("HV_W_TILED")) : 1;
-        k.wt = (tiled && d->w_f16_tiled && !((uintptr_t)d->w_f16_tiled & 15) && (d->Cin & 15) == 0) ? reinterpret_cast<const _Float16*>(d->w_f16_tiled) : nullptr;
+        k.wt = (d->w_f16_tiled && !((uintptr_t)d->w_f16_tiled & 15) && (d->Cin & 15) == 0) ? reinterpret_cast<const _Float16*>(d->w_f16_tiled) : nullptr;
         k.wt_bytes = (unsigned)((size_t)hv_cdiv(d->Cout, 16) * 16 * k.w_row * sizeof(_Float16));
         if (k.wt) { k.w = k.wt; k.w_bytes = k.wt_bytes; }
     }

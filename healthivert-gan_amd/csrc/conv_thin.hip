@@ -245,8 +245,7 @@ static int launch_logits(const ThinK& k, const _Float16* wh, int groups, hipStre
 
 // hv_conv2d: transposed, 4x4, stride 1, pad 1, gradient channel stride 4 (<= 4 live channels), Cout % 16 == 0 (<= 512), fp16 views + fp16 filter copy
 static bool logits_dgrad_eligible(const hv_conv_desc* d) {
-    static const int on = getenv("HV_LOGITS_DGRAD") ? atoi(getenv("HV_LOGITS_DGRAD")) : 1;
-    if (!on || !d->transposed || d->KH != 4 || d->KW != 4 || d->stride != 1 || d->pad != 1 || d->dil != 1 || d->in_shift || d->w_bstride || d->ch_scale || !d->w_f16)
+    if (!d->transposed || d->KH != 4 || d->KW != 4 || d->stride != 1 || d->pad != 1 || d->dil != 1 || d->in_shift || d->w_bstride || d->ch_scale || !d->w_f16)
         return false;
     if (d->Cin != 4 || d->x_ld != 4 || (d->x_coff & 3) || !d->x_f16 || !d->y_f16 || d->bias || d->act != HV_ACT_NONE || d->accumulate > 1) return false;
     if (d->Cout > 512 || (d->Cout & 31) || (d->Cout & (d->Cout - 1)) || ((uintptr_t)d->w_f16 & 15) || (d->y_ld & 7) || (d->y_coff & 7) || ((uintptr_t)d->y & 15) || ((uintptr_t)d->x & 7) ||
@@ -293,8 +292,7 @@ int hv_conv2d_logits_dgrad(const hv_conv_desc* d, hipStream_t s) {
 // 64 LDS filter reads per lane and pixel group cost more than the gather kernel's MFMA tiles save.)
 // hv_conv2d: transposed, 3x3, stride 1, dilation 1, Cin <= 4 (channel stride 4), Cout in {8, 12, 16}, fp16 views, no bias / activation of its own
 int hv_conv2d_thin_dgrad(const hv_conv_desc* d, hipStream_t s) {
-    static const int on = getenv("HV_THIN_DGRAD") ? atoi(getenv("HV_THIN_DGRAD")) : 1;
-    if (!on || !d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dil != 1 || d->in_shift || d->w_bstride || d->ch_scale) return HV_ERR_UNSUPPORTED;
+    if (!d->transposed || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->dil != 1 || d->in_shift || d->w_bstride || d->ch_scale) return HV_ERR_UNSUPPORTED;
     if (d->Cin > 4 || (d->x_ld & 3) || (d->x_coff & 3) || !d->x_f16 || !d->y_f16 || d->bias || d->act != HV_ACT_NONE || d->accumulate > 1) return HV_ERR_UNSUPPORTED;
     if (d->Cout > 16 || (d->Cout & 3) || (d->y_ld & 3) || (d->y_coff & 3) || ((uintptr_t)d->y & 7) || ((uintptr_t)d->x & 7) || d->Ho != d->H || d->Wo != d->W) return HV_ERR_UNSUPPORTED;
     if (d->mul_src && (!d->mul_f16 || (d->mul_ld & 3) || (d->mul_coff & 3) || ((uintptr_t)d->mul_src & 7))) return HV_ERR_UNSUPPORTED;

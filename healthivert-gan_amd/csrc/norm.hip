@@ -23,8 +23,8 @@ static NormPlan norm_plan(int B, int HW, int C, int norm, int groups = 1, bool v
     p.CB = vec ? (CV < 32 ? CV : 32) : CV;
     p.slices = CV / p.CB;
     p.rstep = 256 / p.CB;
-    static const int blocks = getenv("HV_NORM_BLOCKS") ? atoi(getenv("HV_NORM_BLOCKS")) : 2048;   // tuning knob
-    long long cap = blocks / ((long long)p.G * p.slices);
+    constexpr int kBlocks = 2048;
+    long long cap = kBlocks / ((long long)p.G * p.slices);
     if (cap < 16) cap = 16;
     if (cap > 512) cap = 512;
     long long rpb = (long long)p.rstep * 8;              // at least 8 iterations per block
@@ -237,7 +237,12 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const NormK k) {
     }
 }
 
-static int apply_grid(long long n, int G) { static const int ab = getenv("HV_NORM_APPLY_BLOCKS") ? atoi(getenv("HV_NORM_APPLY_BLOCKS")) : 1024;   /* step-level A/B: 15.12 ms at 1024, 15.19 at 2048, 15.42 at 4096 */ long long b = (n + 255) / 256, cap = ab / (G > 0 ? G : 1); if (cap < 8) cap = 8; return (int)(b > cap ? cap : (b < 1 ? 1 : b)); }
+static int apply_grid(long long n, int G) {
+    constexpr int kBlocks = 1024;      // (step-level A/B: 15.12 ms at 1024, 15.19 at 2048, 15.42 at 4096)
+    long long b = (n + 255) / 256, cap = kBlocks / (G > 0 ? G : 1);
+    if (cap < 8) cap = 8;
+    return (int)(b > cap ? cap : (b < 1 ? 1 : b));
+}
 static int n_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 extern "C" int hv_norm_act_forward(const hv_norm_desc* d, void* stream) {
@@ -278,17 +283,13 @@ extern "C" int hv_norm_act_forward(const hv_norm_desc* d, void* stream) {
         HV_LAUNCH_CHECK();
     }
     const int update = d->norm == HV_NORM_BATCH && d->training && d->running_mean && d->running_var;
-    static const int skip_fin = getenv("HV_DIAG_SKIP") && strstr(getenv("HV_DIAG_SKIP"), "norm_finalize") ? 1 : 0;     // timing-only diagnostic (stale statistics): what the finalize launches cost the step
-    static int fin_calls = 0;
-    if (!skip_fin || ++fin_calls <= 36)      // (the first two steps' statistics stay in place: sane operands for everything downstream)
     hipLaunchKernelGGL(norm_fwd_finalize_kernel, dim3(d->C), dim3(64), 0, s, part, pl.G, handed ? d->n_partials : pl.nchunk, d->C, pl.R,
                        d->eps, d->momentum, d->stats, d->running_mean, d->running_var, d->num_batches_tracked, use_running ? 1 : 0, update,
                        handed ? d->partials : nullptr);
     HV_LAUNCH_CHECK();
     const long long n = (long long)pl.R * (vec ? d->C / 4 : d->C);
     const dim3 agrid(apply_grid(n, pl.G), pl.G);
-    static const int skip_apply = getenv("HV_DIAG_SKIP") && strstr(getenv("HV_DIAG_SKIP"), "norm_apply") ? 1 : 0;     // timing-only diagnostic (wrong results)
-    if (skip_apply || !d->y) return HV_OK;
+    if (!d->y) return HV_OK;
     if (d->f16) {
         if (vec) hipLaunchKernelGGL((norm_apply_kernel<true, true>), agrid, dim3(256), 0, s, k);
         else hipLaunchKernelGGL((norm_apply_kernel<false, true>), agrid, dim3(256), 0, s, k);
@@ -436,17 +437,12 @@ extern "C" int hv_norm_act_backward(const hv_norm_bwd_desc* d, void* stream) {
         }
         HV_LAUNCH_CHECK();
     }
-    static const int skip_bfin = getenv("HV_DIAG_SKIP") && strstr(getenv("HV_DIAG_SKIP"), "norm_finalize") ? 1 : 0;     // (timing-only diagnostic)
-    static int bfin_calls = 0;
-    if (!skip_bfin || ++bfin_calls <= 30)
     hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(d->C), dim3(64), 0, s, part, pl.G, handed ? d->n_partials : pl.nchunk, d->C, ab, d->dgamma, d->dbeta,
                        d->param_accumulate, handed ? d->partials : nullptr);
     HV_LAUNCH_CHECK();
     const int batch_stats = (d->norm == HV_NORM_INSTANCE || d->training) ? 1 : 0;
     const long long n = (long long)pl.R * (vec ? d->C / 4 : d->C);
     const dim3 agrid(apply_grid(n, pl.G), pl.G);
-    static const int skip_bapply = getenv("HV_DIAG_SKIP") && strstr(getenv("HV_DIAG_SKIP"), "norm_bwd") ? 1 : 0;     // timing-only diagnostic (wrong results)
-    if (skip_bapply) return HV_OK;
     if (d->f16) {
         if (vec) hipLaunchKernelGGL((norm_bwd_apply_kernel<true, true>), agrid, dim3(256), 0, s, k, ab, batch_stats);
         else hipLaunchKernelGGL((norm_bwd_apply_kernel<false, true>), agrid, dim3(256), 0, s, k, ab, batch_stats);

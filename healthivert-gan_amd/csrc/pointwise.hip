@@ -513,8 +513,8 @@ extern "C" int hv_gan_loss_head(const float* z, long long n, int target_is_real,
 
 // Both ranges in ONE launch of ceil(n / 256) workgroups: a workgroup writes its block sums (loss, stored gradient) to `part`, takes a ticket, and the workgroup
 // that draws the last one folds the partials of each range in their fixed order (deterministic) into the loss slots and the bias gradient, then puts the
-// ticket back to zero for the next launch.  Hand-off per the MI355X guide: every wave's stores drained, workgroup barrier, ONE agent-scope release, relaxed
-// agent-scope fetch_add; the last arriver: ONE agent-scope acquire, barrier, plain loads.  (A single 1 024-thread workgroup walking all 28 800 logits of a
+// ticket back to zero for the next launch.  Hand-off by the fence-free fold of hv_common.h: thread 0 publishes its sums, waits for its own stores and takes a
+// relaxed agent-scope ticket; the last arriver: ONE agent-scope acquire (hv_acquire_once), then plain loads.  (A single 1 024-thread workgroup walking all 28 800 logits of a
 // bs-32 pass took 29 us: 28 dependent load -> exp / log1p -> store rounds per lane.)
 __global__ __launch_bounds__(256) void gan_loss_head_pair_kernel(const float* __restrict__ z0, int n0, float t0, float* loss0, _Float16* __restrict__ c0,
                                                                  const float* __restrict__ z1, int n1, float t1, float* loss1, _Float16* __restrict__ c1, int mode,

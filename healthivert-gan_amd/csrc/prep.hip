@@ -331,8 +331,6 @@ __global__ __launch_bounds__(256) void weight_layout_fused_kernel(const hv_wprep
 
 extern "C" int hv_weight_prep2(const hv_wprep_layer* d_layers, int n_layers, long long max_numel, int any_sn, int any_legacy, void* stream) {
     if (!d_layers || n_layers <= 0 || max_numel <= 0) return HV_ERR_ARG;
-    static const int fused = getenv("HV_WPREP_FUSED") ? atoi(getenv("HV_WPREP_FUSED")) : 1;      // A/B knob
-    if (!fused) return hv_weight_prep(d_layers, n_layers, max_numel, stream);
     if (any_sn) {      // sigma (and the power iteration); layers without spectral norm keep the 1.0 their sigma slot was created with
         hipLaunchKernelGGL(weight_prep_kernel, dim3(n_layers), dim3(PREP_THREADS), 0, (hipStream_t)stream, d_layers);
         HV_LAUNCH_CHECK();
@@ -584,9 +582,9 @@ static int act_bwd_blocks(long long npix, int C, int* rows_per_block) {
     const int rstep = act_vec_ok(C) ? 256 / (C / 4) : 256 / C;
     long long rpb = (long long)rstep * 4;       // one 4-row batch per lane unless that exceeds the block cap below (256 blocks = one per CU was a latency chain)
     long long nb = (npix + rpb - 1) / rpb;
-    static const int ab = getenv("HV_ACT_BLOCKS") ? atoi(getenv("HV_ACT_BLOCKS")) : 2048;   // tuning knob
-    if (nb > ab) {   // ~8 workgroups per CU keep enough loads in flight to stream from HBM
-        rpb = (npix + ab - 1) / ab;
+    constexpr int kBlocks = 2048;
+    if (nb > kBlocks) {   // ~8 workgroups per CU keep enough loads in flight to stream from HBM
+        rpb = (npix + kBlocks - 1) / kBlocks;
         rpb = (rpb + rstep - 1) / rstep * rstep;
         nb = (npix + rpb - 1) / rpb;
     }

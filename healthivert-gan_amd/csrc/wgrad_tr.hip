@@ -511,15 +511,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_trd_kernel(const WTrK p) {
 struct WTrPlan { int BN, BC, gx, dil; size_t lds; bool dma; };
 
 static bool wgrad_tr_plan(const hv_wgrad_desc* d, WTrPlan* pl) {
-    static const int enabled = getenv("HV_WGRAD_TR") ? atoi(getenv("HV_WGRAD_TR")) : 1;   // A/B knob
-    if (!enabled || d->precision != HV_F16 || !d->x_f16 || !d->g_f16 || d->KH != d->KW) return false;
+    if (d->precision != HV_F16 || !d->x_f16 || !d->g_f16 || d->KH != d->KW) return false;
     if (!((d->KH == 3 || d->KH == 4) && (d->stride == 1 || d->stride == 2))) return false;
     pl->dil = 1;
     if (d->dil != 1) {
         // dilated same-size 3x3 layers (the generators' d = 2, 4, 8): d*d undilated weight gradients on the residue sub-grids, summed in the same accumulators
         // (round 4; they ran in the gather kernel at 24.5 us).  d = 16 leaves 4 x 4-pixel sub-grids in 8 x 16 tiles: stays there
-        static const int dilated = getenv("HV_WGRAD_TR_DIL") ? atoi(getenv("HV_WGRAD_TR_DIL")) : 1;      // A/B knob
-        if (!dilated || (d->dil != 2 && d->dil != 4 && d->dil != 8) || d->KH != 3 || d->stride != 1 || d->pad != d->dil || d->in_shift) return false;
+        if ((d->dil != 2 && d->dil != 4 && d->dil != 8) || d->KH != 3 || d->stride != 1 || d->pad != d->dil || d->in_shift) return false;
         if (d->H % d->dil || d->W % d->dil || d->Ho != d->H || d->Wo != d->W) return false;
         pl->dil = d->dil;
     } else if (d->Ho != (d->H + 2 * d->pad - d->KH) / d->stride + 1 || d->Wo != (d->W + 2 * d->pad - d->KW) / d->stride + 1) return false;
@@ -532,8 +530,8 @@ static bool wgrad_tr_plan(const hv_wgrad_desc* d, WTrPlan* pl) {
     pl->BC = d->Cin >= 32 ? 32 : 16;
     {   // layers with a small dW (the generators' 64 x 64 x 9): every workgroup writes a whole slab of its tile pair, so 32-filter blocks halve the slab bytes
         // (and double the pixel tiles per workgroup at the same workgroup count)
-        static const int bn32 = getenv("HV_WTR_BN32") ? atoi(getenv("HV_WTR_BN32")) : 1;      // A/B knob (three same-box pairs: 8.85 -> 8.82 ms)
-        if (bn32 && d->stride == 1 && d->Cout == 64 && d->Cin <= 64 && d->Cin >= 32) pl->BN = 32;
+        // (three same-box pairs: 8.85 -> 8.82 ms)
+        if (d->stride == 1 && d->Cout == 64 && d->Cin <= 64 && d->Cin >= 32) pl->BN = 32;
     }
     // (Measured and not kept, round 4: 16 x 16 blocks -- 16 block pairs x 32 pixel chunks, 9-KB slab tiles, 4.7 MB of slabs instead of 18.9 -- for the
     // generators' 32- / 64-channel 3x3 layers: 64 -> 64 @64^2 21.6 -> 29.1 us, 32 -> 32 @128^2 19.4 -> 27.1, 32 -> 32 @256^2 40.2 -> 91.7 at the best of 256 .. 2048
@@ -543,8 +541,7 @@ static bool wgrad_tr_plan(const hv_wgrad_desc* d, WTrPlan* pl) {
     const int PH = 7 * d->stride + d->KH, PW = 15 * d->stride + d->KW;
     pl->lds = (size_t)128 * wtr_stride(pl->BN, 1) + (size_t)PH * PW * wtr_stride(pl->BC, d->stride);
     // the LDS-DMA form: 64-channel output blocks, its fixed input block (32 channels at stride 1, 16 at stride 2), no fused upsampling
-    static const int dma_on = getenv("HV_WGRAD_TRD") ? atoi(getenv("HV_WGRAD_TRD")) : 1;   // A/B knob
-    pl->dma = dma_on && pl->BN == 64 && pl->BC == 32 && d->in_shift == 0 && pl->dil == 1;
+    pl->dma = pl->BN == 64 && pl->BC == 32 && d->in_shift == 0 && pl->dil == 1;
     const bool dma_candidate = pl->dma;
     if (pl->dma) {
         const int PWP = d->stride == 1 ? 24 : 48, XI = PH * PWP * (pl->BC / 8);
@@ -555,13 +552,12 @@ static bool wgrad_tr_plan(const hv_wgrad_desc* d, WTrPlan* pl) {
     // generators' 64-channel layers: 2 tiles, 256 slabs of 147 KB = 38 MB for 17 MB of operands) is bound by its slab traffic, not by its MFMAs
     // (step-level A/B, round 3, same box: PatchGAN layers 512 -> 256 workgroups 9.43 -> 9.25 ms (their slabs are 8 MB each); 192: 9.23; the
     // generators' layers 512 / 256: no difference, 128: +0.2 ms)
-    static const int want_big = getenv("HV_WGRAD_TR_WGS") ? atoi(getenv("HV_WGRAD_TR_WGS")) : 256;
-    static const int want_small = getenv("HV_WGRAD_TR_WGS_SMALL") ? atoi(getenv("HV_WGRAD_TR_WGS_SMALL")) : 512;
+    constexpr int kWantBig = 256, kWantSmall = 512;
     auto chunks = [&]() {
         const long long pairs = (long long)hv_cdiv(d->Cout, pl->BN) * hv_cdiv(d->Cin, pl->BC);
         // (the small-dW rule by BYTES since round 4: with 32-channel blocks at stride 2 the PatchGAN 64 -> 128 layer has 4 pairs too, and 128 slabs of its
         // 0.5-MB dW would be 67 MB)
-        const int want = (pairs <= 4 && (long long)d->Cout * d->KH * d->KW * d->Cin * 4 <= 256 * 1024) ? want_small : want_big;
+        const int want = (pairs <= 4 && (long long)d->Cout * d->KH * d->KW * d->Cin * 4 <= 256 * 1024) ? kWantSmall : kWantBig;
         long long gx = (want + pairs - 1) / pairs;
         if (gx > ntiles) gx = ntiles;
         if (gx < 1) gx = 1;
@@ -954,13 +950,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_thing_kernel(const WTrK p) {
 // ---- thin input: which layers, how many workgroups
 struct WThinPlan { int kind, gx; size_t lds; };      // kind 1: 5x5 stride 1, Cin <= 4, Cout <= 16 (the generators' stems); 2 / 3: Cout <= 4, stride 1 -- 4x4 with Cin % 64 == 0 (the PatchGAN head) / 3x3 with Cin <= 16 (the generators' heads)
 static bool wgrad_thin_plan(const hv_wgrad_desc* d, WThinPlan* pl) {
-    static const int enabled = getenv("HV_WGRAD_THIN") ? atoi(getenv("HV_WGRAD_THIN")) : 3;   // A/B knob: bit 0 thin input (kind 1), bit 1 thin gradient (kinds 2, 3)
-    if (!enabled || d->precision != HV_F16 || !d->x_f16 || !d->g_f16 || d->KH != d->KW || d->dil != 1 || d->in_shift != 0) return false;
+    if (d->precision != HV_F16 || !d->x_f16 || !d->g_f16 || d->KH != d->KW || d->dil != 1 || d->in_shift != 0) return false;
     if (d->Ho != (d->H + 2 * d->pad - d->KH) / d->stride + 1 || d->Wo != (d->W + 2 * d->pad - d->KW) / d->stride + 1) return false;
     pl->kind = 0;
     const bool thin_x = d->Cin <= 4 && !(d->x_ld & 3) && !(d->x_coff & 3) && !(d->Cout & 7) && !(d->g_ld & 7) && !(d->g_coff & 7);
-    const bool thin_g = (enabled & 2) && d->Cout <= 4 && !(d->g_ld & 3) && !(d->g_coff & 3) && d->stride == 1 && !d->dbias && !(d->x_ld & 3) && !(d->x_coff & 3);
-    if ((enabled & 1) && thin_x && d->KH == 5 && d->stride == 1 && d->Cout <= 16) pl->kind = 1;
+    const bool thin_g = d->Cout <= 4 && !(d->g_ld & 3) && !(d->g_coff & 3) && d->stride == 1 && !d->dbias && !(d->x_ld & 3) && !(d->x_coff & 3);
+    if (thin_x && d->KH == 5 && d->stride == 1 && d->Cout <= 16) pl->kind = 1;
     else if (thin_g && d->KH == 4 && !(d->Cin & 63) && !(d->x_ld & 7) && !(d->x_coff & 7)) pl->kind = 2;
     else if (thin_g && d->KH == 3 && d->Cin <= 16 && d->Cin > 4) pl->kind = 3;
     // (Measured and not kept: the PatchGAN stem -- 4x4 stride 2, 1 -> 64 -- as wgrad_thinx_kernel<4, 2, 64>: 249 registers, two tiles of loads in flight, 33.3 / 26.9 us
@@ -973,9 +968,9 @@ static bool wgrad_thin_plan(const hv_wgrad_desc* d, WThinPlan* pl) {
     if (pl->lds < 4096) pl->lds = 4096;      // (the carried fold's workgroups use the launch's LDS)
     // tiles: output pixels (thin input) / input pixels (thin gradient)
     const long long ntiles = pl->kind == 1 ? (long long)d->B * hv_cdiv(d->Ho, 8) * hv_cdiv(d->Wo, 16) : (long long)d->B * hv_cdiv(d->H, 8) * hv_cdiv(d->W, 16);
-    static const int want = getenv("HV_WGRAD_THIN_WGS") ? atoi(getenv("HV_WGRAD_THIN_WGS")) : 512;      // tuning knob (kernel + fold, us at 128 / 256 / 384 / 512 / 768 / 1024: 41.5 / 26.1 / 22.0 / 19.7 / 20.9 / 23.8)
+    constexpr int kWant = 512;      // workgroups (kernel + fold, us at 128 / 256 / 384 / 512 / 768 / 1024: 41.5 / 26.1 / 22.0 / 19.7 / 20.9 / 23.8)
     const long long blocks = pl->kind == 2 ? d->Cin / 64 : 1;      // channel blocks along y
-    long long gx = want / blocks;
+    long long gx = kWant / blocks;
     if (gx < 32) gx = 32;
     pl->gx = (int)(gx < ntiles ? gx : ntiles);
     return true;

@@ -149,9 +149,9 @@ class GradSync:
     def exchange_stream(self, device):
         if self.stream is None:
             from . import engine
-            # default priority.  A high-priority exchange stream (HV_DDP_COMM_PRIO=-1) gets a hardware queue of its own whose scheduling
-            # slows the compute streams' phase graphs: one-rank rehearsal of the exact schedule, same device, 13.85 ms/step against 11.73
-            self.stream = engine.named_stream('exchange', device, priority=int(os.environ.get('HV_DDP_COMM_PRIO', '0')))
+            # default priority.  A high-priority exchange stream gets a hardware queue of its own whose scheduling slows the compute streams'
+            # phase graphs: one-rank rehearsal of the exact schedule, same device, 13.85 ms/step against 11.73
+            self.stream = engine.named_stream('exchange', device)
         return self.stream
 
     def reduce_branch(self, flat, producer=None):
@@ -159,22 +159,15 @@ class GradSync:
         behind the previous one by an explicit edge, in the order of the calls (D_1, D_2, D_3, G: the same on every rank by construction; RCCL requires
         it) -- ordered after everything queued on `producer` (default: the current stream), which continues when the mean is there.  Under stream capture
         the collectives are kernel nodes of the graph being captured, and the other streams keep running beside them.
-        Two forms (HV_DP_BRANCH): 'chain' (default) issues the collective on the PRODUCER's stream behind an event recorded after the previous collective
-        (D_k's mean beside the other discriminators' passes; the only extra edges are joins between branches that exist anyway); 'stream' issues all of
-        them on the exchange stream (a branch of its own: hipStreamEndCapture of ROCm 7.0 / 7.2 crashes on that topology, kept for newer runtimes)."""
+        The collective is issued on the PRODUCER's stream behind an event recorded after the previous collective (D_k's mean beside the other
+        discriminators' passes; the only extra edges are joins between branches that exist anyway).  (All of them on the exchange stream, a branch of
+        its own, crashes hipStreamEndCapture of ROCm 7.0 / 7.2: retired.)"""
         if not flat.is_cuda or flat.dtype != torch.float32:
             raise RuntimeError('reduce_branch: fp32 device tensors only')
         comm = self.open()
         if comm is None:
             raise RuntimeError('reduce_branch: needs an RCCL process group')
         producer = producer if producer is not None else torch.cuda.current_stream(flat.device)
-        if os.environ.get('HV_DP_BRANCH', 'chain') == 'stream':
-            st = self.exchange_stream(flat.device)
-            st.wait_stream(producer)
-            with torch.cuda.stream(st):
-                comm.all_reduce_mean(flat)
-            producer.wait_stream(st)
-            return
         capturing = torch.cuda.is_current_stream_capturing()
         prev = self._chain.get(capturing)
         if prev is not None and prev[0] != producer.cuda_stream:

@@ -190,12 +190,12 @@ class ParamSet:
         pi = bool(power_iter)
         table = self.t_prep[pi]
         tset = 'full'
-        if LEAN and LEAN_TABLES and ops.precision_id(None) == ops.F16:
+        if LEAN and ops.precision_id(None) == ops.F16:
             tset = tuple((c.use_fwd, c.use_bwd) for c in self.convs)
         if only_if_stale and not pi and PREP_SKIP and self.prepared is not None and self.prepared[0] == self.version and self.prepared[1] in ('full', tset):
             return      # the tables in memory were written from these very weights (and cover the tables asked for)
         self.prepared = (self.version, tset)
-        if LEAN and LEAN_TABLES and ops.precision_id(None) == ops.F16:
+        if LEAN and ops.precision_id(None) == ops.F16:
             # inside the train step, after the step has been seen once for this batch shape: the layout pass skips the tables no kernel of the layer reads
             # (fp16 mode: the big layers read the fragment-ordered tables only -- 4 of 20 bytes per weight)
             key = (self._key, pi, tuple((c.use_fwd, c.use_bwd) for c in self.convs))
@@ -250,9 +250,9 @@ class ConvNode:
 
     def split_forward(self, prec):
         """True when the forward reads [up-sampled low | x1] without the concat: asked of the C dispatch (hv_conv2d_supported -- the x1 kernel exists
-        for two channel shapes only and follows the HV_CONV_LF knobs), once per node; otherwise the materialised concat is built and read."""
+        for two channel shapes only and follows the HV_CONV_LF knob), once per node; otherwise the materialised concat is built and read."""
         p = self.p
-        if self.split is None or not SPLIT_CONCAT or p.w_fwd_t2 is None or ops.precision_id(prec) != ops.F16:
+        if self.split is None or p.w_fwd_t2 is None or ops.precision_id(prec) != ops.F16:
             return False
         key = (ops.precision_id(prec), p.w_fwd_t2.data_ptr(), self.y.t.data_ptr())
         if getattr(self, '_split_ok', None) is None or self._split_ok[0] != key:
@@ -310,7 +310,6 @@ def named_stream(name, device, priority=0):
 
 
 PREP_SKIP = os.environ.get('HV_PREP_SKIP', '1') != '0'      # A/B knob: ParamSet.prep(only_if_stale=True) may skip (see there)
-LEAN_TABLES = os.environ.get('HV_LEAN_TABLES', '1') != '0' and os.environ.get('HV_WPREP_FUSED', '1') != '0'   # A/B knob: see ParamSet.prep
 LEAN = False              # set by lean_tables(): the caller vouches that every convolution of its networks has run once for the current shapes
 
 
@@ -327,8 +326,6 @@ def lean_tables(on=True):
         LEAN = prev
 
 
-SPLIT_CONCAT = os.environ.get('HV_SPLIT_CONCAT', '1') != '0'   # [up-sampled | 1 channel] concat layers read the small tensor + the channel (A/B knob)
-FUSE_DBIAS = os.environ.get('HV_FUSE_DBIAS', '1') != '0'   # bias gradients computed inside the weight-gradient kernels
 SERIAL = False            # True: no side streams at all (per-kernel timing with HIP events needs the GPU to itself)
 
 
@@ -406,7 +403,7 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
     want_dbias = p.bias is not None and node.use_bias and wgrad and not dbias_done      # dbias_done: the caller's seed pass already summed it
     # the bias gradient (column sums of the activation gradient) rides in the weight-gradient kernels, which stream g anyway;
     # conv_transpose nodes (roles of x and g swapped there) and unpadded channel counts keep the stand-alone reduction
-    fuse_dbias = want_dbias and not node.transposed and FUSE_DBIAS and p.coutP == p.cout
+    fuse_dbias = want_dbias and not node.transposed and p.coutP == p.cout
     if (node.act != 'none' and not premultiplied) or (want_dbias and not fuse_dbias):
         ops.act_backward(gy, node.y, 'none' if premultiplied else node.act, dbias=p.bias.grad if (want_dbias and not fuse_dbias) else None, dbias_accumulate=dbias_accumulate)
     gfull = Act(gy.t, p.coutP, gy.coff)
@@ -452,7 +449,7 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
                        precision=prec, mul=(Act(node.x.t, p.cin_fwd, node.x.coff), mul_x) if mul_x else None, wuse=(p, 'use_bwd'), bn=bn)
 
 
-BRANCHES = os.environ.get('HV_G_BRANCHES', '1') != '0'   # independent generator branches on two HIP streams / graph branches
+# independent generator branches on two HIP streams / graph branches
 #   (step-level A/B under graph replay, three pairs in one call: 14.80 / 14.81 / 14.85 ms on vs 15.01 / 14.96 / 15.05 ms off)
 _branch_streams = {}
 
@@ -460,7 +457,7 @@ _branch_streams = {}
 def branch_stream():
     """Side stream for an independent branch of the generator (None when everything must stay on one stream).  Weight gradients
     issued on it stay in line (no nested fork: see NO_FORK_STREAMS)."""
-    if not BRANCHES or SERIAL:
+    if SERIAL:
         return None
     cur = torch.cuda.current_stream()
     if cur.cuda_stream in NO_FORK_STREAMS:
@@ -471,9 +468,6 @@ def branch_stream():
         st = _branch_streams[key] = named_stream('generator-branch', cur.device)
         NO_FORK_STREAMS.add(st.cuda_stream)
     return st
-
-
-FUSE_ACT = os.environ.get('HV_FUSE_ACT', '1') != '0'   # act' of the producer layer applied in the consumer's data-gradient epilogue
 
 
 def _pool2_node_ok(node, gfull, gx, prec):
@@ -491,7 +485,7 @@ def chain_link(n, nxt, prec=None):
             return False
     elif n.shift:
         return False
-    return bool(FUSE_ACT and nxt is not None and n.need_dx and not n.transposed and nxt.act != 'none'
+    return bool(nxt is not None and n.need_dx and not n.transposed and nxt.act != 'none'
                 and n.x.t is nxt.y.t and n.x.coff == nxt.y.coff and n.p.cin_fwd <= nxt.y.t.shape[-1] - nxt.y.coff)
 
 
@@ -502,7 +496,7 @@ def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=Fa
     act-gradient pass (read g, read y, write g) between two convs disappears.
     stop_before: the node that follows nodes[-1] in the chain but is run by the caller later (with
     premultiplied=chain_link(nodes[-1], stop_before))."""
-    pre = premultiplied_first and FUSE_ACT     # every writer of nodes[0]'s output gradient already applied its act'
+    pre = premultiplied_first     # every writer of nodes[0]'s output gradient already applied its act'
     for i, n in enumerate(nodes):
         nxt = nodes[i + 1] if i + 1 < len(nodes) else stop_before
         link = chain_link(n, nxt, prec)
@@ -511,11 +505,8 @@ def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=Fa
 
 
 # ================================================================================================ contextual attention
-CA_FUSE_PREP = os.environ.get('HV_CA_FUSE_PREP', '1') != '0'   # score-fusion adjoint + Gs + coef in one kernel at 32 x 32 (A/B knob)
-CA_F16_IO = os.environ.get('HV_CA_F16_IO', '1') != '0'   # the attention block's boundary kernels read / write fp16-stored maps themselves (A/B knob)
-CA_F16_COPIES = os.environ.get('HV_CA_F16_COPIES', '1') != '0'   # GEMM route: fp16 operand copies written by their producers (wp_h, A as fp16 only); A/B knob
-CA_GRAM = os.environ.get('HV_CA_GRAM', '1') != '0'     # GEMM route: matching scores and their gradient on the pixel Gram matrix (csrc/attention_gram.hip); A/B knob
-CA_GEMM = os.environ.get('HV_CA_GEMM', '1') != '0'     # fp16 mode: the attention block's five contractions as batched NT GEMMs (csrc/bgemm.hip)
+CA_GRAM = True     # GEMM route: matching scores and their gradient on the pixel Gram matrix (csrc/attention_gram.hip); False: the patch-table GEMMs (a test's reference)
+CA_GEMM = True     # fp16 mode: the attention block's five contractions as batched NT GEMMs (csrc/bgemm.hip); False: the conv kernels (a test's reference)
 
 
 def _bgemm(A, B, C, M, N, K, batch, alpha=1.0, colscale=None, b_split=0):
@@ -559,40 +550,34 @@ class AttentionPlan:
         gemm = CA_GEMM and ops.precision_id(prec) == ops.F16 and (9 * C) % 32 == 0 and L % 32 == 0 and C % 4 == 0
         self.gemm = gemm
         # (the GEMM route's boundary kernels read / write fp16-stored maps themselves: same values, no conversion copies)
-        if f.f16 and not (gemm and CA_F16_IO):
+        if f.f16 and not gemm:
             self.f32 = getattr(self, 'f32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=f.t.device))
             ops.copy_channels(f, self.f32, mode=0)
             f = self.f32
-        if out.f16 and not (gemm and CA_F16_IO):
+        if out.f16 and not gemm:
             self.out32 = getattr(self, 'out32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=f.t.device))
             out_user, out = out, self.out32
         if gemm:
             # GEMM route: the patch tables that are only GEMM operands are stored as fp16 (half the bytes through the vector memory path, no
             # conversion when staged); wp stays fp32 (norms, the patch gradient's coefficient term), its transpose is written as fp16
             # Round 3: the copies are written by their PRODUCERS -- wp_h beside wp by the patch kernel, the attention matrix as fp16 only by the
-            # soft-max (HV_CA_F16_COPIES=0: the previous form, fp32 tables converted when a GEMM stages them: same GEMM bits) -- and the transpose of
+            # soft-max (the form before, fp32 tables converted when a GEMM stages them, gave the same GEMM bits; retired) -- and the transpose of
             # wp, which only the backward reads, is taken there
             if getattr(self, 'raw_h', None) is None:
                 hz = lambda *s: torch.zeros(*s, dtype=torch.float16, device=f.t.device)
                 self.raw_h, self.rawT_h, self.wpT_h = hz(B, L, 16 * C), hz(B, 16 * C, L), hz(B, 9 * C, L)
-                self.O = torch.zeros(B, L, 16 * C, dtype=torch.float32, device=f.t.device)
-                if CA_F16_COPIES:
-                    self.wp_h, self.A_h = hz(B, L, 9 * C), hz(B, L, L)
-                    self.O = hz(B, L, 16 * C)          # the paste product only feeds the fold (whose result is stored as fp16): fp16 too
-            self.f16_copies = CA_F16_COPIES
+                self.wp_h, self.A_h = hz(B, L, 9 * C), hz(B, L, L)
+                self.O = hz(B, L, 16 * C)          # the paste product only feeds the fold (whose result is stored as fp16): fp16 too
             # scores on the pixel Gram matrix (K = C, no patch tables) where the kernels serve the shape
-            self.gram = bool(CA_GRAM and self.f16_copies and f.f16 and C == 64 and self.w in (32, 64) and f.ld % 8 == 0 and f.coff == 0)
+            self.gram = bool(CA_GRAM and f.f16 and C == 64 and self.w in (32, 64) and f.ld % 8 == 0 and f.coff == 0)
             if self.gram:
                 if getattr(self, 'fd_h', None) is None:
                     self.fd_h = torch.zeros(B, L, C, dtype=torch.float16, device=f.t.device)
                     self.fdT_h = torch.zeros(B, C, L, dtype=torch.float16, device=f.t.device)
                     self.q = torch.zeros(B, L, dtype=torch.float32, device=f.t.device)
                 L_.call('hv_ca_gram_down', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd_h), ptr(self.fdT_h), ptr(self.q), stream())
-            elif self.f16_copies:
-                L_.call('hv_ca_patches_h', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), ptr(self.wp_h), ptr(self.norm), ptr(self.rnorm), stream())
             else:
-                L_.call('hv_ca_patches', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), None, ptr(self.norm), ptr(self.rnorm), stream())
-                L_.call('hv_transpose_batched_f16', ptr(self.wp), ptr(self.wpT_h), B, L, 9 * C, stream())
+                L_.call('hv_ca_patches_h', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), ptr(self.wp_h), ptr(self.norm), ptr(self.rnorm), stream())
             L_.call('hv_ca_raw_patches_f16', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.raw_h), ptr(self.rawT_h), stream())
         else:
             L_.call('hv_ca_patches', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), ptr(self.wpT), ptr(self.norm), ptr(self.rnorm), stream())
@@ -604,12 +589,10 @@ class AttentionPlan:
                     self.h, self.w, ptr(self.mm_b), stream())
         else:
             L_.call('hv_ca_mask', ptr(mask_img), self.img_hw[0], self.img_hw[1], self.h, self.w, ptr(self.mm), stream())
-        f16c = gemm and self.f16_copies
         if gemm and self.gram:
             L_.call('hv_ca_gram_scores', ptr(self.fd_h), ptr(self.q), B, self.h, self.w, C, ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), stream())
         elif gemm:    # the 3x3 patches of the (zero-padded) map are both the conv's input columns and its filters: scores = rnorm (.) wp wp^T
-            wp_op = self.wp_h if f16c else self.wp
-            _bgemm(wp_op, wp_op, self.S0.t, L, L, 9 * C, B, colscale=self.rnorm)
+            _bgemm(self.wp_h, self.wp_h, self.S0.t, L, L, 9 * C, B, colscale=self.rnorm)
         else:
             ops.conv2d(self.fd, self.wp, self.S0, 3, 1, 1, 1, w_bstride=L * 9 * C, ch_scale=self.rnorm, ch_scale_bstride=L, precision=prec)
         if self.fuse:
@@ -617,7 +600,7 @@ class AttentionPlan:
             s = self.S1
         else:
             s = self.S0
-        if f16c:
+        if gemm:
             L_.call('hv_ca_softmax_f16', ptr(s.t), ptr(self.mm_b if per_sample_mask else self.mm), ctypes.c_longlong(L if per_sample_mask else 0),
                     ptr(self.A_h), B, L, ctypes.c_float(self.scale), ptr(self.argmax) if want_argmax else None, stream())
         elif per_sample_mask:
@@ -627,8 +610,8 @@ class AttentionPlan:
             L_.call('hv_ca_softmax', ptr(s.t), ptr(self.mm), ptr(self.A.t), B, L, ctypes.c_float(self.scale),
                     ptr(self.argmax) if want_argmax else None, stream())
         if gemm:    # paste = (A rawT^T) folded: O[p][(c, tap)], then every output pixel sums the 4 taps that reach it
-            _bgemm(self.A_h if f16c else self.A.t, self.rawT_h, self.O, L, 16 * C, L, B, b_split=C)          # rows of rawT [c][tap] taken as (tap, c): O[p][tap][c]
-            L_.call('hv_ca_fold_h' if self.O.dtype == torch.float16 else 'hv_ca_fold', ptr(self.O), ptr(out.t), out.f16, B, H, W, C, out.ld, ctypes.c_float(0.25), 0, stream())
+            _bgemm(self.A_h, self.rawT_h, self.O, L, 16 * C, L, B, b_split=C)          # rows of rawT [c][tap] taken as (tap, c): O[p][tap][c]
+            L_.call('hv_ca_fold_h', ptr(self.O), ptr(out.t), out.f16, B, H, W, C, out.ld, ctypes.c_float(0.25), 0, stream())
         else:
             ops.conv2d(self.A, self.rawT, out, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=C * 16 * L, precision=prec)
         if out_user is not None:
@@ -646,7 +629,7 @@ class AttentionPlan:
         bw = self.bw
         df_user = None
         gemm = getattr(self, 'gemm', False) and ops.precision_id(prec) == ops.F16
-        if dout.f16 and not (gemm and CA_F16_IO):
+        if dout.f16 and not gemm:
             self.dout32 = getattr(self, 'dout32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=dout.t.device))
             ops.copy_channels(dout, self.dout32, mode=0)
             dout = self.dout32
@@ -660,12 +643,9 @@ class AttentionPlan:
                 bw['dOraw_h'], bw['dOrawT_h'], bw['AT_h'] = hz(B, L, 16 * C), hz(B, 16 * C, L), hz(B, L, L)
             L_.call('hv_ca_raw_patches_f16', ptr(dout.t), dout.f16, B, H, W, C, dout.ld, ptr(bw['dOraw_h']), ptr(bw['dOrawT_h']), stream())
             _bgemm(bw['dOraw_h'], self.raw_h, bw['dA'].t, L, L, 16 * C, B, alpha=0.25)
-            if self.f16_copies:
-                L_.call('hv_transpose_batched_h2h', ptr(self.A_h), ptr(bw['AT_h']), B, L, L, stream())
-            else:
-                L_.call('hv_transpose_batched_f16', ptr(self.A.t), ptr(bw['AT_h']), B, L, L, stream())
+            L_.call('hv_transpose_batched_h2h', ptr(self.A_h), ptr(bw['AT_h']), B, L, L, stream())
             _bgemm(bw['AT_h'], bw['dOrawT_h'], self.O, L, 16 * C, L, B, b_split=C)      # d(raw patches)[l][tap][c] (the forward's O buffer is free by now)
-            L_.call('hv_ca_fold_h' if self.O.dtype == torch.float16 else 'hv_ca_fold', ptr(self.O), ptr(df.t), df.f16, B, H, W, C, df.ld, ctypes.c_float(0.25),
+            L_.call('hv_ca_fold_h', ptr(self.O), ptr(df.t), df.f16, B, H, W, C, df.ld, ctypes.c_float(0.25),
                     int(bool(accumulate)), stream())
         else:
             ops.conv2d(dout, self.raw, bw['dA'], 4, 2, 1, 1, alpha=0.25, w_bstride=L * 16 * C, precision=prec)
@@ -674,13 +654,13 @@ class AttentionPlan:
             ops.conv2d(bw['AT'], bw['dOrawT'], df, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=C * 16 * L,
                        accumulate=int(accumulate), precision=prec)
         # through softmax and score fusion
-        if gemm and self.f16_copies:
+        if gemm:
             L_.call('hv_ca_softmax_backward_f16', ptr(bw['dA'].t), ptr(self.A_h), ptr(self.mm), ptr(bw['dS1'].t), B, L, ctypes.c_float(self.scale), stream())
         else:
             L_.call('hv_ca_softmax_backward', ptr(bw['dA'].t), ptr(self.A.t), ptr(self.mm), ptr(bw['dS1'].t), B, L, ctypes.c_float(self.scale), stream())
         # ... and through the normalised patch matching (patches act as both filters and inputs)
         use_gram = gemm and getattr(self, 'gram', False)
-        if self.fuse and self.h == 32 and self.w == 32 and CA_FUSE_PREP:      # one pass, the plain scores' gradient stays on chip
+        if self.fuse and self.h == 32 and self.w == 32:      # one pass, the plain scores' gradient stays on chip
             L_.call('hv_ca_fuse_backward_prep', ptr(bw['dS1'].t), ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), ptr(bw['Gs'].t), ptr(bw['coef']),
                     B, self.h, self.w, stream())
         else:
@@ -695,8 +675,7 @@ class AttentionPlan:
             L_.call('hv_ca_gram_backward', ptr(bw['Gs'].t), ptr(self.fd_h), ptr(self.fdT_h), ptr(bw['coef']), B, self.h, self.w, C, ptr(df.t), df.ld, stream())
         else:
             if gemm:
-                if self.f16_copies:      # (the transpose of wp has this one reader)
-                    L_.call('hv_transpose_batched_f16', ptr(self.wp), ptr(self.wpT_h), B, L, 9 * C, stream())
+                L_.call('hv_transpose_batched_f16', ptr(self.wp), ptr(self.wpT_h), B, L, 9 * C, stream())      # (the transpose of wp has this one reader)
                 _bgemm(bw['Gs'].t, self.wpT_h, bw['dwp'].t, L, 9 * C, L, B)
             else:
                 ops.conv2d(bw['Gs'], self.wpT, bw['dwp'], 1, 1, 0, 1, w_bstride=9 * C * L, precision=prec)

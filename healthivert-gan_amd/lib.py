@@ -120,8 +120,6 @@ class _Lib:
             setattr(self, k, v)
 
     def call(self, name, *args):
-        if _DIAG_SKIP_C and name in _DIAG_SKIP_C:      # timing-only diagnostics (tools/marginal_step.sh): the entry point is not called, results are wrong
-            return
         rc = getattr(self.cdll, name)(*args)
         if rc != 0:
             if rc <= -1000:
@@ -133,7 +131,6 @@ class _Lib:
 
 
 _lib = None
-_DIAG_SKIP_C = frozenset(x for x in os.environ.get('HV_DIAG_SKIP_C', '').split(',') if x)
 
 
 def get():

@@ -15,13 +15,8 @@ from torch.nn.utils import spectral_norm as _sn_register
 from ._backend import engine as E
 from ._backend import lib as _lib
 from ._backend import ops
-from ._backend import lib as _lib_
-ptr, stream = _lib_.ptr, _lib_.stream
-from ._backend import ops as _ops_
-
-import os as _os_
-HEAD_SEED = _os_.environ.get('HV_HEAD_SEED', '1') != '0'      # fused seed pass of the 1-channel heads (A/B knob)
-Act, rup = _ops_.Act, _ops_.rup
+ptr, stream = _lib.ptr, _lib.stream
+Act, rup = ops.Act, ops.rup
 
 _ACTS = ('relu', 'elu', 'lrelu', 'prelu', 'selu', 'tanh', 'sigmoid', 'none')
 
@@ -315,10 +310,6 @@ class _GenPlan:
         self.g_head = {n: z(H, W, 1) for n in ('c17', 'c18', 'f17', 'f18')}
 
 
-G_WGRAD_BLOCK = _os_.environ.get('HV_G_WGRAD_BLOCK', '1') != '0'     # A/B knob: see Generator.run_backward
-G_WGRAD_COARSE = int(_os_.environ.get('HV_G_WGRAD_COARSE', '2'))      # A/B knob: see Generator.run_backward
-
-
 class Generator(nn.Module):
     def __init__(self, config, use_cuda):
         super().__init__()
@@ -469,13 +460,13 @@ class Generator(nn.Module):
         carrier = P.g_head[gname]                       # [B,H,W,4], channel 0 live
         book.twins[id(node.y.t)] = carrier.t            # the head's output gradient lives in the carrier
         pn = node.p
-        if HEAD_SEED and carrier.f16 and seed.dtype == torch.float32 and seed.is_contiguous() and pn.bias is not None and node.use_bias:
+        if carrier.f16 and seed.dtype == torch.float32 and seed.is_contiguous() and pn.bias is not None and node.use_bias:
             # seed -> act' -> carrier -> bias gradient in one pass (was: copy, in-place act' pass, column sums)
             ops.head_seed_backward(seed, node.y, Act(carrier.t, 4, 0), node.act, dbias=pn.bias.grad)
-            E.conv_backward(node, book, prec, premultiplied=True, dbias_done=True, mul_x=mul_x if E.FUSE_ACT else None)
+            E.conv_backward(node, book, prec, premultiplied=True, dbias_done=True, mul_x=mul_x)
             return
         ops.copy_channels(Act(seed.view(P.B, P.H, P.W, 1)), carrier, mode=0)
-        E.conv_backward(node, book, prec, mul_x=mul_x if E.FUSE_ACT else None)
+        E.conv_backward(node, book, prec, mul_x=mul_x)
 
     def run_backward(self, P, d_coarse_seg, d_fine_seg, d_x_stage1, d_x_stage2, d_pred1, d_pred2):
         """Gradients of a scalar loss wrt the six differentiable outputs -> .grad of every parameter.
@@ -492,22 +483,22 @@ class Generator(nn.Module):
         d_pred1, d_pred2 = zero(d_pred1, P.pred1), zero(d_pred2, P.pred2)
         M = P.f_nodes_merge
         # the concat inputs of the split layers (forward: never built) for their weight gradients: up-sampled now, beside the head kernels -- or, where the
-        # layer's weight gradient goes to the side stream (HV_G_WGRAD_COARSE), on that stream right in front of it: 35 + 20 us of copies (67 + 33 MB written)
-        # off the head of the backward's critical path
+        # layer's weight gradient goes to the side stream, on that stream right in front of it: 35 + 20 us of copies (67 + 33 MB written) off the head of
+        # the backward's critical path
         late_copies = []
-        wg_block_now = G_WGRAD_BLOCK and not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
-        for grp, (node, low, cat, k2) in enumerate(((P.c_nodes[15], a['c14'], a['cat19'], 2 * c), (P.c_nodes[12], a['c12'], a['cat20'], 4 * c)), start=1):
+        wg_block_now = not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
+        for node, low, cat, k2 in ((P.c_nodes[15], a['c14'], a['cat19'], 2 * c), (P.c_nodes[12], a['c12'], a['cat20'], 4 * c)):
             if node.split_forward(prec):
-                if wg_block_now and G_WGRAD_COARSE >= grp:
+                if wg_block_now:
                     late_copies.append(lambda low=low, cat=cat, k2=k2: ops.copy_channels(low, cat.slice(0, k2), mode=1))
                 else:
                     ops.copy_channels(low, cat.slice(0, k2), mode=1)
-        # the refinement generator's weight gradients as ONE block on a side stream beside the coarse generator's whole backward (round 4, HV_G_WGRAD_BLOCK):
+        # the refinement generator's weight gradients as ONE block on a side stream beside the coarse generator's whole backward (round 4):
         # they only feed the optimiser, and the coarse backward -- a chain of small launches that leave most of a CU's registers and LDS free -- does not
         # depend on them.  One fork and one join (per-layer forks cost more than they returned and are gone).  Measured against it, three
         # same-box pairs each: a first block launched before the two branches (three streams busy there) +0.13 ms; the coarse generator's own weight
         # gradients in two more blocks +0.14 ms -- both removed.
-        wg_block = G_WGRAD_BLOCK and not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
+        wg_block = not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
         book.defer_wgrad = bool(wg_block)
         wg_side = E.named_stream('generator-wgrad-block', d_x_stage2.device) if wg_block else None
         def launch_block():
@@ -536,7 +527,7 @@ class Generator(nn.Module):
         ops.gap_fc_sigmoid_backward(d_pred2, P.pred2, P.f_pool, fg.fc_height.weight, book.twin(a['a11']),
                                     fg.fc_height.weight.grad, fg.fc_height.bias.grad, mul=(a['a11'], M[0].act) if pre11 else None)
         # cat11 = [conv10_atrous | pmconv10], both ELU: allconv11's data gradient applies elu' for both producers
-        E.conv_backward(M[0], book, prec, premultiplied=pre11, mul_x='elu' if E.FUSE_ACT else None)
+        E.conv_backward(M[0], book, prec, premultiplied=pre11, mul_x='elu')
         # the two branches run concurrently; both end in the gradient of f_in: the attention branch stops before its first conv,
         # which is run after the join (assign / accumulate order of the shared buffer stays that of the single-stream schedule)
         side = E.branch_stream()
@@ -559,7 +550,7 @@ class Generator(nn.Module):
         d_cs_total = P.d_cs_total
         ops.add_channels(Act(d_coarse_seg.view(B, H, W, 1)), book.twin(P.f_in).slice(1, 1), Act(d_cs_total.view(B, H, W, 1)))
         if wg_block:
-            book.defer_wgrad = G_WGRAD_COARSE > 0      # (the first coarse layers' weight gradients join the side streams' queue behind this block: see below)
+            book.defer_wgrad = True      # (the first coarse layers' weight gradients join the side streams' queue behind this block: see below)
             launch_block()
             book.deferred.extend(late_copies)          # (in front of the coarse weight gradients that read them, on their stream)
         # ---- coarse
@@ -572,7 +563,7 @@ class Generator(nn.Module):
         def pooled(node, low):
             pn = node.p
             g = E.Act(book.twin(node.y).t, pn.coutP, node.y.coff)
-            ok = E.FUSE_ACT and ops.pool2_ok(g, E.Act(book.twin(low).t, node.dx_c, low.coff), node.k, node.s, node.pad, node.d, prec, pn.w_bwd_h, pn.w_bwd_t)
+            ok = ops.pool2_ok(g, E.Act(book.twin(low).t, node.dx_c, low.coff), node.k, node.s, node.pad, node.d, prec, pn.w_bwd_h, pn.w_bwd_t)
             node.pool_to = (low, 'elu') if ok else None
             return ok
         p19 = pooled(C[15], a['c14'])
@@ -580,25 +571,19 @@ class Generator(nn.Module):
         if not p19:
             g14 = book.twin(a['c14'])
             ops.copy_channels(book.twin(a['cat19']).slice(0, 2 * c), g14, mode=3, accumulate=book.mark(g14))
-        # HV_G_WGRAD_COARSE (round 5): the coarse generator's first backward layers -- its heads and the 256 x 256 / 128 x 128 decoder, the most expensive weight
+        # Round 5: the coarse generator's first backward layers -- its heads and the 256 x 256 / 128 x 128 decoder, the most expensive weight
         # gradients of the chain -- hand their weight gradients to the side stream too (ONE more fork: it queues them behind the refinement generator's
         # block), so that the main stream walks these layers with data gradients only; the rest of the coarse backward keeps its weight gradients in line
         # (everything on the side stream made the block outlast the chain: +0.14 ms, round 4)
-        if wg_block and G_WGRAD_COARSE == 1:
-            book.defer_wgrad = False
-            launch_block()
         p20 = pooled(C[12], a['c12'])
         E.conv_backward_chain([C[14], C[13], C[12]], book, prec, premultiplied_first=p19)
         if not p20:
             g12 = book.twin(a['c12'])
             ops.copy_channels(book.twin(a['cat20']).slice(0, 4 * c), g12, mode=3, accumulate=book.mark(g12))
-        if wg_block and G_WGRAD_COARSE == 2:
+        if wg_block:      # (behind the heads and the 256 x 256 / 128 x 128 decoder)
             book.defer_wgrad = False
             launch_block()
         E.conv_backward_chain([C[11], C[10]], book, prec, premultiplied_first=p20, stop_before=C[9])
-        if wg_block and G_WGRAD_COARSE >= 3:
-            book.defer_wgrad = False
-            launch_block()
         pre10 = E.chain_link(C[10], C[9], prec)      # c10 feeds conv11 and the height head: both apply elu'(c10)
         ops.gap_fc_sigmoid_backward(d_pred1, P.pred1, P.c_pool, cg.fc_height.weight, book.twin(a['c10']),
                                     cg.fc_height.weight.grad, cg.fc_height.bias.grad, mul=(a['c10'], C[9].act) if pre10 else None)

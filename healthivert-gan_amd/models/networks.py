@@ -8,7 +8,6 @@ Generators/discriminators the hot path never instantiates (ResNet/U-Net G, pixel
 out of scope and raise NotImplementedError.
 """
 import functools
-import os
 
 import torch
 import torch.nn as nn
@@ -143,11 +142,8 @@ class GANLoss(nn.Module):
 
 
 # ================================================================================================ PatchGAN
-CONV_STATS = os.environ.get('HV_CONV_STATS', '1') != '0'     # A/B knob: BatchNorm statistics from the producing conv's epilogue
-LOSS_HEAD = os.environ.get('HV_LOSS_HEAD', '1') != '0'      # GAN loss kernel writes the logits layer's gradient carrier + bias gradient (A/B knob)
-CONV_BSTATS = os.environ.get('HV_CONV_BSTATS', '1') != '0'   # A/B knob: BatchNorm backward sums from the epilogue of the data gradient that writes dy
-FUSE_NORM_ACT = os.environ.get('HV_FUSE_NORM_ACT', '1') != '0'     # A/B knob, see _DiscPlan-based run_backward
-HEAD_NORM = os.environ.get('HV_HEAD_NORM', '1') != '0'     # A/B knob (same bits): the last normalisation + LeakyReLU made where the logits layer stages its input
+CONV_BSTATS = True   # BatchNorm backward sums from the epilogue of the data gradient that writes dy (False: a test's reference)
+HEAD_NORM = True     # (same bits) the last normalisation + LeakyReLU made where the logits layer stages its input (False: a test's reference)
 
 
 class _DiscPlan:
@@ -317,9 +313,9 @@ class NLayerDiscriminator(nn.Module):
                 if ent[key]:
                     head_xn = cand
             # BatchNorm statistics out of the conv's own epilogue where its kernel has one (the 4x4 stride-2 layers): the normalisation then
-            # skips its reduction pass over z (HV_CONV_STATS=0: always reduce)
+            # skips its reduction pass over z
             parts = 0
-            if CONV_STATS and self.norm_kind == 'batch' and training:      # (groups > 1: the partials are per image tile, in image order: the finalize sums each group's share)
+            if self.norm_kind == 'batch' and training:      # (groups > 1: the partials are per image tile, in image order: the finalize sums each group's share)
                 if 'parts' not in ent:
                     ent['parts'] = int(ent['node'].stats_parts(prec))
                     ent['partials'] = torch.zeros(max(1, ent['parts']) * ent['p'].cout * 2, dtype=torch.float32, device=x.device)
@@ -339,13 +335,11 @@ class NLayerDiscriminator(nn.Module):
         """GAN loss on P.logits + backward.  fp16 storage mode: the loss kernel writes d loss / d logit straight into the logits layer's gradient carrier
         and sums its bias gradient (hv_gan_loss_head) -- the copy, the column-sum pass and its finalize leave the chain between forward and backward."""
         last = P.layers[-1]
-        if LOSS_HEAD and P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
+        if P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
             pl = last['p']
             want_db = param_grads and pl.bias is not None and last['node'].use_bias
-            if not ops.gan_loss_pair(P.logits, target_is_real, loss, Act(P.g_logits.t, 4, 0), mode=mode, loss_weight=loss_weight, grad_weight=grad_weight,
-                                     dbias=pl.bias.grad if want_db else None, dbias_accumulate=accumulate):
-                ops.gan_loss(P.logits, target_is_real, mode, loss=loss, loss_weight=loss_weight, grad_weight=grad_weight, carrier=Act(P.g_logits.t, 4, 0),
-                             dbias=pl.bias.grad if want_db else None, dbias_accumulate=accumulate)
+            ops.gan_loss_pair(P.logits, target_is_real, loss, Act(P.g_logits.t, 4, 0), mode=mode, loss_weight=loss_weight, grad_weight=grad_weight,
+                              dbias=pl.bias.grad if want_db else None, dbias_accumulate=accumulate)
             return self.run_backward(P, None, need_dx=need_dx, param_grads=param_grads, accumulate=accumulate, logits_ready=True)
         if dz is None:
             dz = torch.empty_like(P.logits)
@@ -358,16 +352,12 @@ class NLayerDiscriminator(nn.Module):
         (hv_gan_loss_head), as loss_backward does for a whole batch."""
         last = P.layers[-1]
         B = P.B // 2
-        if LOSS_HEAD and P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
+        if P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
             pl = last['p']
             want_db = pl.bias is not None and last['node'].use_bias
-            # both halves in one single-workgroup launch where they fit (four tiny dependent launches between forward and backward -> one)
-            if not ops.gan_loss_pair(P.logits[:B], False, loss_fake, Act(P.g_logits.t[:B], 4, 0), P.logits[B:], True, loss_real, Act(P.g_logits.t[B:], 4, 0),
-                                     mode=mode, grad_weight=grad_weight, dbias=pl.bias.grad if want_db else None):
-                for half, (real, loss) in enumerate(((False, loss_fake), (True, loss_real))):
-                    sl = slice(half * B, (half + 1) * B)
-                    ops.gan_loss(P.logits[sl], real, mode, loss=loss, grad_weight=grad_weight, carrier=Act(P.g_logits.t[sl], 4, 0),
-                                 dbias=pl.bias.grad if want_db else None, dbias_accumulate=bool(half))
+            # both halves in one launch (four tiny dependent launches between forward and backward -> one)
+            ops.gan_loss_pair(P.logits[:B], False, loss_fake, Act(P.g_logits.t[:B], 4, 0), P.logits[B:], True, loss_real, Act(P.g_logits.t[B:], 4, 0),
+                              mode=mode, grad_weight=grad_weight, dbias=pl.bias.grad if want_db else None)
             return self.run_backward(P, None, need_dx=False, param_grads=True, accumulate=False, logits_ready=True)
         if dz is None:
             dz = torch.empty_like(P.logits)
@@ -390,10 +380,9 @@ class NLayerDiscriminator(nn.Module):
         book.twins.pop(getattr(P, '_in_id', None), None)
         P._in_id = id(P.x_in.t)
         book.twins[P._in_id] = P.dx.view(B, P.H, P.W, 1)
-        fuse0 = E.FUSE_ACT and len(P.layers) > 1 and P.layers[0]['node'].act != 'none' and not P.layers[1]['node'].shift
+        fuse0 = len(P.layers) > 1 and P.layers[0]['node'].act != 'none' and not P.layers[1]['node'].shift
         # a normalised layer's LeakyReLU' rides in the data-gradient epilogue of the layer that consumes its output z (one consumer), so the
-        # normalisation's backward starts from the gradient at ITS output and never reads z (HV_FUSE_NORM_ACT=0: the norm kernels apply it)
-        fuse_n = E.FUSE_ACT and FUSE_NORM_ACT
+        # normalisation's backward starts from the gradient at ITS output and never reads z
         for li in range(len(P.layers) - 1, -1, -1):
             ent = P.layers[li]
             L, node = ent['spec'], ent['node']
@@ -412,16 +401,16 @@ class NLayerDiscriminator(nn.Module):
                 bn = self.norm_kind == 'batch'
                 bparts = ent.get('bparts_used', 0)      # the consumer's data gradient (layer li + 1, a moment ago) summed for this normalisation
                 ops.norm_act_backward(gy, ent['y'], ent['z'], gz, self.norm_kind, P.training, ent['stats'],
-                                      gamma=nm.weight if bn else None, act='none' if fuse_n else 'lrelu',
+                                      gamma=nm.weight if bn else None, act='none',
                                       dgamma=nm.weight.grad if (bn and param_grads) else None,
                                       dbeta=nm.bias.grad if (bn and param_grads) else None, param_accumulate=accumulate,
                                       groups=P.groups, partials=ent['bpartials'] if bparts else None, n_partials=bparts)
             # the stem's output has one consumer (layer 1): its LeakyReLU' rides in layer 1's data-gradient epilogue
-            mul_x = P.layers[0]['node'].act if (li == 1 and fuse0) else ('lrelu' if (prev_normed and fuse_n) else None)
+            mul_x = P.layers[0]['node'].act if (li == 1 and fuse0) else ('lrelu' if prev_normed else None)
             # ... and where layer li - 1 is batch-normalised, the sums of ITS backward (sum g, sum g * xhat over the gradient this launch writes) leave
             # this data gradient's epilogue: the normalisation's backward then skips its reduction pass over g and z (HV_CONV_BSTATS=0: it reduces)
             bn_arg = None
-            if prev_normed and fuse_n and mul_x and CONV_BSTATS and self.norm_kind == 'batch' and P.training:
+            if prev_normed and mul_x and CONV_BSTATS and self.norm_kind == 'batch' and P.training:
                 pe = P.layers[li - 1]
                 bp = pe.setdefault('bparts', {})      # by statistics groups: a plan serves the batched fake | real pass (two groups) and a plain pass of the same size
                 if P.groups not in bp:

@@ -106,7 +106,6 @@ class Pix2PixModel(BaseModel):
         self.grad_scale = float(_os.environ.get('HV_GRAD_SCALE', '8192' if fp16 else '1'))
         if self.grad_scale <= 0 or (self.grad_scale != 1 and not float(self.grad_scale).is_integer()) or int(self.grad_scale) & (int(self.grad_scale) - 1):
             raise ValueError('HV_GRAD_SCALE must be a power of two')
-        self.concurrent_d = _os.environ.get('HV_CONCURRENT_D', '1') != '0'
         # fake | real discriminator passes as ONE 2B-sample launch sequence (per-half BatchNorm groups).  Round 2: no gain beside the three-stream overlap;
         # re-measured at the end of round 3 with the pipelined 4x4 kernels (one round of one workgroup per CU at bs 16): 8.18 -> 8.09 ms in three same-box
         # pairs, although it gives up the real-image passes' overlap with the generator forward.  Both the single-process and the data-parallel step take it.
@@ -133,7 +132,6 @@ class Pix2PixModel(BaseModel):
             raise ValueError("HV_DP_SCHEDULE must be 'auto', 'captured', 'overlapped' or 'graphs'")
         self.dp_preflight_record = None
         self._in_preflight = False
-        self.real_first = _os.environ.get('HV_REAL_FIRST', '1') != '0'   # D real passes overlap the generator forward
         self._through_ab = False
 
     # tensors forward()/backward bind as attributes; they live in per-shape buffers, so the names follow the active batch shape
@@ -344,9 +342,10 @@ class Pix2PixModel(BaseModel):
         else:
             # (only the loss value is wanted; in the fp16 mode the single-launch head serves it -- its gradient goes to the plan's carrier, which nothing reads)
             g = P.g_logits
-            if not (networks.LOSS_HEAD and g.f16 and g.t.shape[-1] == 4 and g.coff == 0 and
-                    ops.gan_loss_pair(P.logits, True, self._loss_slot(15 + k), ops.Act(g.t, 4, 0), mode=self.opt.gan_mode, loss_weight=1.0 / 6.0,
-                                      grad_weight=self.grad_scale / 6.0)):
+            if g.f16 and g.t.shape[-1] == 4 and g.coff == 0:
+                ops.gan_loss_pair(P.logits, True, self._loss_slot(15 + k), ops.Act(g.t, 4, 0), mode=self.opt.gan_mode, loss_weight=1.0 / 6.0,
+                                  grad_weight=self.grad_scale / 6.0)
+            else:
                 ops.gan_loss(P.logits, True, self.opt.gan_mode, loss=self._loss_slot(15 + k), loss_weight=1.0 / 6.0, dz=dz, grad_weight=self.grad_scale / 6.0)
 
     def backward_G(self, d_done=False):
@@ -404,12 +403,9 @@ class Pix2PixModel(BaseModel):
         self._dxs = {}
         if self._inline_exchange:
             self.grad_sync.chain_reset()      # the step's collectives form one chain D_1 -> D_2 -> D_3 -> G (ddp.GradSync.reduce_branch)
-            if __import__('os').environ.get('HV_DP_BRANCH', 'chain') == 'stream':
-                # the exchange branch leaves the MAIN stream here, before the discriminator streams do (a first-level fork of the capture)
-                self.grad_sync.exchange_stream(self.device).wait_stream(main)
-        split = self.real_first and not self.batch_d
+        split = not self.batch_d
         def on(k):
-            side = self._d_streams[k - 1] if (self.concurrent_d and not engine.SERIAL) else main
+            side = main if engine.SERIAL else self._d_streams[k - 1]
             if side is not main:
                 side.wait_stream(main)
             return side
@@ -446,7 +442,7 @@ class Pix2PixModel(BaseModel):
         backward (reference :370-382 up to optimizer_G.step)."""
         main = torch.cuda.current_stream(self.device)
         for k in (1, 2, 3):
-            side = self._d_streams[k - 1] if (self.concurrent_d and not engine.SERIAL) else main
+            side = main if engine.SERIAL else self._d_streams[k - 1]
             if side is not main and not self._through_ab:
                 side.wait_stream(main)
             with torch.cuda.stream(side):
@@ -497,7 +493,7 @@ class Pix2PixModel(BaseModel):
         return out
 
     def _join_d(self, main):
-        if self.concurrent_d and not engine.SERIAL:
+        if not engine.SERIAL:
             for side in self._d_streams:
                 main.wait_stream(side)
 
@@ -771,7 +767,7 @@ class Pix2PixModel(BaseModel):
             # one graph: D_k goes from its backward straight on to its Adam step and its pass for the generator on its own stream -- no join of the three
             # discriminator streams between the phases (that join only exists for the cut schedule's exchange): a discriminator that is done early
             # (D_3 reads the 128 x 128 crop) does not wait for the others
-            self._through_ab = self.concurrent_d and not engine.SERIAL and not (self._inline_exchange and self.dp_schedule == 'captured')
+            self._through_ab = not engine.SERIAL and not (self._inline_exchange and self.dp_schedule == 'captured')
             try:
                 self._phase_a(); self._phase_b(); self._phase_c()
             finally:

@@ -244,9 +244,6 @@ def conv2d(x, w, y, k, stride=1, pad=0, dil=1, bias=None, act='none', transposed
     return y
 
 
-POOL2 = os.environ.get('HV_POOL2', '1') != '0'      # A/B knob: data gradients of up-sampled inputs written pooled by the conv itself
-
-
 _SUPPORTED = {}
 
 
@@ -258,7 +255,7 @@ def conv2d_supported(*args, **kw):
 
 def pool2_ok(g, y_low, k, stride, pad, dil, precision, w_h, w_t, cout=None, w=None):
     """Can conv2d(..., transposed=True, pool2=True) serve this data gradient?  Asked of the C dispatch (hv_conv2d_supported), once per shape."""
-    if not POOL2 or w_h is None or w_t is None or precision_id(precision) != F16 or g.H != 2 * y_low.H or g.W != 2 * y_low.W:
+    if w_h is None or w_t is None or precision_id(precision) != F16 or g.H != 2 * y_low.H or g.W != 2 * y_low.W:
         return False
     co = y_low.C if cout is None else cout
     key = ('pool2', g.B, g.H, g.W, g.C, g.ld, g.coff, g.f16, co, y_low.ld, y_low.coff, y_low.f16, k, stride, pad, dil, ptr(w_t).value & 15)
@@ -295,10 +292,7 @@ class FoldChain:
             _lib.get().call('hv_wgrad_fold_now', ctypes.byref(f), stream())
 
 
-FOLD_CHAIN = os.environ.get('HV_FOLD_CHAIN', '1') != '0'      # A/B knob: 0 = every weight gradient folds its slabs in a launch of its own right away
-
-
-_DIAG_SKIP_WGRAD = frozenset(v for v in os.environ.get('HV_DIAG_SKIP_WGRAD', '').split(',') if v)
+FOLD_CHAIN = True      # False (a test's reference): every weight gradient folds its slabs in a launch of its own right away
 
 
 def conv2d_wgrad(x, g, dw, k, stride=1, pad=0, dil=1, in_shift=0, accumulate=False, precision=None, cin=None, cout=None, dbias=None,
@@ -310,12 +304,6 @@ def conv2d_wgrad(x, g, dw, k, stride=1, pad=0, dil=1, in_shift=0, accumulate=Fal
     L = _lib.get()
     d = L.hv_wgrad_desc()
     kh, kw = (k, k) if isinstance(k, int) else k
-    if _DIAG_SKIP_WGRAD:      # timing-only diagnostic (wrong parameter gradients): what a class of weight gradients costs the step
-        ci_, co_ = (x.C if cin is None else cin), (g.C if cout is None else cout)
-        cls = {'k%d' % kh, 'thin' if min(ci_, co_) <= 16 else 'wide', 'head' if co_ <= 4 else '', 'dstem' if (kh == 4 and stride == 2 and ci_ <= 4) else '',
-               'g3thin' if (kh == 3 and min(ci_, co_) <= 16 and co_ > 4) else '', 'dhead' if (kh == 4 and co_ <= 4) else '', 'ghead' if (kh == 3 and co_ <= 4) else ''}
-        if cls & _DIAG_SKIP_WGRAD:
-            return
     d.x = ptr(x.t).value
     d.B, d.H, d.W, d.in_shift = x.B, x.H << in_shift, x.W << in_shift, in_shift
     d.x_ld, d.x_coff, d.Cin = x.ld, x.coff, (x.C if cin is None else cin)
@@ -416,13 +404,10 @@ def weight_prep_backward(table, max_numel, any_sn):
 
 
 # ------------------------------------------------------------------------------------------------ pointwise
-_DIAG_SKIP = os.environ.get('HV_DIAG_SKIP', '')      # timing-only diagnostics (tools/marginal_step.sh): the named passes are not launched, results are wrong
 
 
 def act_backward(dy, y, act, dbias=None, dbias_accumulate=False):
     """In place: dy *= act'(y); dbias (+)= column sums."""
-    if 'act_bwd' in _DIAG_SKIP:
-        return
     L = _lib.get()
     need = L.size('hv_act_backward_workspace_bytes', ctypes.c_longlong(dy.npix), dy.C) if dbias is not None else 0
     b, nb = _ws(need, dy.t.device)
@@ -443,8 +428,6 @@ def head_seed_backward(seed, y, carrier, act, dbias=None, dbias_accumulate=False
 
 def copy_channels(src, dst, mode=0, accumulate=False):
     """dst (+)= resample(src); H,W of dst rule (mode: 0 same, 1 up x2, 2 down x1/2, 3 adjoint of 1, 4 adjoint of 2)."""
-    if 'copy_channels' in _DIAG_SKIP:
-        return
     assert src.C == dst.C
     _lib.get().call('hv_copy_channels', ptr(src.t), src.f16, ptr(dst.t), dst.f16, dst.B, dst.H, dst.W, dst.C, src.ld, src.coff, dst.ld, dst.coff,
                     mode, int(accumulate), stream())
@@ -493,31 +476,18 @@ def sobel(img, out=None):
     return out
 
 
-GAN_LOSS_WS = os.environ.get('HV_GAN_LOSS_WS', '1') != '0'   # A/B knob
-
-
-def gan_loss(z, target_is_real, mode='vanilla', loss=None, loss_weight=1.0, loss_accumulate=False, dz=None, grad_weight=1.0, carrier=None, dbias=None,
-             dbias_accumulate=False):
-    """carrier: Act fp16 [.., 4] -- the logits layer's padded gradient operand, written directly (hv_gan_loss_head), with the layer's bias gradient dbias."""
+def gan_loss(z, target_is_real, mode='vanilla', loss=None, loss_weight=1.0, loss_accumulate=False, dz=None, grad_weight=1.0):
+    """The GAN loss of the logits z and its gradient dz (fp32); the fp16 mode's discriminators take gan_loss_pair."""
     m = {'vanilla': 0, 'lsgan': 1}[mode]
     L = _lib.get()
     n = z.numel()
-    if carrier is not None:
-        assert carrier.f16 and carrier.ld == 4 and carrier.coff == 0 and carrier.npix == n
-        b, nb = _ws(L.size('hv_gan_loss_head_workspace_bytes', ctypes.c_longlong(n)), z.device, slot=2)
-        L.call('hv_gan_loss_head', ptr(z), ctypes.c_longlong(n), int(bool(target_is_real)), m, ctypes.c_float(loss_weight), ptr(loss), int(loss_accumulate),
-               ctypes.c_float(grad_weight), ptr(dz), ptr(carrier.t), ptr(dbias), int(dbias_accumulate), ptr(b), nb, stream())
-        return
-    if n >= 4096 and GAN_LOSS_WS:      # many workgroups + per-stream scratch for their partial sums
+    if n >= 4096:      # many workgroups + per-stream scratch for their partial sums
         b, nb = _ws(L.size('hv_gan_loss_workspace_bytes', ctypes.c_longlong(n)), z.device, slot=2)
         L.call('hv_gan_loss_ws', ptr(z), ctypes.c_longlong(n), int(bool(target_is_real)), m, ctypes.c_float(loss_weight), ptr(loss),
                int(loss_accumulate), ctypes.c_float(grad_weight), ptr(dz), ptr(b), nb, stream())
         return
     L.call('hv_gan_loss', ptr(z), ctypes.c_longlong(n), int(bool(target_is_real)), m, ctypes.c_float(loss_weight),
            ptr(loss), int(loss_accumulate), ctypes.c_float(grad_weight), ptr(dz), stream())
-
-
-GAN_LOSS_PAIR = os.environ.get('HV_GAN_LOSS_PAIR', '1') != '0'   # A/B knob
 
 
 _TICKETS = {}
@@ -535,9 +505,7 @@ def _ticket(device):
 def gan_loss_pair(z0, real0, loss0, carrier0, z1=None, real1=True, loss1=None, carrier1=None, mode='vanilla', loss_weight=1.0, loss_accumulate=False,
                   grad_weight=1.0, dbias=None, dbias_accumulate=False):
     """The PatchGAN loss head of one or two logit ranges (the fake | real halves of a batched discriminator pass) in ONE launch (hv_gan_loss_head_pair: the
-    last workgroup folds the block sums).  Returns False when switched off (the caller then takes gan_loss per range)."""
-    if not GAN_LOSS_PAIR:
-        return False
+    last workgroup folds the block sums)."""
     n0, n1 = z0.numel(), (0 if z1 is None else z1.numel())
     for c, n in ((carrier0, n0), (carrier1, n1)):
         assert c is None or (c.f16 and c.ld == 4 and c.coff == 0 and c.npix == n)
@@ -547,7 +515,6 @@ def gan_loss_pair(z0, real0, loss0, carrier0, z1=None, real1=True, loss1=None, c
            int(bool(real1)), ptr(loss1), None if carrier1 is None else ptr(carrier1.t), {'vanilla': 0, 'lsgan': 1}[mode], ctypes.c_float(loss_weight),
            int(loss_accumulate), ctypes.c_float(grad_weight), ptr(dbias), int(dbias_accumulate), ptr(b), nb,
            ptr(_ticket(z0.device)), stream())
-    return True
 
 
 def adam_step(table, max_numel, lr_dev, beta1, beta2, eps, step_dev, guard_flat=None, grad_mul=1.0):

@@ -866,7 +866,7 @@ def test_conv_heads_data_gradient_taps_as_one_mfma(case):
     wb = wb.to(dev())
     y = ops.Act(torch.full((B, H, W, Cout), 0.25, device=dev(), dtype=torch.float16))
     ops.conv2d(ga, wb, y, 3, 1, 1, 1, transposed=True, precision='fp16', w_h=wb.half(), mul=(ma, 'elu'), accumulate=1, cin=4)
-    assert lib.get().size('hv_last_kernel_path') in (9, 14)      # (14: conv_px_kernel takes the shape first unless HV_CONV_PX masks it)
+    assert lib.get().size('hv_last_kernel_path') in (9, 14)      # (14: conv_px_kernel takes the shape first)
     torch.cuda.synchronize()
     ref = F.conv_transpose2d(gy[:, :live].half().float(), w.half().float(), None, stride=1, padding=1)
     mh = m.half().float()

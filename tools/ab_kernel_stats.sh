@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel averages of the default bench command under rocprofv3 for several settings of ONE environment knob (same box, one call):
-#   tools/ab_kernel_stats.sh HV_CA_GRAM_NBY "2 4" "ca_gram_backward|ca_fuse_adj|ca_coef"
+#   tools/ab_kernel_stats.sh HV_LF_PERSIST "0 1" "conv_lf"
 knob=$1; vals=$2; pat=$3
 export TMPDIR=/tmp
 out=gpurun_out/abk_$knob

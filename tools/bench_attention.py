@@ -1,6 +1,6 @@
 """The contextual-attention block alone (forward + backward, fp16 mode) for rocprofv3 --kernel-trace --stats: per-kernel durations without the rest of the step.
 
-    python tools/bench_attention.py [B=16] [H=64] [iters=20]        (HV_CA_GRAM=0: the patch-table route)
+    python tools/bench_attention.py [B=16] [H=64] [iters=20]        (engine.CA_GRAM = False: the patch-table route)
 """
 import os
 import sys

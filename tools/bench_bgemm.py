@@ -25,4 +25,4 @@ g.replay(); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / iters * 1e3
-print('bgemm %dx%dx%d x%d DMA=%s VAR=%s: %.1f us  %.0f TF' % (M, N, K, batch, os.environ.get('HV_BGEMM_DMA', '1'), os.environ.get('HV_BGEMM_VAR', '0'), us, 2.0 * M * N * K * batch / us / 1e6))
+print('bgemm %dx%dx%d x%d: %.1f us  %.0f TF' % (M, N, K, batch, us, 2.0 * M * N * K * batch / us / 1e6))

@@ -18,12 +18,9 @@ def run_case(case):
     from hvgan import synth
     from hvgan.models.pix2pix_model import Pix2PixModel
     torch.manual_seed(0)
-    if case == 'phase_a_serial':
-        os.environ['HV_CONCURRENT_D'] = '0'
-    if case == 'phase_a_dstreams':
-        pass
-    if case == 'phase_a_wgrad':
-        os.environ['HV_CONCURRENT_D'] = '0'
+    if case in ('phase_a_serial', 'phase_a_wgrad'):
+        from hvgan import engine
+        engine.SERIAL = True
     model = Pix2PixModel(make_opt())
     model.use_graph = False
     model.set_input(synth.make_batch(2, 256, seed=1))
