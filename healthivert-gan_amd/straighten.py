@@ -1,0 +1,309 @@
+"""Spine straightening and per-vertebra volume extraction on the device (stage 1 of the reference workflow).
+
+The reference runs this stage on the CPU, one patient at a time:
+  straighten/location_json_local.py:14-16,33-45          the centroid list (mean voxel index per label, two small-label drops)
+  straighten/straighten_mask_3d.py:463-563 process_mask3d curve extension, bone window, straightening along the spine curve
+                                                          (straighten/curve.py, Interpolator with get_local_basis), the split cleanup
+                                                          and the per-vertebra crops (mask_2d and the file I/O excepted)
+Here the two volumes stay on the device: one stats pass (CT min / max, per-label counts and index sums, the label check), one small read
+back of that record, the curve math on the host (a few hundred points, numpy), then one sampling launch and one crop launch for every
+requested vertebra (csrc/straighten.hip).
+
+  vertebra_centroids(label) -> [{"label", "X", "Y", "Z"}, ...]             the JSON list location_json_local.py writes
+  straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64)) -> {vert_id: (ct_vol, label_vol)}
+
+Volumes are [X, Y, Z] device tensors as nibabel hands them over (any strides; a Fortran-ordered array passes as it lies).  The CT may be
+int16, float32 or float64 and is windowed in double for every dtype.  Deviation: the reference reads CT files over 500 MB as float32
+(straighten_mask_3d.py:474-477); here the CT is always widened to double, which moves the windowed values of such files by less than 1e-4.
+
+The host functions below restate the reference's curve code (citing the lines they restate); they are numpy only and never build the
+N x 128 x 128 x 3 sample grid: the kernel computes each sample's coordinate from the knot and the frame of its plane.
+"""
+import ctypes
+import warnings
+
+import numpy as np
+import torch
+
+from . import lib as _lib
+
+PLANE = (128, 128)            # interpolate_along(vol, shape) (straighten_mask_3d.py:494)
+WINDOW = (-300.0, 800.0)      # window(ct_data, -300, 800) (:491)
+EXTENSION = 20                # extend_curve(coords, 20, (0, 0, 0), label.shape) (:487)
+DROP_MAX, DROP_MIN = 8000, 6000   # location_json_local.py:40-43
+
+_DT = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4, torch.float64: 5}
+_CT_DT = (torch.int16, torch.float32, torch.float64)
+_HDR, _CNT, _SUM, _PRES = 4, 4, 260, 1028   # word offsets of the stats record (include/hvgan.h)
+
+
+# ------------------------------------------------------------------------------------------------ host curve math (numpy)
+def interp_linear(x, y, x_new):
+    """scipy.interpolate.interp1d(x, y, axis=0) (linear; extrapolating with the end segments) at x_new: x sorted stably, the segment
+    found by searchsorted and clipped to [1, len - 1], y = slope * (x_new - x_lo) + y_lo with slope = (y_hi - y_lo) / (x_hi - x_lo)."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    order = np.argsort(x, kind='mergesort')
+    x, y = x[order], y[order]
+    x_new = np.atleast_1d(np.asarray(x_new, dtype=np.float64))
+    hi = np.searchsorted(x, x_new).clip(1, len(x) - 1).astype(int)
+    lo = hi - 1
+    slope = (y[hi] - y[lo]) / (x[hi] - x[lo])[:, None]
+    return slope * (x_new - x[lo])[:, None] + y[lo]
+
+
+def extend_curve(curve, extension_length=EXTENSION, min_bounds=(0, 0, 0), max_bounds=None):
+    """straighten_mask_3d.py:96-121: one point more at each end, `extension_length` along the end segment, each axis clamped to
+    [min_bounds[i], max_bounds[i]] (the reference passes the volume shape, so the upper bound is shape_i, not shape_i - 1)."""
+    curve = np.asarray(curve, dtype=np.float64)
+    out = [None, None]
+    for k, (p, q) in enumerate(((curve[0], curve[1]), (curve[-1], curve[-2]))):
+        d = p - q
+        pt = p + d / np.linalg.norm(d) * extension_length
+        out[k] = np.array([max(min_bounds[i], min(max_bounds[i], pt[i])) for i in range(3)])
+    return np.vstack([out[0], curve, out[1]])
+
+
+def cumulative_length(curve):
+    """curve.py:203-206: 0, then the running sum of the segment lengths."""
+    return np.insert(np.cumsum(np.linalg.norm(np.diff(curve, axis=0), axis=1)), 0, 0)
+
+
+def local_basis(grad):
+    """get_local_basis (straighten_mask_3d.py:155-170): columns = unit tangent, a unit vector in the sagittal (axis 0, axis 2) plane
+    oriented by the sign of a 2 x 2 determinant, and their cross product.  -> [N][3][3], basis[n][:, j] = vector j."""
+    g = grad / np.linalg.norm(grad, axis=1, keepdims=True)
+    sag = g[:, [0, 2]]
+    second = sag[:, ::-1] * [1, -1]
+    dets = np.linalg.det(np.stack([sag, second], -1))
+    second = second * dets[:, None]
+    second = second / np.linalg.norm(second, axis=1, keepdims=True)
+    second = np.insert(second, 1, np.zeros_like(second[:, 0]), axis=1)
+    return np.stack([g, second, np.cross(second, g)], -1)
+
+
+def curve_frame(curve, step=1):
+    """Interpolator(curve, step, get_local_basis=get_local_basis) (curve.py:26-52 with get_derivatives :209-221): knots at
+    arange(0, L, step) of the cumulative length, np.gradient of the points interpolated the same way, the frame of local_basis.
+    -> knots [N][3], basis [N][3][3]."""
+    curve = np.asarray(curve, dtype=np.float64)
+    lengths = cumulative_length(curve)
+    xs = np.arange(0, lengths[-1], step)
+    knots = interp_linear(lengths, curve, xs)
+    grad = interp_linear(lengths, np.gradient(curve, axis=0), xs)
+    return knots, local_basis(grad)
+
+
+def global_to_local(point, knots, basis, shape=PLANE):
+    """Interpolator.global_to_local (curve.py:104-150,223-239) for one point: its offsets from every knot in that knot's frame, plus the
+    plane centres (cumulative length, shape / 2); the plane is chosen where the distance to the plane changes sign closest to the nearest
+    knot, and the coordinates are interpolated linearly to distance 0 over up to four planes around it."""
+    p = np.asarray(point, dtype=np.float64) - knots
+    to_origin = np.linalg.norm(p, axis=-1)
+    p = np.einsum('nji,nj->ni', basis, p)
+    to_plane = p[:, 0]
+    centers = np.zeros_like(knots)
+    centers[:, 0] = cumulative_length(knots)
+    centers[:, 1:] = np.broadcast_to(shape, 2) / 2
+    coords = p + centers
+    idx = to_origin.argmin()
+    cand, = np.diff(np.sign(to_plane)).nonzero()
+    if len(cand) != 1:
+        warnings.warn("Couldn't uniquely choose a local basis.")
+    if len(cand) > 0:
+        idx = cand[np.abs(cand - idx).argmin()]
+    slc = slice(max(0, idx - 2), idx + 2)
+    return interp_linear(to_plane[slc], coords[slc], 0.0)[0]
+
+
+def crop_box(center, src_shape, size):
+    """extract_3d_volume (straighten_mask_3d.py:222-247) as index arithmetic: per axis the source range [lo, lo + n) (int() truncation of
+    c -+ d // 2, clipped to the volume) and where it lands in the zero volume of `size` (centred; on the last axis a range longer than the
+    output keeps its first size[2] elements).  -> (lo0, lo1, lo2, n0, n1, n2, start0, start1, start2)."""
+    lo, n, start = [], [], []
+    for i in range(3):
+        c, d = center[i], size[i]
+        a, b = max(0, int(c - d // 2)), min(src_shape[i], int(c + d // 2))
+        m = b - a
+        s = (d - m) // 2
+        if m > d:
+            if i < 2:
+                raise ValueError('crop: source range %d longer than the output axis %d' % (m, d))
+            s, m = 0, d
+        lo.append(a)
+        n.append(max(m, 0))
+        start.append(s)
+    return lo + n + start
+
+
+def centroids_from_counts(counts, sums):
+    """location_json_local.py:33-45 from per-label voxel counts [256] and index sums [256][3] (exact integers): labels in ascending order,
+    the largest dropped below 8000 voxels, the smallest below 6000, centre = sum / count per axis."""
+    labels = [l for l in range(1, 256) if counts[l] > 0]
+    out = []
+    for l in labels:
+        if counts[l] < DROP_MAX and l == max(labels):
+            continue
+        if counts[l] < DROP_MIN and l == min(labels):
+            continue
+        c = [float(np.float64(int(sums[l][a])) / np.float64(int(counts[l]))) for a in range(3)]
+        out.append({'label': int(l), 'X': c[0], 'Y': c[1], 'Z': c[2]})
+    out.sort(key=lambda e: e.get('label', 0))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ device side
+def _dtype_code(t, allowed, what):
+    if t.dtype not in allowed:
+        raise TypeError('%s: dtype %s not supported (%s)' % (what, t.dtype, ', '.join(str(d) for d in allowed)))
+    return _DT[t.dtype]
+
+
+def _check(ct, label):
+    _lib.require_gpu(ct, label)
+    if ct.dim() != 3 or tuple(ct.shape) != tuple(label.shape):
+        raise ValueError('straighten: CT and label must be two [X, Y, Z] volumes of one shape, got %s and %s'
+                         % (tuple(ct.shape), tuple(label.shape)))
+    if ct.device != label.device:
+        raise ValueError('straighten: CT and label on different devices')
+    return _dtype_code(ct, _CT_DT, 'CT'), _dtype_code(label, tuple(_DT), 'label')
+
+
+def _strides(t):
+    return [ctypes.c_longlong(s) for s in t.stride()]
+
+
+class _Stats:
+    def __init__(self, words):
+        w = words.view(np.uint64)
+        kmin, kmax = ~w[0], w[1]
+        self.ct_min = float(self._decode(kmin))
+        self.ct_max = float(self._decode(kmax))
+        self.bad_label = bool(w[2])
+        self.counts = w[_CNT:_CNT + 256].astype(np.int64)
+        self.sums = w[_SUM:_SUM + 768].reshape(256, 3)
+
+    @staticmethod
+    def _decode(k):
+        k = np.uint64(k)
+        u = k ^ np.uint64(1 << 63) if k >> np.uint64(63) else ~k
+        return np.array([u], dtype=np.uint64).view(np.float64)[0]
+
+
+def _stats(ct, label, ctc, lc):
+    L = _lib.get()
+    X, Y, Z = ct.shape
+    nbytes = L.size('hv_straighten_stats_bytes', Y)
+    rec = torch.empty(nbytes // 8, dtype=torch.int64, device=ct.device)
+    L.call('hv_straighten_stats', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z, _lib.ptr(rec),
+           ctypes.c_size_t(nbytes), _lib.stream())
+    head = rec[:_PRES].cpu().numpy()          # the one read back per patient: the curve math runs on the host
+    st = _Stats(head)
+    if st.bad_label:
+        raise ValueError('straighten: the label volume holds values that are not integers in [0, 255]')
+    return st, rec
+
+
+def vertebra_centroids(label):
+    """The centroid list of location_json_local.py for one label volume (device tensor [X, Y, Z], integer values 0..255): labels ascending,
+    the two small-label drops applied, {"label", "X", "Y", "Z"} = mean voxel index along axes 0, 1, 2 (bit-identical to numpy's)."""
+    _lib.require_gpu(label)
+    lc = _dtype_code(label, tuple(_DT), 'label')
+    L = _lib.get()
+    X, Y, Z = label.shape
+    nbytes = L.size('hv_straighten_stats_bytes', Y)
+    rec = torch.empty(nbytes // 8, dtype=torch.int64, device=label.device)
+    zero = [ctypes.c_longlong(0)] * 3
+    L.call('hv_straighten_stats', None, 0, *zero, _lib.ptr(label), lc, *_strides(label), X, Y, Z, _lib.ptr(rec),   # no CT: labels only
+           ctypes.c_size_t(nbytes), _lib.stream())
+    st = _Stats(rec[:_PRES].cpu().numpy())
+    if st.bad_label:
+        raise ValueError('vertebra_centroids: the label volume holds values that are not integers in [0, 255]')
+    return centroids_from_counts(st.counts, st.sums)
+
+
+def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE):
+    """Host part of process_mask3d (straighten_mask_3d.py:485-541) for a centroid list and a volume shape: the extended curve, knots and
+    frame (None, None with one centroid), and per requested vertebra the local centroid and its crop box.  Raises ValueError for a
+    missing id or a degenerate curve (the reference would divide by zero or hit a NameError)."""
+    coords = [[e['X'], e['Y'], e['Z']] for e in centroids if isinstance(e, dict) and 'X' in e]
+    if not coords:
+        raise ValueError('straighten: no centroid')
+    knots = basis = None
+    if len(coords) > 1:
+        curve = np.asarray(coords, dtype=np.float64)
+        if not np.isfinite(curve).all() or (np.linalg.norm(np.diff(curve, axis=0), axis=1) == 0).any():
+            raise ValueError('straighten: degenerate curve (two equal consecutive centroids)')
+        curve = extend_curve(curve, EXTENSION, (0, 0, 0), tuple(shape))
+        if (np.linalg.norm(np.diff(curve, axis=0), axis=1) == 0).any():
+            raise ValueError('straighten: degenerate curve after the extension')
+        knots, basis = curve_frame(curve, 1)
+        if len(knots) == 0 or not (np.isfinite(knots).all() and np.isfinite(basis).all()):
+            raise ValueError('straighten: degenerate curve (no finite frame)')
+        src_shape = (len(knots), plane[1], plane[0])
+    else:
+        src_shape = tuple(shape)
+    boxes, local = [], {}
+    for vid in vertebrae_ids:
+        centroid = None
+        for e in centroids:            # the last entry with that label wins, as in the reference's loop (:516-523)
+            if e.get('label') is None:
+                continue
+            if e['label'] == vid:
+                centroid = (e['X'], e['Y'], e['Z'])
+        if centroid is None:
+            raise ValueError('straighten: vertebra %r has no centroid' % (vid,))
+        if knots is not None:
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')
+                centroid = global_to_local(centroid, knots, basis, plane)
+            if not np.isfinite(centroid).all():
+                raise ValueError('straighten: vertebra %r: no local position on the curve' % (vid,))
+        local[vid] = np.asarray(centroid, dtype=np.float64)
+        boxes.append(crop_box(centroid, src_shape, out_size))
+    return knots, basis, local, boxes
+
+
+def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False):
+    """process_mask3d(ct, label, json, vertebrae_ids, out, out_size) on device tensors (straighten_mask_3d.py:463-563, mask_2d and file I/O
+    excepted).  ct: [X, Y, Z] int16 / float32 / float64; label: [X, Y, Z] integer values 0..255 in any integer or float dtype.  centroids:
+    the list location_json_local.py writes, or None = computed on the device from the same stats pass.
+    -> {vert_id: (ct_vol float64, label_vol uint8)}, each [out_size] on the device, the orientation the reference saves."""
+    ctc, lc = _check(ct, label)
+    L = _lib.get()
+    dev = ct.device
+    X, Y, Z = ct.shape
+    st, rec = _stats(ct, label, ctc, lc)
+    if centroids is None:
+        centroids = centroids_from_counts(st.counts, st.sums)
+    vertebrae_ids = list(vertebrae_ids)
+    knots, basis, local, boxes = plan(centroids, (X, Y, Z), vertebrae_ids, out_size)
+    # window(): the whole volume inside (-300, 800) is returned unchanged (:172-176)
+    win = 0 if (st.ct_max < WINDOW[1] and st.ct_min > WINDOW[0]) else 1
+    wmin, wmax = ctypes.c_double(WINDOW[0]), ctypes.c_double(WINDOW[1])
+    O0, O1, O2 = (int(s) for s in out_size)
+    V = len(vertebrae_ids)
+    ct_out = torch.empty(max(V, 1), O0, O1, O2, dtype=torch.float64, device=dev)
+    lab_out = torch.empty(max(V, 1), O0, O1, O2, dtype=torch.uint8, device=dev)
+    if V:
+        d_boxes = torch.tensor(boxes, dtype=torch.int32).to(dev, non_blocking=False)
+        if knots is not None:
+            N, PA, PB = len(knots), PLANE[1], PLANE[0]
+            d_knots = torch.from_numpy(np.ascontiguousarray(knots)).to(dev)
+            d_basis = torch.from_numpy(np.ascontiguousarray(basis)).to(dev)
+            sct = torch.empty(N, PA, PB, dtype=torch.float64, device=dev)
+            slab = torch.empty(N, PA, PB, dtype=torch.uint8, device=dev)
+            pbytes = L.size('hv_straighten_presence_bytes', PA)
+            pres = torch.empty(pbytes // 8, dtype=torch.int64, device=dev)
+            L.call('hv_straighten_sample', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z,
+                   _lib.ptr(d_knots), _lib.ptr(d_basis), N, PA, PB, win, wmin, wmax, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres),
+                   ctypes.c_size_t(pbytes), _lib.stream())
+            L.call('hv_straighten_crop', _lib.ptr(sct), 5, *_strides(sct), _lib.ptr(slab), 0, *_strides(slab), PA, 0, wmin, wmax,
+                   _lib.ptr(pres), _lib.ptr(d_boxes), V, O0, O1, O2, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
+        else:   # one centroid: the windowed raw CT and the raw label are cropped at the raw position (:499-502)
+            L.call('hv_straighten_crop', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), Y, win, wmin, wmax,
+                   _lib.ptr(rec[_PRES:]), _lib.ptr(d_boxes), V, O0, O1, O2, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
+    out = {vid: (ct_out[i], lab_out[i]) for i, vid in enumerate(vertebrae_ids)}
+    if return_plan:
+        return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win)}
+    return out

@@ -183,3 +183,54 @@ def make_spine_volume(seed, H=96, W=56, Z=10, first_id=10, n_vert=5, pitch=18):
             z, r, c = int(rng.randint(1, Z - 1)), top + 15, int(rng.randint(0, W - 4))
             label[r:r + 2, c:c + 3, z] = first_id + v
     return ct, label, cam
+
+
+def make_spine_patient(seed=0, shape=(48, 64, 96), n_vert=5, first_id=16, radius=(8, 7, 4), end_radius=(5, 5, 3), margin=12,
+                       curve=(3.0, 6.0), window_inside=False, process=True):
+    """Synthetic patient for the straightening stage: an int16 HU-like CT and a uint8 label volume, [X, Y, Z] like
+    the reference's NIfTI arrays, the spine running along axis 2 on a curve that bends along axes 0 and 1.  Vertebrae are ellipsoids of
+    `radius` (the two end ones of `end_radius`, small enough for location_json_local.py's two drops when the end radii are small), ids
+    first_id, first_id + 1, ... from z = margin to Z - 1 - margin; each has a posterior process along +axis 1 behind a 2-voxel gap, which
+    the split cleanup removes.  CT: air -1000 outside an elliptic body, soft tissue around 40, bone 250 at a vertebra's centre rising to
+    ~1150 at its surface (so the bone window clips); window_inside: the CT clipped to [-290, 790] (window() then returns it unchanged).
+    Built box by box, so a 512 x 512 x 300 patient costs only the two volumes."""
+    rng = np.random.RandomState(seed)
+    X, Y, Z = shape
+    ph0, ph1 = rng.uniform(0, np.pi, 2)
+
+    def centre(z):
+        t = z / max(Z - 1, 1)
+        return (X / 2 + curve[0] * np.sin(np.pi * t + ph0), Y / 2 - Y / 10 + curve[1] * np.sin(np.pi * t * 1.3 + ph1))
+
+    xs, ys = np.arange(X)[:, None], np.arange(Y)[None, :]
+    body = ((xs - X / 2) / (0.48 * X)) ** 2 + ((ys - Y / 2) / (0.45 * Y)) ** 2 <= 1.0
+    tissue = np.round(40 + 12 * np.sin(xs / 5.0) * np.cos(ys / 7.0)).astype(np.int16)
+    plane = np.where(body, tissue, np.int16(-1000)).astype(np.int16)
+    ct = np.empty((X, Y, Z), dtype=np.int16)
+    ct[...] = plane[:, :, None]
+    label = np.zeros((X, Y, Z), dtype=np.uint8)
+    zc = np.linspace(margin, Z - 1 - margin, n_vert)
+    for k in range(n_vert):
+        rx, ry, rz = end_radius if k in (0, n_vert - 1) else radius
+        cz = zc[k] + rng.uniform(-0.5, 0.5)
+        cx, cy = centre(cz)
+        x0, x1 = max(0, int(cx - rx) - 1), min(X, int(cx + rx) + 2)
+        y0, y1 = max(0, int(cy - ry) - 1), min(Y, int(cy + ry) + 2)
+        z0, z1 = max(0, int(cz - rz) - 1), min(Z, int(cz + rz) + 2)
+        gx, gy, gz = np.meshgrid(np.arange(x0, x1), np.arange(y0, y1), np.arange(z0, z1), indexing='ij')
+        r2 = ((gx - cx) / rx) ** 2 + ((gy - cy) / ry) ** 2 + ((gz - cz) / rz) ** 2
+        inside = r2 <= 1.0
+        sub = label[x0:x1, y0:y1, z0:z1]
+        sub[inside] = first_id + k
+        ctsub = ct[x0:x1, y0:y1, z0:z1]
+        ctsub[inside] = np.round(250 + 900 * r2[inside]).astype(np.int16)
+        if process:
+            py0, py1 = int(cy + ry) + 3, min(Y, int(cy + ry) + 3 + max(2, ry // 2))
+            px0, px1 = max(0, int(cx) - 1), min(X, int(cx) + 2)
+            pz0, pz1 = max(0, int(cz) - 1), min(Z, int(cz) + 2)
+            if py1 > py0:
+                label[px0:px1, py0:py1, pz0:pz1] = first_id + k
+                ct[px0:px1, py0:py1, pz0:pz1] = 900
+    if window_inside:
+        np.clip(ct, -290, 790, out=ct)
+    return ct, label

@@ -567,6 +567,39 @@ int hv_volume_scan(const double* label, long long HW, int Z, double id0, double 
 int hv_volume_slices(const double* vol, long long HW, int Z, int z0, int S, float* out, void* stream);
 int hv_volume_merge(const float* src, const int* flag, long long HW, int Z, int z0, int S, double* out, void* stream);
 
+/* ---- spine straightening and per-vertebra volume extraction (reference straighten/location_json_local.py:14-16,33-45,
+ * straighten/straighten_mask_3d.py:123-146,172-184,222-247,463-563, straighten/curve.py:54-102) ----
+ * Volumes are [D0][D1][D2] (the NIfTI axes as nibabel hands them over), element (i, j, k) at base[i*s0 + j*s1 + k*s2] (strides in elements,
+ * any order: a Fortran-ordered array passes as it lies).  dtype codes below; the CT may be HV_DT_I16 / F32 / F64, the label any of them.
+ * hv_straighten_stats: one read of each volume into `stats` (hv_straighten_stats_bytes(D1) bytes, zeroed by the call; ct may be NULL: labels
+ *   only), 64-bit words:
+ *   [0] ~key(min CT), [1] key(max CT) with key(v) = the double's bits, sign bit flipped for v >= 0, all bits flipped for v < 0;
+ *   [2] non-zero if a label is not an integer in [0, 255]; [4 + l] voxel count of label l (1..255; label 0 is not counted);
+ *   [260 + 3 l + a] sum of the axis-a index over the voxels of label l; [1028 ...] presence bits of the raw geometry (below).
+ * Presence bits (remove_spine_labels_after_split): for a volume whose height axis has R rows, word l * ceil((R - R/2) / 64) + h / 64, bit h % 64
+ *   is set if label l occurs in row R/2 + h of the centre column (all of axis 0, axis 2 at its centre); hv_straighten_presence_bytes(R) bytes.
+ * hv_straighten_sample: the straight volumes [N][PA][PB] (interpolate_along(vol, (PB, PA)), 128 x 128 in the reference): sample (n, a, b) at
+ *   knots[n] + basis[n][:,1] (b - PB/2) + basis[n][:,2] (a - PA/2) (knots [N][3], basis [N][3][3] row-major, fp64), trilinear on the CT
+ *   (windowed when `window`: 255 (v - win_min) / (win_max - win_min) clipped to [0, 255]), nearest on the label, 0 outside [0, D - 1];
+ *   presence (hv_straighten_presence_bytes(PA) bytes, zeroed by the call) for the straight label.
+ * hv_straighten_crop: extract_3d_volume for V vertebrae in one launch from a source volume (the straight ones: dtype F64 / U8, D1 = PA; or the
+ *   raw ones, windowed when `window`): boxes (device, V x 9 ints) {lo0, lo1, lo2, len0, len1, len2, start0, start1, start2}: output (i, j, k)
+ *   of vertebra v = source (lo + (i, j, k) - start) where 0 <= (i, j, k) - start < len, else 0.  A label voxel in a source row (axis 1) at or
+ *   past its label's cutoff (the first row >= D1/2 whose presence bit is clear) becomes 0.  ct_out [V][O0][O1][O2] fp64, label_out the same
+ *   in uint8.  Labels must have passed hv_straighten_stats (the flag) first. */
+enum { HV_DT_U8 = 0, HV_DT_I16 = 1, HV_DT_I32 = 2, HV_DT_I64 = 3, HV_DT_F32 = 4, HV_DT_F64 = 5 };
+size_t hv_straighten_presence_bytes(int rows);
+size_t hv_straighten_stats_bytes(int D1);
+int hv_straighten_stats(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                        long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, uint64_t* stats, size_t stats_bytes, void* stream);
+int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                         long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis, int N,
+                         int PA, int PB, int window, double win_min, double win_max, double* straight_ct, uint8_t* straight_label,
+                         uint64_t* presence, size_t presence_bytes, void* stream);
+int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                       long long ls0, long long ls1, long long ls2, int D1, int window, double win_min, double win_max, const uint64_t* presence,
+                       const int* boxes, int V, int O0, int O1, int O2, double* ct_out, uint8_t* label_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
