@@ -214,9 +214,11 @@ class GradSync:
 
 
 def broadcast_parameters(modules, src=0, group=None):
-    """Make every rank start from rank `src`'s weights and buffers."""
+    """Make every rank start from rank `src`'s weights and buffers (a module with a built ParamSet is told that its weights changed)."""
     if not GradSync.active():
         return
     for m in modules:
         for t in list(m.parameters()) + list(m.buffers()):
             dist.broadcast(t.data, src=src, group=group)
+        if getattr(m, '_pset', None) is not None:
+            m._pset.weights_changed()

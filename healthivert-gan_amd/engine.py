@@ -73,9 +73,11 @@ class ParamSet:
         for c in self.convs:
             c.owner = self
         self.flat_grad = None
+        # the factor by which flat_grad differs from the true gradient: S (ops.grad_scale) from Pix2PixModel's backward until the bound FusedAdam step, else 1
+        self.grad_factor = 1.0
         self._key = None
-        # which weights the prepared tables belong to: `version` counts the changes of the parameters that this code knows of (optimiser steps, state-dict
-        # loads, new storage), `prepared` = (version, table set) of the last prep launch.  prep(only_if_stale=True) skips the launch when both still match --
+        # which weights the prepared tables belong to: `version` counts the changes of the parameters that this code knows of (weights_changed(), new
+        # storage), `prepared` = (version, table set) of the last prep launch.  prep(only_if_stale=True) skips the launch when both still match --
         # the discriminators' tables written for the generator's part of step t are the ones the discriminator update of step t + 1 reads
         self.version = 0
         self.prepared = None
@@ -140,6 +142,7 @@ class ParamSet:
             self.flat_grad.zero_()
         else:
             self.flat_grad = torch.zeros(n, dtype=torch.float32, device=device)
+        self.grad_factor = 1.0
         off = 0
         for p in ps:
             p.grad = self.flat_grad[off:off + p.numel()].view_as(p)
@@ -156,7 +159,8 @@ class ParamSet:
             self.t_bwd[acc].update(rows, key, device)
 
     def attach_grads(self):
-        """Re-point .grad at the flat buffer (optimizer.zero_grad(set_to_none=True) drops the views)."""
+        """Re-point .grad at the flat buffer (optimizer.zero_grad(set_to_none=True) drops the views).  Ends every explicit backward: grad_factor 1."""
+        self.grad_factor = 1.0
         off = 0
         for p in self.trainable():
             n = p.numel()
@@ -181,8 +185,8 @@ class ParamSet:
         return rows
 
     def weights_changed(self):
-        """The parameters were written by something other than this ParamSet's own launches (an optimiser step, load_state_dict, user code): the next
-        prep(only_if_stale=True) must run."""
+        """The parameters were written by something other than this ParamSet's own launches: the next prep(only_if_stale=True) must run.  Bound FusedAdam
+        steps, load_state_dict and ddp.broadcast_parameters call it; code that writes `p.data` itself must too (that moves no torch version counter)."""
         self.version += 1
 
     def prep(self, device, power_iter, only_if_stale=False):

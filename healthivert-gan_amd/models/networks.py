@@ -490,17 +490,17 @@ class _DiscFn(torch.autograd.Function):
             raise RuntimeError("NLayerDiscriminator: the activations of this forward pass were overwritten before its backward ran")
         pg = any(p.requires_grad for p in net.parameters())
         acc = pg and not grads_are_fresh(net)
-        if pg:
-            net.paramset().attach_grads()
-        # fp16 storage mode: scaled seeds (ops.bridge_grad_scale); gradients already in .grad are scaled up first when this call accumulates
-        S = ops.bridge_grad_scale(net.precision)
-        flat = net.paramset().flat_grad if pg else None
+        # fp16 storage mode: scaled seeds (ops.grad_scale), parameter gradients unscaled afterwards; gradients accumulated onto go from grad_factor to S first
+        S = ops.grad_scale(net.precision)
+        pset = net.paramset()
         if acc:
-            ops.scale_inplace(flat, S)
+            ops.scale_inplace(pset.flat_grad, S / pset.grad_factor)
+        if pg:
+            pset.attach_grads()
         dx = net.run_backward(plan, g.contiguous() * S if S != 1.0 else g.contiguous(), need_dx=ctx.need_dx, param_grads=pg, accumulate=acc)
         if pg:
             net.finish()
-            ops.scale_inplace(flat, 1.0 / S)
+            ops.scale_inplace(pset.flat_grad, 1.0 / S)
         plan.pending = None
         if dx is not None:
             dx = dx.clone()

@@ -82,10 +82,10 @@ class Pix2PixModel(BaseModel):
             self.criterionL1 = torch.nn.L1Loss()
             if opt.gan_mode not in ('vanilla', 'lsgan'):
                 raise NotImplementedError("Pix2PixModel HIP path: gan_mode in {vanilla, lsgan}")
-            self.optimizer_G = FusedAdam(self.netG.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
-            self.optimizer_D_1 = FusedAdam(self.netD_1.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
-            self.optimizer_D_2 = FusedAdam(self.netD_2.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
-            self.optimizer_D_3 = FusedAdam(self.netD_3.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999))
+            self.optimizer_G = FusedAdam(self.netG.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999), paramset=self.netG.paramset)
+            self.optimizer_D_1 = FusedAdam(self.netD_1.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999), paramset=self.netD_1.paramset)
+            self.optimizer_D_2 = FusedAdam(self.netD_2.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999), paramset=self.netD_2.paramset)
+            self.optimizer_D_3 = FusedAdam(self.netD_3.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999), paramset=self.netD_3.paramset)
             self.optimizers += [self.optimizer_G, self.optimizer_D_1, self.optimizer_D_2, self.optimizer_D_3]
         self._loss_buf = torch.zeros(32, dtype=torch.float32, device=self.device)
         self._bufs = {}
@@ -99,13 +99,10 @@ class Pix2PixModel(BaseModel):
         if self.isTrain:       # every rank starts from rank 0's initial weights (a no-op without a process group)
             ddp.broadcast_parameters([self.netG, self.netD_1, self.netD_2, self.netD_3])
         import os as _os
-        # gradient (loss) scale of the fp16 storage mode: activation gradients of this model are ~1e-5 .. 1e-7, i.e. subnormal or zero in
-        # fp16.  Every gradient seed of the step is multiplied by a power of two S (exact), the whole backward is linear in its seeds, and the
-        # flat parameter-gradient buffer of each network is multiplied by 1/S (exact) before anything reads it.  S = 1 in the fp32 mode.
-        fp16 = ops.default_precision() == _lib.F16
-        self.grad_scale = float(_os.environ.get('HV_GRAD_SCALE', '8192' if fp16 else '1'))
-        if self.grad_scale <= 0 or (self.grad_scale != 1 and not float(self.grad_scale).is_integer()) or int(self.grad_scale) & (int(self.grad_scale) - 1):
-            raise ValueError('HV_GRAD_SCALE must be a power of two')
+        # gradient scale S (ops.grad_scale; 1 in the fp32 mode): the explicit backward's seeds carry S, so each network's flat gradient holds S times the true
+        # one (ParamSet.grad_factor) until its bound optimiser takes 1/S out in the pass that checks it for inf / nan and skips the update if it finds one
+        # (overflow_steps(); head room in DESIGN.md section 3).  Under data parallelism that pass reads the reduced gradient: every rank decides alike.
+        self.grad_scale = ops.grad_scale(None)
         # fake | real discriminator passes as ONE 2B-sample launch sequence (per-half BatchNorm groups).  Round 2: no gain beside the three-stream overlap;
         # re-measured at the end of round 3 with the pipelined 4x4 kernels (one round of one workgroup per CU at bs 16): 8.18 -> 8.09 ms in three same-box
         # pairs, although it gives up the real-image passes' overlap with the generator forward.  Both the single-process and the data-parallel step take it.
@@ -281,6 +278,7 @@ class Pix2PixModel(BaseModel):
             ops.gan_loss(P.logits, True, mode, loss=lr, dz=dz, grad_weight=0.5 * self.grad_scale)
             net.run_backward(P, dz, need_dx=False, param_grads=True, accumulate=True)
         net.finish()
+        net.paramset().grad_factor = self.grad_scale
         setattr(self, 'loss_D_fake_%d' % k, lf)
         setattr(self, 'loss_D_real_%d' % k, lr)
 
@@ -303,6 +301,7 @@ class Pix2PixModel(BaseModel):
         net.loss_backward(P, False, self.opt.gan_mode, lf, 0.5 * self.grad_scale, need_dx=False, param_grads=True, accumulate=True,
                           dz=self._buf('dz%d' % k, P.logits))
         net.finish()
+        net.paramset().grad_factor = self.grad_scale
         setattr(self, 'loss_D_fake_%d' % k, lf)
 
     def _real_local_early(self):
@@ -390,6 +389,7 @@ class Pix2PixModel(BaseModel):
                self.half_band, 0, stream())
         L.call('hv_shrm_backward', ptr(seeds['d_fake_B_coarse']), None, None, ptr(self._rows), 1, ptr(d_x1), B, H, W, self.half_band, 0, stream())
         self.netG.run_backward(self._gplan, seeds['d_coarse_seg'], seeds['d_fine_seg'], d_x1, d_x2, dp1, dp2)
+        self.netG.paramset().grad_factor = self.grad_scale
 
     # ---------------------------------------------------------------- the step, in three device-only phases
     def _phase_a(self):
@@ -446,7 +446,7 @@ class Pix2PixModel(BaseModel):
             if side is not main and not self._through_ab:
                 side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._opt_step(getattr(self, 'optimizer_D_%d' % k), getattr(self, 'netD_%d' % k))
+                getattr(self, 'optimizer_D_%d' % k).step(sync_lr=False)
                 self._g_step_D(k)
         self._join_d(main)
         self.set_requires_grad([self.netD_1, self.netD_2, self.netD_3], False)
@@ -456,15 +456,7 @@ class Pix2PixModel(BaseModel):
             self.grad_sync.reduce_branch(self.netG.paramset().flat_grad)
 
     def _phase_c(self):
-        self._opt_step(self.optimizer_G, self.netG)
-
-    def _opt_step(self, optimizer, net):
-        """Adam step; in the fp16 storage mode behind the device-side overflow guard: the scaled gradients of a step may overflow an fp16 gradient
-        buffer (inf / nan), which then reach every parameter gradient of the network -- such a step is skipped (weights, moments, step count
-        unchanged; under data parallelism the check runs on the reduced gradient, so every rank takes the same decision) and counted
-        (overflow_steps()).  The scale itself is static (HV_GRAD_SCALE, a power of two; head room in DESIGN.md section 3)."""
-        optimizer.step(sync_lr=False, guard_flat=net.paramset().flat_grad if self.grad_scale != 1.0 else None, grad_mul=1.0 / self.grad_scale)
-        net.paramset().weights_changed()
+        self.optimizer_G.step(sync_lr=False)
 
     def overflow_steps(self):
         """{network: optimiser steps skipped by the overflow guard so far} (a host read)."""

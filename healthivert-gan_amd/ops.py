@@ -52,14 +52,13 @@ def cpad(C):
     return rup(C, 8) if C > 16 else rup(C, 4)
 
 
-def bridge_grad_scale(precision):
-    """Power-of-two gradient scale of the nn.Module autograd bridges (`loss.backward()` on module outputs) in the fp16 storage mode: the
-    activation gradients of these networks are 1e-5 .. 1e-7 -- subnormal or zero in fp16 -- so the incoming seeds are multiplied by S, the
-    backward is linear in them, and the parameter gradients / the input gradient are multiplied by 1/S afterwards (exact).  1 in the fp32 mode."""
-    if precision_id(precision) != F16:
-        return 1.0
-    s = float(os.environ.get('HV_GRAD_SCALE', '8192'))
-    return s if s > 0 else 1.0
+def grad_scale(precision):
+    """HV_GRAD_SCALE: the power-of-two gradient scale S that multiplies every gradient seed (exact; the backward is linear in its seeds), by default 8192
+    in the fp16 storage mode (activation gradients of 1e-5 .. 1e-7 are subnormal or zero in fp16) and 1 in the fp32 mode."""
+    s = float(os.environ.get('HV_GRAD_SCALE', '8192' if precision_id(precision) == F16 else '1'))
+    if s <= 0 or (s != 1 and not s.is_integer()) or int(s) & (int(s) - 1):
+        raise ValueError('HV_GRAD_SCALE must be a power of two')
+    return s
 
 
 def scale_inplace(t, factor):

@@ -10,34 +10,29 @@ from . import ops
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, paramset=None):
+        """paramset: the engine.ParamSet of the network whose parameters these are, or a callable that returns it (networks build theirs lazily).  A
+        bound step takes out the factor the flat gradient carries (grad_factor), behind the overflow guard when it is not 1, and calls weights_changed()."""
         if weight_decay != 0:
             raise NotImplementedError("FusedAdam: weight_decay is not used by the reference and not implemented")
         super().__init__(list(params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._paramset = paramset
         self._table = ops.LayerTable('hv_adam_tensor')
         self._m = self._v = self._step = self._lr = None
         self._lr_host = None
 
     def _ensure(self):
-        ps = [p for g in self.param_groups for p in g['params']]
+        ps = self._ensure_state()
         if any(p.grad is None for p in ps):
             raise RuntimeError("FusedAdam.step(): a parameter has no gradient")
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in ps)
-        dev = ps[0].device
-        if self._m is None or self._m.device != dev:
-            n = sum(p.numel() for p in ps)
-            self._m = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._v = torch.zeros(n, dtype=torch.float32, device=dev)
-            if self._lr is None or self._lr.device != dev:
-                self._lr = None
-                self.sync_lr()
         if key != self._table.key:
             rows, off = [], 0
             for p in ps:
                 n = p.numel()
                 rows.append(dict(p=p.data, g=p.grad, m=self._m[off:off + n], v=self._v[off:off + n], n=n))
                 off += n
-            self._table.update(rows, key, dev)
+            self._table.update(rows, key, ps[0].device)
             self._max = max(p.numel() for p in ps)
         return ps
 
@@ -49,9 +44,11 @@ class FusedAdam(torch.optim.Optimizer):
             n = sum(p.numel() for p in ps)
             self._m = torch.zeros(n, dtype=torch.float32, device=dev)
             self._v = torch.zeros(n, dtype=torch.float32, device=dev)
-            if self._lr is None or self._lr.device != dev:
+            if self._lr is not None and self._lr.device != dev:
                 self._lr = None
-        self.sync_lr()
+        if self._lr is None:
+            self.sync_lr()
+        return ps
 
     def sync_lr(self):
         """Copy the scheduler's learning rate to the device scalar the kernel reads (outside any graph capture)."""
@@ -69,12 +66,18 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None, sync_lr=True, guard_flat=None, grad_mul=1.0):
         """guard_flat: the flat gradient buffer behind the parameters' .grad views (fp16 storage mode): the update is skipped on the device when it
         holds an inf / nan (scaled gradients that overflowed an fp16 gradient buffer); skipped_steps() counts those.  grad_mul: the factor that takes the
-        loss scale out of the gradients (1 / scale), applied by the same pass that checks them."""
+        loss scale out of the gradients (1 / scale), applied by the same pass that checks them.  A bound optimiser takes both from its ParamSet."""
         self._ensure()
         if sync_lr:
             self.sync_lr()
+        pset = self._paramset() if callable(self._paramset) else self._paramset
+        if pset is not None:
+            guard_flat, grad_mul = (pset.flat_grad if pset.grad_factor != 1.0 else None), 1.0 / pset.grad_factor
         g = self.param_groups[0]
         ops.adam_step(self._table, self._max, self._lr, g['betas'][0], g['betas'][1], g['eps'], self._step, guard_flat=guard_flat, grad_mul=grad_mul)
+        if pset is not None:
+            pset.grad_factor = 1.0      # (the guarded pass unscales the flat gradient in place)
+            pset.weights_changed()
 
     def skipped_steps(self):
         """Steps the overflow guard skipped so far (a host read: call it between steps, not inside them)."""

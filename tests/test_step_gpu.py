@@ -488,6 +488,124 @@ def test_guarded_adam_equals_torch_adam_and_ignores_a_poisoned_gradient():
     assert opt.skipped_steps() == 2 and float(opt._step[0].item()) == 2.0
 
 
+@pytest.mark.parametrize('precision', ['fp32', 'fp16'])
+def test_weight_writes_between_public_discriminator_passes_refresh_the_tables(precision, monkeypatch):
+    """backward_D_k lays its weight tables out only when they are stale (prep='if_stale').  An optimiser step and a load_state_dict between two
+    backward_D_1 calls must make the second one lay them out again: losses and flat gradients bit-identical to a run that never skips."""
+    monkeypatch.setenv('HV_PRECISION', precision)
+    monkeypatch.setenv('HV_GRAPH', '0')
+    import hvgan
+    from hvgan import engine, synth
+    from hvgan.models.pix2pix_model import Pix2PixModel
+
+    def run(skip):
+        monkeypatch.setattr(engine, 'PREP_SKIP', skip)
+        torch.manual_seed(41)
+        model = Pix2PixModel(make_opt())
+        other = {k: v.clone() for k, v in model.netD_2.state_dict().items()}
+        model.set_input(synth.make_batch(2, 256, seed=41))
+        model.forward()
+        out = []
+
+        def d1():
+            model.backward_D_1()
+            out.extend([torch.stack([model.loss_D_fake_1, model.loss_D_real_1]).clone(), model.netD_1.paramset().flat_grad.clone()])
+        d1()
+        model.optimizer_D_1.step()
+        d1()
+        model.netD_1.load_state_dict(other)
+        d1()
+        torch.cuda.synchronize()
+        return out
+
+    got, ref = run(True), run(False)
+    for i, (a, b) in enumerate(zip(got, ref)):
+        assert torch.equal(a, b), (precision, i, (a - b).abs().max().item())
+
+
+def test_public_per_method_order_equals_optimize_parameters_in_fp16(monkeypatch):
+    """The reference's public train-step API -- forward(), backward_D_k() + optimizer_D_k.step() for k = 1..3, backward_G() + optimizer_G.step() --
+    in the fp16 mode (scaled gradients in .grad until the bound optimisers step): two steps leave the same weights, BatchNorm statistics and Adam
+    state, bit for bit, as optimize_parameters() from the same seed (the same kernels per network, in the same order)."""
+    monkeypatch.setenv('HV_PRECISION', 'fp16')
+    monkeypatch.setenv('HV_GRAPH', '0')
+    import hvgan
+    from hvgan import synth
+    from hvgan.models.pix2pix_model import Pix2PixModel
+    nets = ('G', 'D_1', 'D_2', 'D_3')
+
+    def run(public):
+        torch.manual_seed(77)
+        model = Pix2PixModel(make_opt())
+        for step in range(2):
+            model.set_input(synth.make_batch(2, 256, seed=70 + step))
+            if not public:
+                model.optimize_parameters()
+                continue
+            model.forward()
+            for k in (1, 2, 3):
+                model.set_requires_grad(getattr(model, 'netD_%d' % k), True)
+                getattr(model, 'optimizer_D_%d' % k).zero_grad()
+                getattr(model, 'backward_D_%d' % k)()
+                getattr(model, 'optimizer_D_%d' % k).step()
+            model.set_requires_grad([model.netD_1, model.netD_2, model.netD_3], False)
+            model.optimizer_G.zero_grad()
+            model.backward_G()
+            model.optimizer_G.step()
+        torch.cuda.synchronize()
+        state = {n + '/' + k: v.detach().clone() for n in nets for k, v in getattr(model, 'net' + n).state_dict().items()}
+        for n in nets:
+            o = getattr(model, 'optimizer_' + n)
+            state.update({n + '/adam_m': o._m.clone(), n + '/adam_v': o._v.clone(), n + '/adam_step': o._step[:3].clone()})
+        return state
+
+    a, b = run(True), run(False)
+    bad = [(k, (a[k].double() - b[k].double()).abs().max().item()) for k in a if not torch.equal(a[k], b[k])]
+    assert not bad, ('%d of %d tensors differ' % (len(bad), len(a)), bad[:8])
+
+
+def test_bridge_backward_then_bound_step_in_fp16(monkeypatch):
+    """fp16 mode, netD_1 after the model's explicit backward (its .grad scaled by S): an nn.Module-bridge loss.backward() that accumulates onto
+    those gradients adds true gradients to true gradients; after a fresh bridge backward the bound optimiser's step sees true gradients (no second
+    unscale) and equals torch.optim.Adam on them."""
+    monkeypatch.setenv('HV_PRECISION', 'fp16')
+    monkeypatch.setenv('HV_GRAPH', '0')
+    import hvgan
+    from hvgan import synth
+    from hvgan.models import networks
+    from hvgan.models.pix2pix_model import Pix2PixModel
+    torch.manual_seed(19)
+    model = Pix2PixModel(make_opt())
+    net, opt = model.netD_1, model.optimizer_D_1
+    ps = net.paramset()
+    crit = networks.GANLoss('vanilla').to(torch.device('cuda:0'))
+    model.set_input(synth.make_batch(2, 256, seed=19))
+    model.forward()
+    model.backward_D_1()
+    S = model.grad_scale
+    assert S == 8192.0 and ps.grad_factor == S
+    g1 = ps.flat_grad / S
+    crit(net(model.fake_B.detach()), False).backward()          # accumulates (no zero_grad since the explicit backward)
+    acc = ps.flat_grad.clone()
+    assert ps.grad_factor == 1.0
+    opt.zero_grad()
+    crit(net(model.fake_B.detach()), False).backward()          # the same pass alone, assigned
+    g2 = ps.flat_grad.clone()
+    tol = 1e-5 * (g1.abs().max() + g2.abs().max()).item()
+    assert (acc - (g1 + g2)).abs().max().item() <= tol, ((acc - (g1 + g2)).abs().max().item(), tol)
+    ps_list = list(net.parameters())
+    ref = [torch.nn.Parameter(p.detach().cpu().clone()) for p in ps_list]
+    for r, p in zip(ref, ps_list):
+        r.grad = p.grad.detach().cpu().clone()
+    ropt = torch.optim.Adam(ref, lr=2e-4, betas=(0.5, 0.999))
+    opt.step()
+    ropt.step()
+    torch.cuda.synchronize()
+    assert ps.grad_factor == 1.0 and opt.skipped_steps() == 0
+    for p, r in zip(ps_list, ref):
+        assert (p.detach().cpu() - r.detach()).abs().max().item() <= 1e-6
+
+
 def test_step_at_512_fp16_mode_matches_live_oracle(monkeypatch):
     """BASELINE config #5's slice size in the benchmarked fp16 mode (the fp32-mode 512^2 test is above): one full train step, B = 2, against the
     CPU oracle on the same weights -- continuous activations within |d| <= 1e-3, the 12 losses within the fp16-mode tolerances."""
