@@ -235,7 +235,7 @@ class ParamSet:
 
 class ConvNode:
     """conv (+bias +activation) between two NHWC views; knows how to run forward and backward."""
-    __slots__ = ('p', 'x', 'y', 'k', 's', 'pad', 'd', 'act', 'shift', 'need_dx', 'transposed', 'use_bias', 'dx_c', 'pool_to', 'split', '_split_ok')
+    __slots__ = ('p', 'x', 'y', 'k', 's', 'pad', 'd', 'act', 'shift', 'need_dx', 'transposed', 'use_bias', 'dx_c', 'pool_to', 'split')
 
     def __init__(self, p, x, y, s=1, pad=0, d=1, act='none', shift=0, need_dx=True, transposed=False, use_bias=True, dx_c=None):
         self.p, self.x, self.y, self.k, self.s, self.pad, self.d = p, x, y, p.k, s, pad, d
@@ -244,53 +244,67 @@ class ConvNode:
         # gradient is then a convolution with fewer output channels (the first dx_c rows of the transposed filter table)
         self.dx_c = dx_c
         # pool_to = (Act low, activation of low's producer): x is a concat buffer whose first dx_c channels are the nearest x2 up-sampling of `low`;
-        # set by the owner of the plan when the pooled data gradient can serve it (conv_backward)
+        # set by the owner of the plan when the pooled data gradient can serve it (dx_call form 'pool_to')
         self.pool_to = None
         # split = (Act low, Act x1): x is the concat [nearest x2 up-sampling of low (p.split_k channels) | x1 (one channel) | padding]; where the
         # filters-in-LDS kernel serves the shape the forward reads `low` with the fused up-sampling and adds x1's taps in its epilogue, so the
         # up-sampled part of x is only materialised for the backward (split_forward() tells)
         self.split = None
-        self._split_ok = None
+
+    def forward_call(self, prec, xn=None, x_raw=None):
+        """The call that runs this node's forward (ops.ConvCall).  Where `split` is set and the dispatch serves that form (the x1 kernel exists for two
+        channel shapes only and follows the HV_CONV_LF knob) it reads [up-sampled low | x1] without the concat; otherwise x -- or, with xn, the
+        normalisation's raw input x_raw, normalised + activated where the kernel stages it (xn's `out` fills x)."""
+        p = self.p
+        kw = dict(bias=p.bias if self.use_bias else None, act=self.act, w_h=p.w_fwd_h, precision=prec, cout=p.cout, wuse=(p, 'use_fwd'))
+        if self.split is not None and p.w_fwd_t2 is not None and ops.precision_id(prec) == ops.F16:
+            low, x1 = self.split
+            if low.f16 and self.y.f16 and low.C == p.split_k:
+                call = ops.ConvCall(low, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, w_t=p.w_fwd_t2, in_shift=1, cin=p.split_k,
+                                    x1=(x1, p.w_fwd, p.split_k, p.taps * p.cin_fwd, p.cin_fwd), **kw)
+                if call.supported():
+                    return call
+        src = self.x if x_raw is None else x_raw
+        return ops.ConvCall(Act(src.t, p.cin_fwd, src.coff), p.w_fwd, self.y, self.k, self.s, self.pad, self.d, w_t=p.w_fwd_t, in_shift=self.shift,
+                            transposed=self.transposed, xn=xn, **kw)
 
     def split_forward(self, prec):
-        """True when the forward reads [up-sampled low | x1] without the concat: asked of the C dispatch (hv_conv2d_supported -- the x1 kernel exists
-        for two channel shapes only and follows the HV_CONV_LF knob), once per node; otherwise the materialised concat is built and read."""
-        p = self.p
-        if self.split is None or p.w_fwd_t2 is None or ops.precision_id(prec) != ops.F16:
-            return False
-        key = (ops.precision_id(prec), p.w_fwd_t2.data_ptr(), self.y.t.data_ptr())
-        if getattr(self, '_split_ok', None) is None or self._split_ok[0] != key:
-            low, x1 = self.split
-            ok = bool(low.f16 and self.y.f16 and low.C == p.split_k) and ops.conv2d_supported(
-                low, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, bias=p.bias if self.use_bias else None, act=self.act, w_h=p.w_fwd_h, w_t=p.w_fwd_t2,
-                in_shift=1, precision=prec, cin=p.split_k, cout=p.cout, x1=(x1, p.w_fwd, p.split_k, p.taps * p.cin_fwd, p.cin_fwd))
-            self._split_ok = (key, ok)
-        return self._split_ok[1]
+        """True when the forward reads [up-sampled low | x1] without the concat; otherwise the materialised concat is built and read."""
+        return bool(self.forward_call(prec).d.x1)
 
-    def forward(self, prec, stats=None, xn=None, probe=False, x_raw=None):
-        """xn: the input is normalised + activated where the kernel stages it (ops.conv2d) -- x_raw is then the normalisation's raw input, read instead
-        of self.x (which xn's `out` fills); probe=True only asks whether that form is served."""
-        p = self.p
-        if self.split_forward(prec):
-            low, x1 = self.split
-            ops.conv2d(low, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, bias=p.bias if self.use_bias else None, act=self.act, w_h=p.w_fwd_h,
-                       w_t=p.w_fwd_t2, in_shift=1, precision=prec, cin=p.split_k, cout=p.cout,
-                       x1=(x1, p.w_fwd, p.split_k, p.taps * p.cin_fwd, p.cin_fwd), wuse=(p, 'use_fwd'))
-            return
-        src = self.x if x_raw is None else x_raw
-        xin = Act(src.t, p.cin_fwd, src.coff)
-        if probe:
-            return ops.conv2d_supported(xin, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, bias=p.bias if self.use_bias else None, act=self.act, w_h=p.w_fwd_h,
-                                        w_t=p.w_fwd_t, in_shift=self.shift, transposed=self.transposed, precision=prec, cout=p.cout, xn=xn)
-        ops.conv2d(xin, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, bias=p.bias if self.use_bias else None, act=self.act, w_h=p.w_fwd_h, w_t=p.w_fwd_t,
-                   in_shift=self.shift, transposed=self.transposed, precision=prec, cout=p.cout, stats=stats, wuse=(p, 'use_fwd'), xn=xn)
+    def forward(self, prec, stats=None, xn=None, x_raw=None):
+        self.forward_call(prec, xn, x_raw).launch(stats)
 
     def stats_parts(self, prec):
         """Partial-sum rows this node's forward kernel writes when handed a statistics buffer (0: that kernel has no such epilogue)."""
+        return self.forward_call(prec).stats_parts()
+
+    def dx_view(self, book, form):
+        """The gradient view the data gradient of `form` (dx_call) writes: that of pool_to's tensor for 'pool_to', else x's (its first dx_c channels)."""
+        a = self.pool_to[0] if form == 'pool_to' else self.x
+        g = book.twin(a)
+        C = a.C if form == 'pool_to' else self.p.cin_fwd
+        return Act(g.t, C if form == 'src' else self.dx_c or C, g.coff)
+
+    def dx_call(self, book, prec, form, dst, accumulate, mul_x=None, bn=None):
+        """The call that writes this node's data gradient into the gradient view dst (ops.ConvCall) in one of conv_backward's forms: 'src' (transposed
+        node: plain convolution), 'pool_to' (2x2-pooled into pool_to's gradient, times act' of it), 'pool' (fused up-sampling: 2x2-pooled into x's),
+        'full' (fused up-sampling: full resolution, the caller adds the adjoint copy) or 'plain'.  mul_x ('pool', 'plain'): times act'(x); bn: see
+        conv_backward.  accumulate: the caller's book.mark(dst), or book.accumulates(dst) when it asks ahead of the write."""
         p = self.p
-        xin = Act(self.x.t, p.cin_fwd, self.x.coff)
-        return ops.conv2d_stats_parts(xin, p.w_fwd, self.y, self.k, self.s, self.pad, self.d, bias=p.bias if self.use_bias else None, act=self.act,
-                                      w_h=p.w_fwd_h, w_t=p.w_fwd_t, in_shift=self.shift, transposed=self.transposed, precision=prec, cout=p.cout)
+        gy = book.twin(self.y)
+        mul = None
+        if form == 'pool_to' and self.pool_to[1] != 'none':
+            mul = (Act(self.pool_to[0].t, dst.C, self.pool_to[0].coff), self.pool_to[1])
+        elif form in ('pool', 'plain') and mul_x:
+            mul = (Act(self.x.t, p.cin_fwd, self.x.coff), mul_x)
+        return ops.ConvCall(Act(gy.t, p.coutP, gy.coff), p.w_bwd, dst, self.k, self.s, self.pad, self.d, transposed=form != 'src', pool2=form in ('pool', 'pool_to'),
+                            accumulate=int(accumulate), precision=prec, w_h=p.w_bwd_h, w_t=p.w_bwd_t, mul=mul, bn=bn, wuse=(p, 'use_bwd'))
+
+    def pooled(self, book, prec, form='pool', mul_x=None):
+        """Can the data gradient leave 2x2-pooled in `form` ('pool' or 'pool_to')?  Asked of the call conv_backward would launch."""
+        dst = self.dx_view(book, form)
+        return self.dx_call(book, prec, form, dst, book.accumulates(dst), mul_x=mul_x).supported()
 
 
 # streams on which weight gradients stay in line instead of forking to a side stream: the per-discriminator streams of
@@ -369,11 +383,14 @@ class GradBook:
     def reset(self):
         self.written.clear()
 
+    def accumulates(self, a):
+        """-> accumulate flag of the next write into the gradient of view `a` (mark() records that write)."""
+        return (id(a.t), a.coff, a.C) in self.written
+
     def mark(self, a):
         """-> accumulate flag for a write into the gradient of view `a`."""
-        key = (id(a.t), a.coff, a.C)
-        acc = key in self.written
-        self.written.add(key)
+        acc = self.accumulates(a)
+        self.written.add((id(a.t), a.coff, a.C))
         return acc
 
 
@@ -398,7 +415,7 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
     mul_x: activation name of the layer that produced node.x -- the data gradient is multiplied by act'(node.x) in the conv
     epilogue, so that layer's backward starts `premultiplied` (conv_backward_chain).
     bn: (Act raw input of the batch normalisation that produced node.x, its stats, groups, partials) -- the normalisation's backward sums leave
-    this data gradient's epilogue (ops.conv2d bn=; the caller asked conv2d_bstats_parts first)."""
+    this data gradient's epilogue (ops.ConvCall bn=; the caller asked node.dx_call(...).bstats_parts() first)."""
     p = node.p
     # the batch-norm sums ride in the plain data gradient only: a caller that set them up for a transposed / pooled / shifted node would skip its reduction
     # pass and read partials nobody wrote
@@ -423,34 +440,27 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
             # (in line: per-layer forks to a side stream lost their A/B twice -- 8.25 -> 8.15 ms at the end of round 3, 7.36 -> 7.6-7.8 ms in round 4 -- and are gone;
             # the refinement generator's weight gradients go to a side stream as ONE block, see defer_wgrad)
             _wgrad(node, p, xin, gfull, wgrad_accumulate, prec, dbias=p.bias.grad if fuse_dbias else None, dbias_accumulate=dbias_accumulate)
-    if node.need_dx and node.transposed:
-        gx = book.twin(node.x)
-        gx = Act(gx.t, p.cin_fwd, gx.coff)
-        ops.conv2d(gfull, p.w_bwd, gx, node.k, node.s, node.pad, node.d, transposed=False, accumulate=int(book.mark(gx)), precision=prec, w_h=p.w_bwd_h, w_t=p.w_bwd_t, wuse=(p, 'use_bwd'))
-    elif node.need_dx:
-        gx = book.twin(node.x)
-        gx = Act(gx.t, node.dx_c or p.cin_fwd, gx.coff)
-        if node.pool_to is not None:
-            # node.x is a concat buffer whose first channels are the nearest x2 up-sampling of pool_to[0]: that part of the data gradient is written
-            # 2x2-pooled straight into the small tensor's gradient, times act' of the small tensor (the caller runs its producer premultiplied)
-            low, low_act = node.pool_to
-            gl = book.twin(low)
-            gl = Act(gl.t, node.dx_c or low.C, gl.coff)
-            ops.conv2d(gfull, p.w_bwd, gl, node.k, node.s, node.pad, node.d, transposed=True, pool2=True, accumulate=int(book.mark(gl)), precision=prec,
-                       w_h=p.w_bwd_h, w_t=p.w_bwd_t, mul=(Act(low.t, gl.C, low.coff), low_act) if low_act != 'none' else None, wuse=(p, 'use_bwd'))
-        elif node.shift and _pool2_node_ok(node, gfull, gx, prec):
-            # fused up-sampling in the forward: the data gradient leaves 2x2 sum-pooled from the conv's own epilogue (no full-resolution gradient in
-            # memory, no hv_copy_channels mode 3 pass), times act'(node.x) when the chain asks for it
-            ops.conv2d(gfull, p.w_bwd, gx, node.k, node.s, node.pad, node.d, transposed=True, pool2=True, accumulate=int(book.mark(gx)), precision=prec,
-                       w_h=p.w_bwd_h, w_t=p.w_bwd_t, mul=(Act(node.x.t, p.cin_fwd, node.x.coff), mul_x) if mul_x else None, wuse=(p, 'use_bwd'))
-        elif node.shift:
-            assert not mul_x
-            full = tmp_full() if callable(tmp_full) else tmp_full      # (the full-resolution buffer is only built where this fallback runs)
-            ops.conv2d(gfull, p.w_bwd, full, node.k, node.s, node.pad, node.d, transposed=True, precision=prec, w_h=p.w_bwd_h, w_t=p.w_bwd_t, wuse=(p, 'use_bwd'))
-            ops.copy_channels(full, gx, mode=3, accumulate=book.mark(gx))
-        else:
-            ops.conv2d(gfull, p.w_bwd, gx, node.k, node.s, node.pad, node.d, transposed=True, accumulate=int(book.mark(gx)), w_h=p.w_bwd_h, w_t=p.w_bwd_t,
-                       precision=prec, mul=(Act(node.x.t, p.cin_fwd, node.x.coff), mul_x) if mul_x else None, wuse=(p, 'use_bwd'), bn=bn)
+    if not node.need_dx:
+        return
+    # (pool_to / fused up-sampling: the gradient of the up-sampled tensor leaves 2x2 sum-pooled from the conv's own epilogue where the dispatch serves it --
+    # no full-resolution gradient in memory, no hv_copy_channels mode 3 pass; the owner of pool_to runs its producer premultiplied)
+    if node.transposed:
+        form = 'src'
+    elif node.pool_to is not None:
+        form = 'pool_to'
+    elif node.shift:
+        form = 'pool' if node.pooled(book, prec, 'pool', mul_x) else 'full'
+    else:
+        form = 'plain'
+    if form == 'full':
+        assert not mul_x
+        full = tmp_full() if callable(tmp_full) else tmp_full      # (the full-resolution buffer is only built where this fallback runs)
+        node.dx_call(book, prec, 'full', full, False).launch()
+        gx = node.dx_view(book, 'plain')
+        ops.copy_channels(full, gx, mode=3, accumulate=book.mark(gx))
+    else:
+        dst = node.dx_view(book, form)
+        node.dx_call(book, prec, form, dst, book.mark(dst), mul_x=mul_x, bn=bn).launch()
 
 
 # independent generator branches on two HIP streams / graph branches
@@ -474,23 +484,13 @@ def branch_stream():
     return st
 
 
-def _pool2_node_ok(node, gfull, gx, prec):
-    p = node.p
-    return ops.pool2_ok(gfull, gx, node.k, node.s, node.pad, node.d, prec, p.w_bwd_h, p.w_bwd_t, w=p.w_bwd)
-
-
-def chain_link(n, nxt, prec=None):
+def chain_link(n, nxt, book, prec):
     """True when n's data gradient can carry act' of nxt (the producer of n.x): see conv_backward_chain.  A node with fused up-sampling links when
     its data gradient can leave pooled (conv_backward)."""
-    if n.shift and nxt is not None and n.need_dx and not n.transposed:
-        p = n.p
-        gy = Act(n.y.t, p.coutP, n.y.coff)
-        if prec is None or not _pool2_node_ok(n, gy, Act(n.x.t, p.cin_fwd, n.x.coff), prec):
-            return False
-    elif n.shift:
+    if not (nxt is not None and n.need_dx and not n.transposed and nxt.act != 'none'
+            and n.x.t is nxt.y.t and n.x.coff == nxt.y.coff and n.p.cin_fwd <= nxt.y.t.shape[-1] - nxt.y.coff):
         return False
-    return bool(nxt is not None and n.need_dx and not n.transposed and nxt.act != 'none'
-                and n.x.t is nxt.y.t and n.x.coff == nxt.y.coff and n.p.cin_fwd <= nxt.y.t.shape[-1] - nxt.y.coff)
+    return not n.shift or n.pooled(book, prec, 'pool', nxt.act)
 
 
 def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=False, stop_before=None):
@@ -499,11 +499,11 @@ def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=Fa
     act'(output of nodes[i+1]) in its conv epilogue, so nodes[i+1] starts from its pre-activation gradient: the in-place
     act-gradient pass (read g, read y, write g) between two convs disappears.
     stop_before: the node that follows nodes[-1] in the chain but is run by the caller later (with
-    premultiplied=chain_link(nodes[-1], stop_before))."""
+    premultiplied=chain_link(nodes[-1], stop_before, book, prec))."""
     pre = premultiplied_first     # every writer of nodes[0]'s output gradient already applied its act'
     for i, n in enumerate(nodes):
         nxt = nodes[i + 1] if i + 1 < len(nodes) else stop_before
-        link = chain_link(n, nxt, prec)
+        link = chain_link(n, nxt, book, prec)
         conv_backward(n, book, prec, premultiplied=pre, mul_x=nxt.act if link else None, tmp_full=(tmp_full or {}).get(id(n)))
         pre = link
 

@@ -6,7 +6,7 @@ the forward/backward are explicit kernel sequences from `engine.py` over NHWC bu
 modules created here are parameter containers only (their own forward is never run).
 """
 import contextlib
-import ctypes
+import os
 
 import torch
 import torch.nn as nn
@@ -16,7 +16,7 @@ from ._backend import engine as E
 from ._backend import lib as _lib
 from ._backend import ops
 ptr, stream = _lib.ptr, _lib.stream
-Act, rup = ops.Act, ops.rup
+Act = ops.Act
 
 _ACTS = ('relu', 'elu', 'lrelu', 'prelu', 'selu', 'tanh', 'sigmoid', 'none')
 
@@ -324,8 +324,7 @@ class Generator(nn.Module):
         self._plans = {}
         self._pset = None
         self._eval_graphs = {}
-        import os as _os
-        self.use_graph = _os.environ.get('HV_GRAPH', '1') != '0'
+        self.use_graph = os.environ.get('HV_GRAPH', '1') != '0'
         self._pset_convs = None
         self._tail_stream = None       # a stream still updating the weights (the data-parallel step's exchange stream)
 
@@ -523,7 +522,7 @@ class Generator(nn.Module):
         E.conv_backward_chain([M[6], M[5], M[4], M[3], M[2], M[1]], book, prec, stop_before=M[0],
                               tmp_full={id(M[5]): lambda: self._tmp_up(P, M[5]), id(M[3]): lambda: self._tmp_up(P, M[3])})
         # a11 (allconv11's output, input of M[1]) also feeds the height head: both writers of its gradient apply elu'(a11)
-        pre11 = E.chain_link(M[1], M[0], prec)
+        pre11 = E.chain_link(M[1], M[0], book, prec)
         ops.gap_fc_sigmoid_backward(d_pred2, P.pred2, P.f_pool, fg.fc_height.weight, book.twin(a['a11']),
                                     fg.fc_height.weight.grad, fg.fc_height.bias.grad, mul=(a['a11'], M[0].act) if pre11 else None)
         # cat11 = [conv10_atrous | pmconv10], both ELU: allconv11's data gradient applies elu' for both producers
@@ -545,7 +544,7 @@ class Generator(nn.Module):
         E.conv_backward_chain(list(reversed(P.f_nodes_conv)), book, prec, premultiplied_first=True)
         if side is not None:
             main.wait_stream(side)
-            E.conv_backward(pm_rev[-1], book, prec, premultiplied=E.chain_link(pm_rev[-2], pm_rev[-1], prec))
+            E.conv_backward(pm_rev[-1], book, prec, premultiplied=E.chain_link(pm_rev[-2], pm_rev[-1], book, prec))
         # coarse_seg enters the fine generator as channel 1 of its input
         d_cs_total = P.d_cs_total
         ops.add_channels(Act(d_coarse_seg.view(B, H, W, 1)), book.twin(P.f_in).slice(1, 1), Act(d_cs_total.view(B, H, W, 1)))
@@ -561,11 +560,10 @@ class Generator(nn.Module):
         # conv19 / conv20 read [up-sampled c14 / c12 | CAM]: where the pooled data gradient serves the shape (fp16 mode) the gradient of the small tensor
         # comes 2x2-pooled and times elu' straight from the conv's epilogue; otherwise full-resolution gradient + adjoint-of-up-sampling pass
         def pooled(node, low):
-            pn = node.p
-            g = E.Act(book.twin(node.y).t, pn.coutP, node.y.coff)
-            ok = ops.pool2_ok(g, E.Act(book.twin(low).t, node.dx_c, low.coff), node.k, node.s, node.pad, node.d, prec, pn.w_bwd_h, pn.w_bwd_t)
-            node.pool_to = (low, 'elu') if ok else None
-            return ok
+            node.pool_to = (low, 'elu')
+            if not node.pooled(book, prec, 'pool_to'):
+                node.pool_to = None
+            return node.pool_to is not None
         p19 = pooled(C[15], a['c14'])
         E.conv_backward_chain([C[17], C[16], C[15]], book, prec, premultiplied_first=True)
         if not p19:
@@ -584,7 +582,7 @@ class Generator(nn.Module):
             book.defer_wgrad = False
             launch_block()
         E.conv_backward_chain([C[11], C[10]], book, prec, premultiplied_first=p20, stop_before=C[9])
-        pre10 = E.chain_link(C[10], C[9], prec)      # c10 feeds conv11 and the height head: both apply elu'(c10)
+        pre10 = E.chain_link(C[10], C[9], book, prec)      # c10 feeds conv11 and the height head: both apply elu'(c10)
         ops.gap_fc_sigmoid_backward(d_pred1, P.pred1, P.c_pool, cg.fc_height.weight, book.twin(a['c10']),
                                     cg.fc_height.weight.grad, cg.fc_height.bias.grad, mul=(a['c10'], C[9].act) if pre10 else None)
         E.conv_backward_chain(list(reversed(C[:10])), book, prec, premultiplied_first=pre10)

@@ -17,8 +17,7 @@ from torch.optim import lr_scheduler
 from ._backend import engine as E
 from ._backend import lib as _lib
 from ._backend import ops
-from ._backend import ops as _ops_
-Act, rup = _ops_.Act, _ops_.rup
+Act, rup = ops.Act, ops.rup
 
 
 class Identity(nn.Module):
@@ -289,7 +288,7 @@ class NLayerDiscriminator(nn.Module):
             self.paramset().prep(x.device, power_iter=False, only_if_stale=(prep == 'if_stale'))
         xin = Act(x.view(B, H, W, 1))
         P.x_in = xin
-        head_xn = None
+        head = None       # the logits layer's call when it normalises its input where it stages it
         for li, ent in enumerate(P.layers):
             L = ent['spec']
             if li == 0:
@@ -297,21 +296,19 @@ class NLayerDiscriminator(nn.Module):
                 ent['node'].forward(prec)
                 continue
             if L['last']:
-                ent['node'].forward(prec, xn=head_xn, x_raw=P.layers[li - 1]['z'] if head_xn is not None else None)
+                (head or ent['node'].forward_call(prec)).launch()
                 break
             nm = self.model[L['norm']]
             # the layer below the logits: its normalisation + LeakyReLU is applied by the logits layer's kernel where it stages its input (hv_conv_desc.xn_*; that
             # kernel also stores the normalised map the backward reads) -- the normalisation call below then only finalises the statistics.  Asked of the C
-            # dispatch once per plan and mode (HV_HEAD_NORM=0: always the separate pass)
-            head_xn = None
+            # dispatch (HV_HEAD_NORM=0: always the separate pass); the answer is recorded under ('head_xn', ...)
+            head = None
             if HEAD_NORM and P.layers[li + 1]['spec']['last'] and ent['z'].f16:
-                cand = (ent['stats'], nm.weight if self.norm_kind == 'batch' else None, nm.bias if self.norm_kind == 'batch' else None,
-                        groups if self.norm_kind == 'batch' else B, 'lrelu', ent['y'])
-                key = ('head_xn', self.norm_kind, groups, prec)
-                if key not in ent:
-                    ent[key] = bool(P.layers[li + 1]['node'].forward(prec, xn=cand, probe=True, x_raw=ent['z']))
-                if ent[key]:
-                    head_xn = cand
+                xn = (ent['stats'], nm.weight if self.norm_kind == 'batch' else None, nm.bias if self.norm_kind == 'batch' else None,
+                      groups if self.norm_kind == 'batch' else B, 'lrelu', ent['y'])
+                head = P.layers[li + 1]['node'].forward_call(prec, xn=xn, x_raw=ent['z'])
+                ent[('head_xn', self.norm_kind, groups, prec)] = ok = head.supported()
+                head = head if ok else None
             # BatchNorm statistics out of the conv's own epilogue where its kernel has one (the 4x4 stride-2 layers): the normalisation then
             # skips its reduction pass over z
             parts = 0
@@ -321,7 +318,7 @@ class NLayerDiscriminator(nn.Module):
                     ent['partials'] = torch.zeros(max(1, ent['parts']) * ent['p'].cout * 2, dtype=torch.float32, device=x.device)
                 parts = ent['parts']
             ent['node'].forward(prec, stats=ent['partials'] if parts else None)
-            y_out = None if head_xn is not None else ent['y']
+            y_out = None if head is not None else ent['y']
             if self.norm_kind == 'batch':
                 ops.norm_act_forward(ent['z'], y_out, 'batch', training, ent['stats'], nm.weight, nm.bias, nm.running_mean,
                                      nm.running_var, nm.num_batches_tracked, act='lrelu', eps=nm.eps, momentum=_stat_momentum(nm.momentum, stat_order),
@@ -414,7 +411,9 @@ class NLayerDiscriminator(nn.Module):
                 pe = P.layers[li - 1]
                 bp = pe.setdefault('bparts', {})      # by statistics groups: a plan serves the batched fake | real pass (two groups) and a plain pass of the same size
                 if P.groups not in bp:
-                    bp[P.groups] = self._bstats_parts(node, pe, P, book, prec, mul_x)
+                    # (asked of the plain data gradient conv_backward issues; none when it accumulates -- not a whole sum, never the case in this chain)
+                    gx = node.dx_view(book, 'plain')
+                    bp[P.groups] = node.dx_call(book, prec, 'plain', gx, book.accumulates(gx), mul_x=mul_x, bn=(pe['z'], pe['stats'], P.groups, None)).bstats_parts()
                     # (a buffer per group count: captured graphs of both uses keep their own addresses)
                     pe.setdefault('bpartials_by', {})[P.groups] = torch.zeros(max(1, bp[P.groups]) * pe['p'].cout * 2, dtype=torch.float32, device=pe['z'].t.device)
                 if bp[P.groups]:
@@ -429,19 +428,6 @@ class NLayerDiscriminator(nn.Module):
             g = book.twin(P.x_in)
             return g.t.view(B, 1, P.H, P.W)
         return None
-
-    def _bstats_parts(self, node, pe, P, book, prec, mul_x):
-        """Parts of the batch-norm backward sums that node's data gradient (exactly as conv_backward issues it) would write for the normalised layer
-        pe below it; 0 = its kernel has no such epilogue."""
-        p = node.p
-        gy = book.twin(node.y)
-        gfull = Act(gy.t, p.coutP, gy.coff)
-        gx = book.twin(node.x)
-        gx = Act(gx.t, node.dx_c or p.cin_fwd, gx.coff)
-        if (id(gx.t), gx.coff, gx.C) in book.written:       # (an accumulating data gradient is not a whole sum; never the case in this chain)
-            return 0
-        return int(ops.conv2d_bstats_parts(gfull, p.w_bwd, gx, node.k, node.s, node.pad, node.d, transposed=True, accumulate=0, w_h=p.w_bwd_h, w_t=p.w_bwd_t,
-                                           precision=prec, mul=(Act(node.x.t, p.cin_fwd, node.x.coff), mul_x), bn=(pe['z'], pe['stats'], P.groups, None)))
 
     def finish(self):
         for P in self._plans.values():

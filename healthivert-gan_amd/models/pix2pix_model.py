@@ -7,6 +7,7 @@ no autograd tape, no per-sample Python loops, no `.item()` host syncs (the SHRM 
 device), fused multi-tensor Adam.  Losses stay on the device until get_current_losses() converts them.
 """
 import ctypes
+import os
 
 import torch
 
@@ -14,21 +15,13 @@ from ._backend import ddp
 from ._backend import engine
 from ._backend import lib as _lib
 from ._backend import ops
-from ._backend import lib as _lib_
-ptr, stream = _lib_.ptr, _lib_.stream
-from ._backend import optim as _optim_
-FusedAdam = _optim_.FusedAdam
+from ._backend import optim
+ptr, stream = _lib.ptr, _lib.stream
+FusedAdam = optim.FusedAdam
 from . import networks
 from .base_model import BaseModel
 from .edge_operator import Sobel
 from .inpaint_networks import Generator
-
-
-
-
-def _os_environ_graph():
-    import os
-    return os.environ.get('HV_GRAPH', '1') != '0'
 
 
 def diceCoeff(pred, gt, eps=1e-5, activation='sigmoid'):
@@ -94,11 +87,10 @@ class Pix2PixModel(BaseModel):
         self._graphs = None
         self._inline_exchange = False
         self._eager_steps = 0
-        self.use_graph = _os_environ_graph()
+        self.use_graph = os.environ.get('HV_GRAPH', '1') != '0'
         self.grad_sync = ddp.GradSync() if self.isTrain else None
         if self.isTrain:       # every rank starts from rank 0's initial weights (a no-op without a process group)
             ddp.broadcast_parameters([self.netG, self.netD_1, self.netD_2, self.netD_3])
-        import os as _os
         # gradient scale S (ops.grad_scale; 1 in the fp32 mode): the explicit backward's seeds carry S, so each network's flat gradient holds S times the true
         # one (ParamSet.grad_factor) until its bound optimiser takes 1/S out in the pass that checks it for inf / nan and skips the update if it finds one
         # (overflow_steps(); head room in DESIGN.md section 3).  Under data parallelism that pass reads the reduced gradient: every rank decides alike.
@@ -106,7 +98,7 @@ class Pix2PixModel(BaseModel):
         # fake | real discriminator passes as ONE 2B-sample launch sequence (per-half BatchNorm groups).  Round 2: no gain beside the three-stream overlap;
         # re-measured at the end of round 3 with the pipelined 4x4 kernels (one round of one workgroup per CU at bs 16): 8.18 -> 8.09 ms in three same-box
         # pairs, although it gives up the real-image passes' overlap with the generator forward.  Both the single-process and the data-parallel step take it.
-        self.batch_d = _os.environ.get('HV_BATCH_D', '1') != '0'
+        self.batch_d = os.environ.get('HV_BATCH_D', '1') != '0'
         # the three phases are captured as ONE graph (7.81 -> 7.70 ms over four same-box pairs: two graph-launch boundaries less) -- except under the cut
         # data-parallel schedule, which issues its collectives between the graphs
         # data-parallel step schedule (one process per GPU); every collective of the step goes to one communicator on one stream in the order D_1, D_2, D_3, G:
@@ -120,7 +112,7 @@ class Pix2PixModel(BaseModel):
         #       graph's branches (this runtime executes branch-crossing edges poorly: +0.3 ms in a one-rank group where 'captured' costs nothing).
         #   'auto' (default): gloo -> 'graphs'; RCCL -> dp_preflight() runs ALL on the job's first batch, checks that every rank ends with the same
         #       weights, keeps the fastest correct one and puts the weights back (the preflight steps are not training steps).
-        self.dp_schedule = _os.environ.get('HV_DP_SCHEDULE', 'auto')
+        self.dp_schedule = os.environ.get('HV_DP_SCHEDULE', 'auto')
         if self.dp_schedule == 'phases':      # (the twelve-phase schedule of rounds 1-3 is gone; old launch scripts keep working)
             import warnings
             warnings.warn("HV_DP_SCHEDULE=phases is deprecated: taking 'graphs'", DeprecationWarning)
@@ -524,7 +516,6 @@ class Pix2PixModel(BaseModel):
         if not self.grad_sync.active():
             self.dp_schedule = 'graphs'
             return
-        import os
         if os.environ.get('HV_DP_PREFLIGHT', '1') == '0':
             self.dp_schedule = 'captured' if self.grad_sync.capturable() else 'graphs'
             return
@@ -563,7 +554,6 @@ class Pix2PixModel(BaseModel):
         the recorded text.  A rank that never comes back from a collective cannot be recovered in-process: a timer (HV_DP_PREFLIGHT_TIMEOUT_S,
         default 300 s) then ends THIS process with the text on stderr and exit code 3 instead of hanging the launcher (never a re-exec: the
         process has touched the GPU; a retry is a fresh job)."""
-        import os
         import sys
         import threading
         import time
@@ -749,7 +739,6 @@ class Pix2PixModel(BaseModel):
             # the watchdog then aborts the process: seen once in ~20 runs of the one-rank RCCL test, a few ms after the warm-up steps' collectives (weight
             # broadcast, the communicator's id exchange, the cut schedule's means).  The device is idle here: give the watchdog time for three polls so
             # that nothing is left for it to query during the capture.  Once per batch shape.
-            import os
             import time
             time.sleep(float(os.environ.get('HV_DP_CAPTURE_SETTLE_MS', '350')) * 1e-3)
         graphs, pool = [], None

@@ -159,120 +159,134 @@ def conv_out_size(n, k, stride, pad, dil):
     return (n + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
-def conv2d(x, w, y, k, stride=1, pad=0, dil=1, bias=None, act='none', transposed=False, in_shift=0, alpha=1.0,
-           accumulate=0, ch_scale=None, w_bstride=0, ch_scale_bstride=0, precision=None, cin=None, cout=None, w_h=None, mul=None, w_t=None,
-           stats=None, _parts_only=False, pool2=False, x1=None, _supported_only=False, wuse=None, bn=None, _bparts_only=False, xn=None):
-    """y = act(alpha*ch_scale*conv(x, w) + bias)  [* act'(m) with mul = (Act m, activation name): see hv_conv_desc.mul_src].  x,y: Act; w: prepared [CoutF][k*k][CinP] tensor (or [B][...] with
-    w_bstride).  cin/cout default to the view widths (x.C consumed, y.C produced).
-    stats: float tensor of conv2d_stats_parts(...) * Cout * 2 elements that receives the per-channel partial sums of the stored output
-    (hv_conv_desc.stats; feeds norm_act_forward(partials=...)).
-    pool2: y (and mul's tensor) hold the 2x2 sum-pooled output, i.e. half the convolution's own output size (hv_conv_desc.pool2; raises
-    RuntimeError 'unsupported' unless the filters-in-LDS kernel serves the shape: pool2_ok()).
-    xn = (stats [G][2][Cin], gamma or None, beta or None, groups, activation name, Act out or None): x is the RAW input of a normalisation + activation whose
-    statistics norm_act_forward(x, None, ...) left in `stats`; the kernel normalises where it stages x and also stores the normalised map in `out`
-    (hv_conv_desc.xn_*; the PatchGAN logits layer only: ask conv2d_supported first)."""
-    L = _lib.get()
-    d = L.hv_conv_desc()
-    kh, kw = (k, k) if isinstance(k, int) else k
-    d.x = ptr(x.t).value
-    d.B, d.H, d.W = x.B, x.H << in_shift, x.W << in_shift
-    d.in_shift, d.x_ld, d.x_coff, d.Cin = in_shift, x.ld, x.coff, (x.C if cin is None else cin)
-    d.w = ptr(w).value
-    d.w_bstride = w_bstride
-    d.Cout, d.KH, d.KW, d.stride, d.pad, d.dil, d.transposed = (y.C if cout is None else cout), kh, kw, stride, pad, dil, int(transposed)
-    d.bias = None if bias is None else ptr(bias).value
-    d.ch_scale = None if ch_scale is None else ptr(ch_scale).value
-    d.ch_scale_bstride = ch_scale_bstride
-    d.alpha, d.act, d.accumulate = alpha, ACT[act], int(accumulate)
-    d.y = ptr(y.t).value
-    d.Ho, d.Wo, d.y_ld, d.y_coff = (y.H << 1 if pool2 else y.H), (y.W << 1 if pool2 else y.W), y.ld, y.coff
-    d.pool2 = int(bool(pool2))
-    if x1 is not None:      # (Act of ONE channel at the conv's own resolution, full fp32 forward table, its channel index there, row stride, tap stride)
-        xa, wfull, ch, w1_row, w1_tap = x1
-        assert xa.C == 1 and xa.H == d.H and xa.W == d.W
-        d.x1, d.x1_f16, d.x1_ld, d.x1_coff = ptr(xa.t).value, xa.f16, xa.ld, xa.coff
-        d.w1, d.w1_row, d.w1_tap = ptr(wfull).value + 4 * ch, w1_row, w1_tap
-    d.precision = precision_id(precision)
-    d.w_f16 = None if w_h is None else ptr(w_h).value
-    d.w_f16_tiled = None if (w_t is None or w_h is None) else ptr(w_t).value      # w_h in MFMA-fragment order (tile_weights / hv_weight_prep)
-    d.x_f16, d.y_f16 = x.f16, y.f16
-    if mul is not None:
-        m, mact = mul
-        d.mul_src, d.mul_ld, d.mul_coff, d.mul_act, d.mul_f16 = ptr(m.t).value, m.ld, m.coff, ACT[mact], m.f16
-    if bn is not None:      # (Act x_raw, stats [G][2][C], groups, partials or None): batch-norm backward sums out of this data gradient's epilogue (hv_conv_desc.bstats)
-        bx, bstat, bgroups, bpart = bn
-        assert bx.f16 == y.f16 and bx.H == y.H and bx.W == y.W and bx.B == y.B
-        d.bn_x, d.bn_x_ld, d.bn_x_coff = ptr(bx.t).value, bx.ld, bx.coff
-        d.bn_stats, d.bn_groups = ptr(bstat).value, int(bgroups)
-        if bpart is not None:
-            d.bstats = ptr(bpart).value
-    if xn is not None:
-        nstat, ngam, nbet, ngroups, nact, nout = xn
-        d.xn_stats, d.xn_groups, d.xn_act = ptr(nstat).value, int(ngroups), ACT[nact]
-        if ngam is not None:
-            d.xn_gamma, d.xn_beta = ptr(ngam).value, ptr(nbet).value
-        if nout is not None:
-            assert nout.f16 and nout.B == x.B and nout.H == x.H and nout.W == x.W
-            d.xn_out, d.xn_out_ld, d.xn_out_coff = ptr(nout.t).value, nout.ld, nout.coff
-    if _bparts_only:
-        return L.size('hv_conv2d_bstats_parts', ctypes.byref(d))
-    if _parts_only:
-        return L.size('hv_conv2d_stats_parts', ctypes.byref(d))
-    if d.Cout == 1:      # single-channel heads / logits: the [pixel][tap] table of conv_head.hip lives in the per-stream scratch
-        need = L.size('hv_conv2d_workspace_bytes', ctypes.byref(d))
-        if need:
-            b, _ = _ws(need, x.t.device, slot=1)
-            d.workspace, d.workspace_bytes = ptr(b).value, b.numel()
-    if _supported_only:
-        return bool(L.cdll.hv_conv2d_supported(ctypes.byref(d)))
-    if stats is not None:
-        d.stats = ptr(stats).value
-    if _TIMER is not None:
-        taps = kh * kw if not transposed else max(1, (kh * kw) // (stride * stride))
-        flops = 2.0 * y.B * y.H * y.W * d.Cout * taps * d.Cin
-        wbytes = (2 if (w_h is not None and d.precision == F16 and not w_bstride) else 4) * d.Cout * kh * kw * d.Cin * (x.B if w_bstride else 1)
-        xb, yb = (2 if x.f16 else 4), (2 if y.f16 else 4)      # algorithmic bytes: every operand once, at its storage width
-        nbytes = xb * x.B * x.H * x.W * d.Cin + yb * y.B * y.H * y.W * d.Cout * (2 if accumulate else 1) + wbytes + \
-            ((2 if mul[0].f16 else 4) * y.B * y.H * y.W * d.Cout if mul is not None else 0)
-        _TIMER.wrap(('conv', x.B, d.H, d.W, d.Cin, d.Cout, kh, stride, dil, int(transposed)), flops,
-                    lambda: L.call('hv_conv2d', ctypes.byref(d), stream()), nbytes)
-    else:
-        L.call('hv_conv2d', ctypes.byref(d), stream())
-    if wuse is not None:      # (owner, attribute): which of the layer's prepared tables this call's kernel read (engine.ParamSet skips the others when it may)
-        setattr(wuse[0], wuse[1], getattr(wuse[0], wuse[1]) | int(L.cdll.hv_last_weight_tables()))
-    return y
+_PROBES = {}      # (entry point, descriptor bytes) -> answer: the questions below are functions of the descriptor alone
 
 
-_SUPPORTED = {}
+class ConvCall:
+    """One hv_conv2d call: its filled hv_conv_desc, asked about (supported / stats_parts / bstats_parts: the C dispatch run without launching, memoised
+    by the descriptor's bytes) and launched from the same bytes.  y = act(alpha*ch_scale*conv(x, w) + bias) [* act'(m) with mul = (Act m, activation)].
+    x,y: Act; w: prepared [CoutF][k*k][CinP] tensor (or [B][...] with w_bstride); cin/cout default to the view widths (x.C consumed, y.C produced).
+    pool2: y (and mul's tensor) hold the 2x2 sum-pooled output.  x1 = (Act of ONE channel at the conv's own resolution, full fp32 forward table, its channel
+    index there, row stride, tap stride).  bn = (Act x_raw, stats [G][2][C], groups, partials or None): batch-norm backward sums out of this data gradient's
+    epilogue.  xn = (stats [G][2][Cin], gamma or None, beta or None, groups, activation name, Act out or None): x is the RAW input of a normalisation +
+    activation that the kernel applies where it stages x, storing the normalised map in `out` (hv_conv_desc in include/hvgan.h).  The pool2, x1 and xn
+    forms have no generic fallback: launch() raises RuntimeError 'unsupported' where supported() says no, so callers ask first.
+    wuse = (owner, attribute): launch() ORs in which of the layer's prepared tables its kernel read (engine.ParamSet skips the others when it may)."""
+    __slots__ = ('d', 'x', 'y', 'wuse')
+
+    def __init__(self, x, w, y, k, stride=1, pad=0, dil=1, bias=None, act='none', transposed=False, in_shift=0, alpha=1.0, accumulate=0, ch_scale=None,
+                 w_bstride=0, ch_scale_bstride=0, precision=None, cin=None, cout=None, w_h=None, mul=None, w_t=None, pool2=False, x1=None, wuse=None, bn=None,
+                 xn=None):
+        L = _lib.get()
+        self.d = d = L.hv_conv_desc()
+        self.x, self.y, self.wuse = x, y, wuse
+        kh, kw = (k, k) if isinstance(k, int) else k
+        d.x = ptr(x.t).value
+        d.B, d.H, d.W = x.B, x.H << in_shift, x.W << in_shift
+        d.in_shift, d.x_ld, d.x_coff, d.Cin = in_shift, x.ld, x.coff, (x.C if cin is None else cin)
+        d.w = ptr(w).value
+        d.w_bstride = w_bstride
+        d.Cout, d.KH, d.KW, d.stride, d.pad, d.dil, d.transposed = (y.C if cout is None else cout), kh, kw, stride, pad, dil, int(transposed)
+        d.bias = None if bias is None else ptr(bias).value
+        d.ch_scale = None if ch_scale is None else ptr(ch_scale).value
+        d.ch_scale_bstride = ch_scale_bstride
+        d.alpha, d.act, d.accumulate = alpha, ACT[act], int(accumulate)
+        d.y = ptr(y.t).value
+        d.Ho, d.Wo, d.y_ld, d.y_coff = (y.H << 1 if pool2 else y.H), (y.W << 1 if pool2 else y.W), y.ld, y.coff
+        d.pool2 = int(bool(pool2))
+        if x1 is not None:
+            xa, wfull, ch, w1_row, w1_tap = x1
+            assert xa.C == 1 and xa.H == d.H and xa.W == d.W
+            d.x1, d.x1_f16, d.x1_ld, d.x1_coff = ptr(xa.t).value, xa.f16, xa.ld, xa.coff
+            d.w1, d.w1_row, d.w1_tap = ptr(wfull).value + 4 * ch, w1_row, w1_tap
+        d.precision = precision_id(precision)
+        d.w_f16 = None if w_h is None else ptr(w_h).value
+        d.w_f16_tiled = None if (w_t is None or w_h is None) else ptr(w_t).value      # w_h in MFMA-fragment order (tile_weights / hv_weight_prep)
+        d.x_f16, d.y_f16 = x.f16, y.f16
+        if mul is not None:
+            m, mact = mul
+            d.mul_src, d.mul_ld, d.mul_coff, d.mul_act, d.mul_f16 = ptr(m.t).value, m.ld, m.coff, ACT[mact], m.f16
+        if bn is not None:
+            bx, bstat, bgroups, bpart = bn
+            assert bx.f16 == y.f16 and bx.H == y.H and bx.W == y.W and bx.B == y.B
+            d.bn_x, d.bn_x_ld, d.bn_x_coff = ptr(bx.t).value, bx.ld, bx.coff
+            d.bn_stats, d.bn_groups = ptr(bstat).value, int(bgroups)
+            if bpart is not None:
+                d.bstats = ptr(bpart).value
+        if xn is not None:
+            nstat, ngam, nbet, ngroups, nact, nout = xn
+            d.xn_stats, d.xn_groups, d.xn_act = ptr(nstat).value, int(ngroups), ACT[nact]
+            if ngam is not None:
+                d.xn_gamma, d.xn_beta = ptr(ngam).value, ptr(nbet).value
+            if nout is not None:
+                assert nout.f16 and nout.B == x.B and nout.H == x.H and nout.W == x.W
+                d.xn_out, d.xn_out_ld, d.xn_out_coff = ptr(nout.t).value, nout.ld, nout.coff
+        if d.Cout == 1:      # single-channel heads / logits: the [pixel][tap] table of conv_head.hip lives in the per-stream scratch (the xn check reads it too)
+            need = L.size('hv_conv2d_workspace_bytes', ctypes.byref(d))
+            if need:
+                b, _ = _ws(need, x.t.device, slot=1)
+                d.workspace, d.workspace_bytes = ptr(b).value, b.numel()
+
+    def _probe(self, fn):
+        key = (fn, bytes(self.d))
+        if key not in _PROBES:
+            _PROBES[key] = _lib.get().size(fn, ctypes.byref(self.d))
+        return _PROBES[key]
+
+    def supported(self):
+        return bool(self._probe('hv_conv2d_supported'))
+
+    def stats_parts(self):      # rows launch(stats) would write (0: no statistics epilogue)
+        return self._probe('hv_conv2d_stats_parts')
+
+    def bstats_parts(self):     # parts of the batch-norm backward sums bn=(x_raw, stats, groups, None) would write (0: no such epilogue)
+        return self._probe('hv_conv2d_bstats_parts')
+
+    def launch(self, stats=None):
+        """stats: float tensor of stats_parts() * Cout * 2 elements that receives the per-channel partial sums of the stored output (hv_conv_desc.stats;
+        feeds norm_act_forward(partials=...))."""
+        L, d, x, y = _lib.get(), self.d, self.x, self.y
+        if stats is not None:
+            d.stats = ptr(stats).value
+        if _TIMER is not None:
+            taps = d.KH * d.KW if not d.transposed else max(1, (d.KH * d.KW) // (d.stride * d.stride))
+            flops = 2.0 * y.B * y.H * y.W * d.Cout * taps * d.Cin
+            wbytes = (2 if (d.w_f16 and d.precision == F16 and not d.w_bstride) else 4) * d.Cout * d.KH * d.KW * d.Cin * (x.B if d.w_bstride else 1)
+            xb, yb = (2 if x.f16 else 4), (2 if y.f16 else 4)      # algorithmic bytes: every operand once, at its storage width
+            nbytes = xb * x.B * x.H * x.W * d.Cin + yb * y.B * y.H * y.W * d.Cout * (2 if d.accumulate else 1) + wbytes + \
+                ((2 if d.mul_f16 else 4) * y.B * y.H * y.W * d.Cout if d.mul_src else 0)
+            _TIMER.wrap(('conv', x.B, d.H, d.W, d.Cin, d.Cout, d.KH, d.stride, d.dil, d.transposed), flops,
+                        lambda: L.call('hv_conv2d', ctypes.byref(d), stream()), nbytes)
+        else:
+            L.call('hv_conv2d', ctypes.byref(d), stream())
+        if self.wuse is not None:
+            setattr(self.wuse[0], self.wuse[1], getattr(*self.wuse) | int(L.cdll.hv_last_weight_tables()))
+        return y
+
+
+def conv2d(*args, stats=None, **kw):
+    """ConvCall(...).launch(stats) -> y."""
+    return ConvCall(*args, **kw).launch(stats)
 
 
 def conv2d_supported(*args, **kw):
-    """Would conv2d(...) with these arguments be served?  (hv_conv2d_supported: the C dispatch itself, run without launching -- the x1 and pool2
-    forms have no generic fallback, so their callers ask before they drop the materialised alternative.)"""
-    return conv2d(*args, _supported_only=True, **kw)
-
-
-def pool2_ok(g, y_low, k, stride, pad, dil, precision, w_h, w_t, cout=None, w=None):
-    """Can conv2d(..., transposed=True, pool2=True) serve this data gradient?  Asked of the C dispatch (hv_conv2d_supported), once per shape."""
-    if w_h is None or w_t is None or precision_id(precision) != F16 or g.H != 2 * y_low.H or g.W != 2 * y_low.W:
-        return False
-    co = y_low.C if cout is None else cout
-    key = ('pool2', g.B, g.H, g.W, g.C, g.ld, g.coff, g.f16, co, y_low.ld, y_low.coff, y_low.f16, k, stride, pad, dil, ptr(w_t).value & 15)
-    r = _SUPPORTED.get(key)
-    if r is None:
-        r = _SUPPORTED[key] = conv2d_supported(g, w_h if w is None else w, Act(y_low.t, co, y_low.coff), k, stride, pad, dil, transposed=True, pool2=True,
-                                               precision=precision, w_h=w_h, w_t=w_t)
-    return r
-
-
-def conv2d_bstats_parts(*args, **kw):
-    """Parts of the batch-norm backward sums the conv2d call with these arguments (bn=(x_raw, stats, groups, None)) would write (0: no such epilogue)."""
-    return conv2d(*args, _bparts_only=True, **kw)
+    return ConvCall(*args, **kw).supported()
 
 
 def conv2d_stats_parts(*args, **kw):
-    """Partial-sum rows the conv2d call with these arguments would write into `stats` (0: its kernel has no statistics epilogue)."""
-    return conv2d(*args, _parts_only=True, **kw)
+    return ConvCall(*args, **kw).stats_parts()
+
+
+def conv2d_bstats_parts(*args, **kw):
+    return ConvCall(*args, **kw).bstats_parts()
+
+
+def pool2_ok(g, y_low, k, stride, pad, dil, precision, w_h, w_t, cout=None, w=None):
+    """Can conv2d(..., transposed=True, pool2=True) serve this data gradient?"""
+    if w_h is None or w_t is None or precision_id(precision) != F16 or g.H != 2 * y_low.H or g.W != 2 * y_low.W:
+        return False
+    return conv2d_supported(g, w_h if w is None else w, Act(y_low.t, y_low.C if cout is None else cout, y_low.coff), k, stride, pad, dil, transposed=True,
+                            pool2=True, precision=precision, w_h=w_h, w_t=w_t)
 
 
 class FoldChain:

@@ -632,8 +632,8 @@ def test_generator_with_other_widths_takes_the_materialised_concat(monkeypatch):
 
 def test_train_step_with_the_filters_in_lds_kernel_switched_off():
     """HV_CONV_LF=0 (a documented A/B knob, read once by the C side: own process): every 3x3 layer falls back to conv_halo2 -- incl. the concat layers, whose
-    extra-channel form and pooled data gradient only the switched-off kernel serves: the Python side asks hv_conv2d_supported / pool2_ok of the dispatch
-    and materialises the concat / the full-resolution gradient again.  Two train steps run and give the default build's losses."""
+    extra-channel form and pooled data gradient only the switched-off kernel serves: the Python side asks hv_conv2d_supported of the dispatch
+    (ConvNode.forward_call / pooled) and materialises the concat / the full-resolution gradient again.  Two train steps run and give the default build's losses."""
     import json
     import subprocess
     import sys
