@@ -600,6 +600,26 @@ int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs
                        long long ls0, long long ls1, long long ls2, int D1, int window, double win_min, double win_max, const uint64_t* presence,
                        const int* boxes, int V, int O0, int O1, int O2, double* ct_out, uint8_t* label_out, void* stream);
 
+/* ---- generation-quality evaluation of a synthesized volume (reference evaluation/generation_eval_sagittal.py:11-37 calculate_iou /
+ * calculate_dice / relative_volume_difference, :39-103 process_images; generation_eval_coronal.py the same with the slice axis 1; SURVEY.md
+ * row 17).  Four [H][W][Z] volumes: element (h, w, z) of the CTs at base[h*cs0 + w*cs1 + z*cs2], of the labels
+ * at base[h*ls0 + w*ls1 + z*ls2] (strides in elements, any order); ct_dtype HV_DT_F32 / F64, label_dtype HV_DT_U8 / F32 / F64; all
+ * arithmetic in float64.  view 2 = sagittal (slices [:, :, z]), 1 = coronal ([:, z, :]).  ori = (ori_seg == label), fake = (fake_seg == label).
+ * Slices z0..z1 (the ori's extent along the view axis), n = z1 - z0 + 1, m = (4n)//5, evaluated: z in [z0 + (n - m)//2, +m) whose ori has
+ * more than 400 voxels.  Per evaluated slice: rows x1..x2 (the ori's first / last row) x the whole other axis is the patch; PSNR
+ * 10 log10(R^2 / mean squared error) and SSIM (scikit-image 0.22: 7x7 uniform window, covariance 49/48, C1 (0.01 R)^2, C2 (0.03 R)^2,
+ * 3-pixel border cropped) of the patch and of the whole slice, R = max - min of the ori CT over the patch / slice.
+ * out[16]: [0] global psnr, [1] global ssim, [2] patch psnr, [3] patch ssim (means over the evaluated slices of the non-NaN values, 0 if
+ * none), [4] iou, [5] rv_diff, [6] dice (exact integer counts), [7] 1 if the ori is empty (the reference raises), [8] 1 if an evaluated
+ * slice's patch or side is shorter than 7 (structural_similarity raises), [9] evaluated slices, [10..12] |ori|, |fake|, |ori & fake|,
+ * [13] z0, [14] z1, [15] records written.  slices (NULL or 9 doubles per slice along the view axis): per slice of the 4/5 range in order
+ * { z, x1, x2, R_patch, R_global, psnr_patch, ssim_patch, psnr_global, ssim_global }, z = -1 where the slice is not evaluated.  ori_ct = fake_ct = NULL: the counts and [4..12]
+ * only.  No host synchronisation; workspace 16-byte aligned, hv_gen_eval_workspace_bytes bytes. */
+size_t hv_gen_eval_workspace_bytes(int H, int W, int Z, int view);
+int hv_gen_eval(const void* ori_ct, const void* fake_ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* ori_seg,
+                const void* fake_seg, int label_dtype, long long ls0, long long ls1, long long ls2, int H, int W, int Z, int view, double label,
+                double* out, double* slices, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
