@@ -9,7 +9,7 @@ __version__ = "0.1.0"
 from . import synth  # noqa: E402,F401  (numpy only)
 from . import lib  # noqa: E402,F401  (ctypes binding; loads libhvgan.so lazily)
 from . import ops  # noqa: E402,F401
-from . import engine, optim, ddp, profiler, evaluation, eval_metrics  # noqa: E402,F401
+from . import engine, optim, ddp, step_runner, profiler, evaluation, eval_metrics  # noqa: E402,F401
 from . import models  # noqa: E402,F401  (drop-in mirror of the reference's `models` package)
 from . import straighten  # noqa: E402,F401  (stage 1: centroids, straightening, per-vertebra crops)
 from . import generation_eval  # noqa: E402,F401  (generation-quality evaluation of synthesized volumes)

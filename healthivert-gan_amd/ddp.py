@@ -16,7 +16,7 @@ all-reduce each on a dedicated HIP stream:
   broadcast through the process group, ncclCommInitRank) on torch's own librccl.so.  torch's ProcessGroupNCCL is used for the rendezvous, the weight
   broadcast and the bench clock only: its watchdog thread polls the end events of its collectives, and a poll that lands while a stream of the
   process is capturing aborts the process on this stack (`hipErrorCapturedEvent`), so nothing of the step is issued through it;
-* which schedule a multi-GPU job takes is decided by a preflight on the job's own first batch (`Pix2PixModel.dp_preflight`): both are run, their
+* which schedule a multi-GPU job takes is decided by a preflight on the job's own first batch (`step_runner.StepRunner.dp_preflight`): both are run, their
   results compared across the ranks, the faster correct one is kept.
 
 `init_from_env()` joins the process group that `python -m torch.distributed.run` describes in the environment, so

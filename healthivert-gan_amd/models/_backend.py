@@ -9,4 +9,4 @@ _root = os.path.dirname(_pkg_dir)
 if _root not in sys.path:
     sys.path.insert(0, _root)
 hv = importlib.import_module(os.path.basename(_pkg_dir))
-engine, ops, lib, ddp, optim = hv.engine, hv.ops, hv.lib, hv.ddp, hv.optim
+engine, ops, lib, ddp, optim, step_runner = hv.engine, hv.ops, hv.lib, hv.ddp, hv.optim, hv.step_runner

@@ -47,11 +47,7 @@ class BaseModel(ABC):
             self.load_networks('iter_%d' % opt.load_iter if opt.load_iter > 0 else opt.epoch)
         self.print_networks(opt.verbose)
 
-    def sync_tail(self):
-        """Order the current stream after work a subclass leaves pending on other streams (Pix2PixModel's data-parallel step)."""
-
     def eval(self):
-        self.sync_tail()
         for _, net in self._nets():
             net.eval()
 
@@ -71,7 +67,6 @@ class BaseModel(ABC):
         return self.image_paths
 
     def update_learning_rate(self):
-        self.sync_tail()      # an optimiser step still queued on another stream (data-parallel schedule) must read the OLD learning rate
         old_lr = self.optimizers[0].param_groups[0]['lr']
         for s in self.schedulers:
             if self.opt.lr_policy == 'plateau':
@@ -81,7 +76,6 @@ class BaseModel(ABC):
         print('learning rate %.7f -> %.7f' % (old_lr, self.optimizers[0].param_groups[0]['lr']))
 
     def get_current_visuals(self):
-        self.sync_tail()
         return OrderedDict((n, getattr(self, n)) for n in self.visual_names if isinstance(n, str))
 
     def get_current_losses(self):
@@ -90,7 +84,6 @@ class BaseModel(ABC):
     def save_networks(self, epoch):
         if ddp.rank() != 0:        # one process per GPU, identical weights on every rank: rank 0 writes the checkpoint
             return
-        self.sync_tail()
         os.makedirs(self.save_dir, exist_ok=True)
         for name, net in self._nets():
             sd = OrderedDict((k, v.detach().cpu()) for k, v in net.state_dict().items())

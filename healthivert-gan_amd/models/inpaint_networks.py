@@ -326,11 +326,6 @@ class Generator(nn.Module):
         self._eval_graphs = {}
         self.use_graph = os.environ.get('HV_GRAPH', '1') != '0'
         self._pset_convs = None
-        self._tail_stream = None       # a stream still updating the weights (the data-parallel step's exchange stream)
-
-    def _wait_tail(self):
-        if self._tail_stream is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream().wait_stream(self._tail_stream)
 
     # ---------------------------------------------------------------- parameters
     def paramset(self):
@@ -598,7 +593,6 @@ class Generator(nn.Module):
         (coarse_seg, fine_seg, x_stage1, x_stage2, offset_flow, pred1_h, pred2_h)."""
         if not torch.is_tensor(slice_ratio):
             slice_ratio = torch.as_tensor(slice_ratio, dtype=torch.float64).reshape(-1)
-        self._wait_tail()
         if self.use_graph and not self.training and not torch.is_grad_enabled() and ops.timer() is None and x.is_cuda:
             P = self._eval_replay(x, mask, CAM, slice_ratio)
         else:

@@ -37,7 +37,7 @@ class FusedAdam(torch.optim.Optimizer):
         return ps
 
     def _ensure_state(self):
-        """Moments, step count and learning rate on the device before the first step (Pix2PixModel.dp_preflight snapshots them)."""
+        """Moments, step count and learning rate on the device before the first step (StepRunner.dp_preflight snapshots them)."""
         ps = [p for g in self.param_groups for p in g['params']]
         dev = ps[0].device
         if self._m is None or self._m.device != dev:

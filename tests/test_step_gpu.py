@@ -242,6 +242,74 @@ def test_graph_recapture_when_the_batch_shape_changes(monkeypatch):
     assert le == lg
 
 
+# what forward() / the phases bound per batch shape before ShapeState recorded it (the hand-kept list it replaces): none may drop out
+STEP_BOUND = ('fake_B', 'fake_B_coarse', 'fake_B_local', 'real_B_local', 'fake_B_mask_raw', 'coarse_seg_binary', 'coarse_seg_sigmoid', 'fake_B_mask_sigmoid',
+              'x_stage1', 'fake_B_raw', 'pred1_h', 'pred2_h', 'real_edges', 'fake_edges', '_gplan', '_rows', '_dxs')
+SHAPE_SEQUENCE = (2, 2, 2, 2, 1, 1, 1, 2, 2)
+
+
+def _shape_sequence_run(use_graph, after_step):
+    from hvgan import synth
+    from hvgan.models.pix2pix_model import Pix2PixModel
+    torch.manual_seed(7)
+    model = Pix2PixModel(make_opt())
+    model.use_graph = use_graph
+    for step, B in enumerate(SHAPE_SEQUENCE):
+        model.set_input(synth.make_batch(B, 256, seed=900 + step))
+        model.optimize_parameters()
+        after_step(model, step, B)
+    torch.cuda.synchronize()
+
+
+def test_every_bound_tensor_follows_the_active_batch_shape(monkeypatch):
+    """Batch sizes 2, 2, 2, 2, 1, 1, 1, 2, 2 with graphs on (fp16 mode): after every step each name the active ShapeState recorded is, on the model,
+    that very tensor, with the current batch size in front; when batch size 2 comes back its tensors are the buffers of its first visit."""
+    monkeypatch.setenv('HV_PRECISION', 'fp16')
+    import hvgan  # noqa: F401
+    first = {}
+
+    def check(model, step, B):
+        bound = model._cur.bound
+        assert set(STEP_BOUND) <= set(bound), sorted(set(STEP_BOUND) - set(bound))
+        tensors = {n: t for n, t in bound.items() if isinstance(t, torch.Tensor)}
+        assert len(tensors) >= len(STEP_BOUND) - 2      # (_gplan is the generator's plan, _dxs a dict of tensors)
+        for n, t in tensors.items():
+            assert getattr(model, n) is t, (step, B, n)
+            if t.dim() == 4 or n == '_rows':      # (B, ...); pred1_h / pred2_h are (1, B)
+                assert t.shape[0] == B, (step, B, n, tuple(t.shape))
+        assert model.pred1_h.shape == model.pred2_h.shape == (1, B)
+        ptrs = {n: t.data_ptr() for n, t in tensors.items()}
+        if B == 2:
+            assert first.setdefault(2, ptrs) == ptrs, (step, [n for n in ptrs if first[2].get(n) != ptrs[n]])
+        else:
+            assert not set(ptrs.values()) & set(first[2].values()), (step, B)
+
+    _shape_sequence_run(True, check)
+
+
+def test_replay_after_a_shape_comes_back_shows_that_shape_s_visuals(monkeypatch):
+    """The same sequence: the first step after batch size 2 returns is a pure graph replay (no Python rebinds anything), and get_current_visuals()
+    must show THAT step's batch-size-2 images: bit for bit those of a run that launches every step eagerly."""
+    monkeypatch.setenv('HV_PRECISION', 'fp16')
+    import hvgan  # noqa: F401
+    back = SHAPE_SEQUENCE.index(2, SHAPE_SEQUENCE.index(1))
+    seen = {}
+
+    def grab(use_graph):
+        def after(model, step, B):
+            if step == back:
+                assert (model._graphs is not None) == use_graph
+                assert list(model.get_current_visuals()) == model.visual_names
+                seen[use_graph] = {n: v.detach().clone() for n, v in model.get_current_visuals().items()}
+        return after
+
+    _shape_sequence_run(False, grab(False))
+    _shape_sequence_run(True, grab(True))
+    for n, v in seen[True].items():
+        assert v.shape[0] == 2, (n, tuple(v.shape))
+        assert torch.equal(v, seen[False][n]), (n, (v.float() - seen[False][n].float()).abs().max().item())
+
+
 def test_step_at_512_matches_live_oracle(monkeypatch):
     """BASELINE config #5's slice size: one full train step at 512 x 512 (attention over 128 x 128 patches, L = 4096; 62 x 62 PatchGAN logits)
     from seeded weights against the CPU oracle on the same weights and batch -- nothing in the kernels or the host mirror is tied to 256."""

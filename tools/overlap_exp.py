@@ -22,7 +22,7 @@ mode = m.opt.gan_mode
 def step_overlap():
     main = torch.cuda.current_stream()
     for k in (1, 2, 3):
-        side = m._d_streams[k - 1]
+        side = m._runner.d_streams[k - 1]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             net = getattr(m, 'netD_%d' % k)
@@ -33,7 +33,7 @@ def step_overlap():
     m.forward()
     fakes = {1: m.fake_B, 2: m.fake_B_mask_raw, 3: m.fake_B_local}
     for k in (1, 2, 3):
-        side = m._d_streams[k - 1]
+        side = m._runner.d_streams[k - 1]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             net = getattr(m, 'netD_%d' % k)
@@ -44,7 +44,7 @@ def step_overlap():
             net.finish()
             getattr(m, 'optimizer_D_%d' % k).step(sync_lr=False)
             m._g_step_D(k)
-    m._join_d(main)
+    m._runner.join(main)
     m.backward_G(d_done=True)
     m.optimizer_G.step(sync_lr=False)
 

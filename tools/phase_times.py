@@ -24,21 +24,21 @@ for it in range(N):
     m.forward()
     ev[1].record()
     # phase A without the forward
-    m._dxs = {}
+    m._bind('_dxs', {})
     for k, bw in ((1, m.backward_D_1), (2, m.backward_D_2), (3, m.backward_D_3)):
-        side = m._d_streams[k - 1]
+        side = m._runner.d_streams[k - 1]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             bw()
-    m._join_d(main)
+    m._runner.join(main)
     ev[2].record()
     for k in (1, 2, 3):
-        side = m._d_streams[k - 1]
+        side = m._runner.d_streams[k - 1]
         side.wait_stream(main)
         with torch.cuda.stream(side):
             getattr(m, 'optimizer_D_%d' % k).step(sync_lr=False)
             m._g_step_D(k)
-    m._join_d(main)
+    m._runner.join(main)
     ev[3].record()
     m.backward_G(d_done=True)
     ev[4].record()
