@@ -7,6 +7,7 @@ The nn.Modules of `models/` hold the parameters (reference state-dict keys) and 
 import contextlib
 import ctypes
 import os
+import types
 
 import torch
 
@@ -521,168 +522,165 @@ def _bgemm(A, B, C, M, N, K, batch, alpha=1.0, colscale=None, b_split=0):
                     ctypes.c_longlong(N if colscale is not None else 0), int(b_split), stream())
 
 
+def attention_route(prec, f, C, h, w):
+    """Route of one AttentionPlan.forward over the map `f`: 'conv' (exact fp32: the contractions as per-sample-filter convolutions), 'gemm' (fp16: batched GEMMs, the scores on the
+    3x3 patch tables) or, where its kernels serve the shape, 'gram' (... the scores on the pixel Gram matrix).  The flags are read at the call."""
+    if not (CA_GEMM and ops.precision_id(prec) == ops.F16 and (9 * C) % 32 == 0 and (h * w) % 32 == 0 and C % 4 == 0):
+        return 'conv'
+    return 'gram' if CA_GRAM and f.f16 and C == 64 and w in (32, 64) and f.ld % 8 == 0 and f.coff == 0 else 'gemm'
+
+
+# The tables each route alone reads, per pass, and the score-side ones every route shares.  f32 / out32 / dout32 / df32: fp32 copies of boundary maps, held where the map is stored as
+# fp16 (the GEMM routes' boundary kernels read / write such maps themselves).  Tables that are only GEMM operands are fp16, written so by their producers (wp_h beside the fp32 wp, A_h).
+CA_TABLES = dict(conv=dict(forward='fd wp wpT raw rawT A f32 out32', backward='AT dOrawT dwp dout32 df32'),
+                 gemm=dict(forward='fd wp wp_h raw_h rawT_h A_h O', backward='wpT_h dwp dOraw_h dOrawT_h AT_h df32'),
+                 gram=dict(forward='fd_h fdT_h q raw_h rawT_h A_h O', backward='dOraw_h dOrawT_h AT_h df32'),
+                 shared=dict(forward='S0 S1 norm rnorm mm argmax', per_sample='mm_b', backward='dA dS1 dS0 Gs coef'))
+
+
 class AttentionPlan:
-    """ContextualAttention(ksize=3, stride=1, rate=2, fuse_k=3, softmax_scale=10, fuse=True) on an NHWC feature map
-    (reference models/inpaint_networks.py:235-410)."""
+    """ContextualAttention(ksize=3, stride=1, rate=2, fuse_k=3, softmax_scale=10, fuse=True) on an NHWC feature map (reference models/inpaint_networks.py:235-410).
+    forward / backward are one skeleton around the steps of the call's route (`steps`); a plan that has served two routes holds two sets of tables that share nothing."""
 
     def __init__(self, B, H, W, C, device, img_hw, scale=10.0, fuse=True):
-        self.B, self.H, self.W, self.C = B, H, W, C
-        self.h, self.w = H // 2, W // 2
-        assert self.h == self.w and H % 2 == 0, "contextual attention expects a square, even-sized feature map"
-        self.L = L = self.h * self.w
+        self.B, self.H, self.W, self.C, self.dims, self.device = B, H, W, C, (B, H, W, C), device
+        self.h, self.w, self.L = h, w, L = H // 2, W // 2, (H // 2) * (W // 2)
+        assert h == w and H % 2 == 0, "contextual attention expects a square, even-sized feature map"
         self.img_hw, self.scale, self.fuse = img_hw, scale, fuse
-        z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
-        self.fd = Act(z(B, self.h, self.w, C))
-        self.wp, self.wpT = z(B, L, 9 * C), z(B, 9 * C, L)
-        self.norm, self.rnorm = z(B, L), z(B, L)
-        self.raw, self.rawT = z(B, L, 16 * C), z(B, C, 16 * L)
-        self.mm = z(L)
-        self.mm_b = None      # [B][L], allocated on the first per-sample-mask forward
-        self.S0, self.S1, self.A = Act(z(B, self.h, self.w, L)), Act(z(B, self.h, self.w, L)), Act(z(B, self.h, self.w, L))
-        self.argmax = torch.zeros(B * L, dtype=torch.int32, device=device)
-        self.bw = None
+        self.fused_adjoint = fuse and h == 32 and w == 32      # hv_ca_fuse_backward_prep: one pass, the plain scores' gradient (dS0) stays on chip
+        self.unused = set() if fuse and not self.fused_adjoint else {'dS0'} if fuse else {'S1', 'dS0'}      # shared tables this plan never reads
+        f32, f16 = torch.float32, torch.float16      # name -> dtype, shape (four-dimensional: held as an Act) of every table a plan may hold
+        LL, fmap, vec, tab, tabT = (f32, (B, h, w, L)), (f32, (B, H, W, C)), (f32, (B, L)), (f16, (B, L, 16 * C)), (f16, (B, 16 * C, L))
+        self.spec = dict(S0=LL, S1=LL, dS0=LL, A=LL, AT=LL, dA=LL, dS1=LL, Gs=LL, f32=fmap, out32=fmap, dout32=fmap, df32=fmap, norm=vec, rnorm=vec, q=vec, mm_b=vec, mm=(f32, (L,)),
+                         argmax=(torch.int32, (B * L,)), coef=(f32, (33 * B, L)), fd=(f32, (B, h, w, C)), dwp=(f32, (B, h, w, 9 * C)), wp=(f32, (B, L, 9 * C)), wpT=(f32, (B, 9 * C, L)),
+                         raw=(f32, (B, L, 16 * C)), rawT=(f32, (B, C, 16 * L)), dOrawT=(f32, (B, C, 16 * L)), wp_h=(f16, (B, L, 9 * C)), wpT_h=(f16, (B, 9 * C, L)), raw_h=tab, rawT_h=tabT,
+                         O=tab, dOraw_h=tab, dOrawT_h=tabT, A_h=(f16, (B, L, L)), AT_h=(f16, (B, L, L)), fd_h=(f16, (B, L, C)), fdT_h=(f16, (B, C, L)))
+        # (route, name) -> every tensor the plan holds; route -> the namespace of that route's tables; route and (precision, per-sample mask) of the last completed forward
+        self.owned, self.sets, self.route, self.last = {}, {}, None, None
+        self.buffers('shared', 'forward')
+
+    gemm = property(lambda self: self.route in ('gemm', 'gram'))
+    gram = property(lambda self: self.route == 'gram')
+    nbytes = lambda self: sum(t.numel() * t.element_size() for t in self.owned.values())      # device bytes of every tensor the plan owns now
+
+    def buffers(self, route, stage, skip=()):
+        """-> the holder of `route`'s tables ('shared': the plan itself) once those of `stage` are in it, bar `skip`: zeroed on first use and kept for the life of the plan."""
+        r = self if route == 'shared' else self.sets.setdefault(route, types.SimpleNamespace())
+        for n in CA_TABLES[route][stage].split():
+            if (route, n) in self.owned or n in self.unused or n in skip:
+                continue
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('AttentionPlan%s: %s route, %s would allocate %s inside a stream capture -- run it eagerly once first' % (self.dims, route, stage, n))
+            t = self.owned[route, n] = torch.zeros(*self.spec[n][1], dtype=self.spec[n][0], device=self.device)
+            setattr(r, n, Act(t) if t.dim() == 4 else t)
+        return r
 
     def forward(self, f, mask_img, out, prec, want_argmax=False, per_sample_mask=False):
-        """f: Act [B,H,W,C] (foreground == background), mask_img: (B,1,Himg,Wimg) tensor, out: Act [B,H,W,C].
-        per_sample_mask: every sample's own mask decides its valid patches -- the batch stands for B independent batch-1 calls (the
-        reference's inference loop); False = the reference's batched behaviour (sample 0's mask for all, inpaint_networks.py:314)."""
-        L_ = _lib.get()
-        B, H, W, C, L = self.B, self.H, self.W, self.C, self.L
-        # the attention block keeps fp32 internally (its score matrices feed a x10 soft-max): fp16-stored feature maps are converted
-        # at its boundary (two small copies of the 64-channel map)
-        out_user = None
-        gemm = CA_GEMM and ops.precision_id(prec) == ops.F16 and (9 * C) % 32 == 0 and L % 32 == 0 and C % 4 == 0
-        self.gemm = gemm
-        # (the GEMM route's boundary kernels read / write fp16-stored maps themselves: same values, no conversion copies)
-        if f.f16 and not gemm:
-            self.f32 = getattr(self, 'f32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=f.t.device))
-            ops.copy_channels(f, self.f32, mode=0)
-            f = self.f32
-        if out.f16 and not gemm:
-            self.out32 = getattr(self, 'out32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=f.t.device))
-            out_user, out = out, self.out32
-        if gemm:
-            # GEMM route: the patch tables that are only GEMM operands are stored as fp16 (half the bytes through the vector memory path, no
-            # conversion when staged); wp stays fp32 (norms, the patch gradient's coefficient term), its transpose is written as fp16
-            # Round 3: the copies are written by their PRODUCERS -- wp_h beside wp by the patch kernel, the attention matrix as fp16 only by the
-            # soft-max (the form before, fp32 tables converted when a GEMM stages them, gave the same GEMM bits; retired) -- and the transpose of
-            # wp, which only the backward reads, is taken there
-            if getattr(self, 'raw_h', None) is None:
-                hz = lambda *s: torch.zeros(*s, dtype=torch.float16, device=f.t.device)
-                self.raw_h, self.rawT_h, self.wpT_h = hz(B, L, 16 * C), hz(B, 16 * C, L), hz(B, 9 * C, L)
-                self.wp_h, self.A_h = hz(B, L, 9 * C), hz(B, L, L)
-                self.O = hz(B, L, 16 * C)          # the paste product only feeds the fold (whose result is stored as fp16): fp16 too
-            # scores on the pixel Gram matrix (K = C, no patch tables) where the kernels serve the shape
-            self.gram = bool(CA_GRAM and f.f16 and C == 64 and self.w in (32, 64) and f.ld % 8 == 0 and f.coff == 0)
-            if self.gram:
-                if getattr(self, 'fd_h', None) is None:
-                    self.fd_h = torch.zeros(B, L, C, dtype=torch.float16, device=f.t.device)
-                    self.fdT_h = torch.zeros(B, C, L, dtype=torch.float16, device=f.t.device)
-                    self.q = torch.zeros(B, L, dtype=torch.float32, device=f.t.device)
-                L_.call('hv_ca_gram_down', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd_h), ptr(self.fdT_h), ptr(self.q), stream())
-            else:
-                L_.call('hv_ca_patches_h', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), ptr(self.wp_h), ptr(self.norm), ptr(self.rnorm), stream())
-            L_.call('hv_ca_raw_patches_f16', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.raw_h), ptr(self.rawT_h), stream())
-        else:
-            L_.call('hv_ca_patches', ptr(f.t), f.f16, B, H, W, C, f.ld, ptr(self.fd.t), ptr(self.wp), ptr(self.wpT), ptr(self.norm), ptr(self.rnorm), stream())
-            L_.call('hv_ca_raw_patches', ptr(f.t), B, H, W, C, f.ld, ptr(self.raw), ptr(self.rawT), stream())
-        if per_sample_mask:
-            if self.mm_b is None:
-                self.mm_b = torch.zeros(B, L, dtype=torch.float32, device=self.mm.device)
-            L_.call('hv_ca_mask_batched', ptr(mask_img), B, ctypes.c_longlong(self.img_hw[0] * self.img_hw[1]), self.img_hw[0], self.img_hw[1],
-                    self.h, self.w, ptr(self.mm_b), stream())
-        else:
-            L_.call('hv_ca_mask', ptr(mask_img), self.img_hw[0], self.img_hw[1], self.h, self.w, ptr(self.mm), stream())
-        if gemm and self.gram:
-            L_.call('hv_ca_gram_scores', ptr(self.fd_h), ptr(self.q), B, self.h, self.w, C, ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), stream())
-        elif gemm:    # the 3x3 patches of the (zero-padded) map are both the conv's input columns and its filters: scores = rnorm (.) wp wp^T
-            _bgemm(self.wp_h, self.wp_h, self.S0.t, L, L, 9 * C, B, colscale=self.rnorm)
-        else:
-            ops.conv2d(self.fd, self.wp, self.S0, 3, 1, 1, 1, w_bstride=L * 9 * C, ch_scale=self.rnorm, ch_scale_bstride=L, precision=prec)
+        """f: Act [B,H,W,C] (foreground == background), mask_img: (B,1,Himg,Wimg) tensor, out: Act [B,H,W,C].  per_sample_mask: every sample's own mask decides its valid patches --
+        the batch stands for B independent batch-1 calls (the reference's inference loop); False = the reference's batched behaviour (sample 0's mask for all, inpaint_networks.py:314)."""
+        route, self.route, self.last = attention_route(prec, f, self.C, self.h, self.w), None, None      # (recorded once every launch is out: a forward that raises leaves no backward)
+        L_, B, L, (patches, scores, paste) = _lib.get(), self.B, self.L, self.steps[route][:3]
+        r = self.buffers(route, 'forward', skip=[n for n, a in (('f32', f), ('out32', out)) if not a.f16])
+        mm, mm_stride = (self.buffers('shared', 'per_sample').mm_b, L) if per_sample_mask else (self.mm, 0)
+        patches(self, r, f)
+        mask = ('hv_ca_mask_batched', ptr(mask_img), B, ctypes.c_longlong(self.img_hw[0] * self.img_hw[1])) if per_sample_mask else ('hv_ca_mask', ptr(mask_img))
+        L_.call(*mask, *self.img_hw, self.h, self.w, ptr(mm), stream())
+        scores(self, r, prec)
         if self.fuse:
             L_.call('hv_ca_fuse', ptr(self.S0.t), ptr(self.S1.t), B, self.h, self.w, 0, stream())
-            s = self.S1
-        else:
-            s = self.S0
-        if gemm:
-            L_.call('hv_ca_softmax_f16', ptr(s.t), ptr(self.mm_b if per_sample_mask else self.mm), ctypes.c_longlong(L if per_sample_mask else 0),
-                    ptr(self.A_h), B, L, ctypes.c_float(self.scale), ptr(self.argmax) if want_argmax else None, stream())
+        s = self.S1 if self.fuse else self.S0      # (the score matrices stay fp32 on every route: they feed a x10 soft-max)
+        if route != 'conv':
+            L_.call('hv_ca_softmax_f16', ptr(s.t), ptr(mm), ctypes.c_longlong(mm_stride), ptr(r.A_h), B, L, ctypes.c_float(self.scale), ptr(self.argmax) if want_argmax else None, stream())
         elif per_sample_mask:
-            L_.call('hv_ca_softmax_batched', ptr(s.t), ptr(self.mm_b), ctypes.c_longlong(L), ptr(self.A.t), B, L, ctypes.c_float(self.scale),
-                    ptr(self.argmax) if want_argmax else None, stream())
+            L_.call('hv_ca_softmax_batched', ptr(s.t), ptr(mm), ctypes.c_longlong(mm_stride), ptr(r.A.t), B, L, ctypes.c_float(self.scale), ptr(self.argmax) if want_argmax else None, stream())
         else:
-            L_.call('hv_ca_softmax', ptr(s.t), ptr(self.mm), ptr(self.A.t), B, L, ctypes.c_float(self.scale),
-                    ptr(self.argmax) if want_argmax else None, stream())
-        if gemm:    # paste = (A rawT^T) folded: O[p][(c, tap)], then every output pixel sums the 4 taps that reach it
-            _bgemm(self.A_h, self.rawT_h, self.O, L, 16 * C, L, B, b_split=C)          # rows of rawT [c][tap] taken as (tap, c): O[p][tap][c]
-            L_.call('hv_ca_fold_h', ptr(self.O), ptr(out.t), out.f16, B, H, W, C, out.ld, ctypes.c_float(0.25), 0, stream())
-        else:
-            ops.conv2d(self.A, self.rawT, out, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=C * 16 * L, precision=prec)
-        if out_user is not None:
-            ops.copy_channels(out, out_user, mode=0)
+            L_.call('hv_ca_softmax', ptr(s.t), ptr(mm), ptr(r.A.t), B, L, ctypes.c_float(self.scale), ptr(self.argmax) if want_argmax else None, stream())
+        paste(self, r, out, prec)
+        self.route, self.last = route, (ops.precision_id(prec), per_sample_mask)
 
     def backward(self, dout, df, accumulate, prec):
-        """dout: Act grad of the output; df: Act grad of the input feature map (assigned or accumulated)."""
-        L_ = _lib.get()
-        B, H, W, C, L = self.B, self.H, self.W, self.C, self.L
-        if self.bw is None:
-            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dout.t.device)
-            self.bw = dict(dA=Act(z(B, self.h, self.w, L)), AT=Act(z(B, self.h, self.w, L)), dOrawT=z(B, C, 16 * L),
-                           dS1=Act(z(B, self.h, self.w, L)), dS0=Act(z(B, self.h, self.w, L)), Gs=Act(z(B, self.h, self.w, L)),
-                           coef=z(33 * B, L), dwp=Act(z(B, self.h, self.w, 9 * C)))
-        bw = self.bw
-        df_user = None
-        gemm = getattr(self, 'gemm', False) and ops.precision_id(prec) == ops.F16
-        if dout.f16 and not gemm:
-            self.dout32 = getattr(self, 'dout32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=dout.t.device))
-            ops.copy_channels(dout, self.dout32, mode=0)
-            dout = self.dout32
-        if df.f16:      # (two kernels add into df: it stays fp32 until both are in, one rounding)
-            self.df32 = getattr(self, 'df32', None) or Act(torch.zeros(B, H, W, C, dtype=torch.float32, device=dout.t.device))
-            df_user, df, df_acc, accumulate = df, self.df32, accumulate, False
-        # through the paste: dA and d(raw patches)
-        if gemm:
-            if 'dOraw_h' not in bw:
-                hz = lambda *s: torch.zeros(*s, dtype=torch.float16, device=dout.t.device)
-                bw['dOraw_h'], bw['dOrawT_h'], bw['AT_h'] = hz(B, L, 16 * C), hz(B, 16 * C, L), hz(B, L, L)
-            L_.call('hv_ca_raw_patches_f16', ptr(dout.t), dout.f16, B, H, W, C, dout.ld, ptr(bw['dOraw_h']), ptr(bw['dOrawT_h']), stream())
-            _bgemm(bw['dOraw_h'], self.raw_h, bw['dA'].t, L, L, 16 * C, B, alpha=0.25)
-            L_.call('hv_transpose_batched_h2h', ptr(self.A_h), ptr(bw['AT_h']), B, L, L, stream())
-            _bgemm(bw['AT_h'], bw['dOrawT_h'], self.O, L, 16 * C, L, B, b_split=C)      # d(raw patches)[l][tap][c] (the forward's O buffer is free by now)
-            L_.call('hv_ca_fold_h', ptr(self.O), ptr(df.t), df.f16, B, H, W, C, df.ld, ctypes.c_float(0.25),
-                    int(bool(accumulate)), stream())
-        else:
-            ops.conv2d(dout, self.raw, bw['dA'], 4, 2, 1, 1, alpha=0.25, w_bstride=L * 16 * C, precision=prec)
-            L_.call('hv_transpose_batched', ptr(self.A.t), ptr(bw['AT'].t), B, L, L, stream())
-            L_.call('hv_ca_raw_patches', ptr(dout.t), B, H, W, C, dout.ld, None, ptr(bw['dOrawT']), stream())
-            ops.conv2d(bw['AT'], bw['dOrawT'], df, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=C * 16 * L,
-                       accumulate=int(accumulate), precision=prec)
-        # through softmax and score fusion
-        if gemm:
-            L_.call('hv_ca_softmax_backward_f16', ptr(bw['dA'].t), ptr(self.A_h), ptr(self.mm), ptr(bw['dS1'].t), B, L, ctypes.c_float(self.scale), stream())
-        else:
-            L_.call('hv_ca_softmax_backward', ptr(bw['dA'].t), ptr(self.A.t), ptr(self.mm), ptr(bw['dS1'].t), B, L, ctypes.c_float(self.scale), stream())
-        # ... and through the normalised patch matching (patches act as both filters and inputs)
-        use_gram = gemm and getattr(self, 'gram', False)
-        if self.fuse and self.h == 32 and self.w == 32:      # one pass, the plain scores' gradient stays on chip
-            L_.call('hv_ca_fuse_backward_prep', ptr(bw['dS1'].t), ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), ptr(bw['Gs'].t), ptr(bw['coef']),
-                    B, self.h, self.w, stream())
+        """dout: Act grad of the output; df: Act grad of the input feature map (assigned or accumulated).  Runs on the route and the tables of the forward
+        before it; refused (nothing launched) without one, in another precision than its, or after a per-sample-mask forward (the soft-max gradient reads mm)."""
+        if self.route is None or self.last != (ops.precision_id(prec), False):
+            raise RuntimeError('AttentionPlan%s: backward(prec=%s) does not follow the last forward: route %s, (precision, per-sample mask) %s' % (self.dims, prec, self.route, self.last))
+        L_, B, L, (paste_grad, score_grad) = _lib.get(), self.B, self.L, self.steps[self.route][3:]
+        r = self.buffers(self.route, 'backward', skip=[n for n, a in (('dout32', dout), ('df32', df)) if not a.f16])
+        self.buffers('shared', 'backward')
+        df_user, df = df, r.df32 if df.f16 else df      # (two kernels add into df: it stays fp32 until both are in, one rounding)
+        paste_grad(self, r, dout, df, accumulate and df is df_user, prec)
+        name, A = ('hv_ca_softmax_backward', r.A.t) if self.route == 'conv' else ('hv_ca_softmax_backward_f16', r.A_h)
+        L_.call(name, ptr(self.dA.t), ptr(A), ptr(self.mm), ptr(self.dS1.t), B, L, ctypes.c_float(self.scale), stream())
+        if self.fused_adjoint:
+            L_.call('hv_ca_fuse_backward_prep', ptr(self.dS1.t), ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), ptr(self.Gs.t), ptr(self.coef), B, self.h, self.w, stream())
         else:
             if self.fuse:
-                L_.call('hv_ca_fuse', ptr(bw['dS1'].t), ptr(bw['dS0'].t), B, self.h, self.w, 1, stream())
-                ds0 = bw['dS0']
-            else:
-                ds0 = bw['dS1']
-            L_.call('hv_ca_score_backward_prep', ptr(ds0.t), ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), ptr(bw['Gs'].t), ptr(bw['coef']), B, L, stream())
-        if use_gram:
-            # d fd = box(Gs) fd + (3x3 sum of coef) fd, added to the even positions of df: one K = L product instead of the L x 9C GEMM + col2im
-            L_.call('hv_ca_gram_backward', ptr(bw['Gs'].t), ptr(self.fd_h), ptr(self.fdT_h), ptr(bw['coef']), B, self.h, self.w, C, ptr(df.t), df.ld, stream())
-        else:
-            if gemm:
-                L_.call('hv_transpose_batched_f16', ptr(self.wp), ptr(self.wpT_h), B, L, 9 * C, stream())      # (the transpose of wp has this one reader)
-                _bgemm(bw['Gs'].t, self.wpT_h, bw['dwp'].t, L, 9 * C, L, B)
-            else:
-                ops.conv2d(bw['Gs'], self.wpT, bw['dwp'], 1, 1, 0, 1, w_bstride=9 * C * L, precision=prec)
-            L_.call('hv_ca_patches_backward', ptr(bw['dwp'].t), ptr(self.wp), ptr(bw['coef']), ptr(df.t), B, H, W, C, df.ld, 1, stream())
-        if df_user is not None:
-            ops.copy_channels(df, df_user, mode=0, accumulate=bool(df_acc))
+                L_.call('hv_ca_fuse', ptr(self.dS1.t), ptr(self.dS0.t), B, self.h, self.w, 1, stream())
+            L_.call('hv_ca_score_backward_prep', ptr((self.dS0 if self.fuse else self.dS1).t), ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), ptr(self.Gs.t), ptr(self.coef), B, L, stream())
+        score_grad(self, r, df, prec)
+        if df is not df_user:
+            ops.copy_channels(df, df_user, mode=0, accumulate=bool(accumulate))
+
+    # ---- the routes' own steps over r, the route's tables (the plan's are the shared ones): patches, scores, paste | paste_grad (dA and d(raw patches)), score_grad
+    def _conv_patches(self, r, f):
+        if f.f16:
+            ops.copy_channels(f, r.f32, mode=0)
+            f = r.f32
+        _lib.get().call('hv_ca_patches', ptr(f.t), f.f16, *self.dims, f.ld, ptr(r.fd.t), ptr(r.wp), ptr(r.wpT), ptr(self.norm), ptr(self.rnorm), stream())
+        _lib.get().call('hv_ca_raw_patches', ptr(f.t), *self.dims, f.ld, ptr(r.raw), ptr(r.rawT), stream())
+
+    def _conv_scores(self, r, prec):
+        ops.conv2d(r.fd, r.wp, self.S0, 3, 1, 1, 1, w_bstride=self.L * 9 * self.C, ch_scale=self.rnorm, ch_scale_bstride=self.L, precision=prec)
+
+    def _conv_paste(self, r, out, prec):
+        ops.conv2d(r.A, r.rawT, r.out32 if out.f16 else out, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=self.C * 16 * self.L, precision=prec)
+        if out.f16:
+            ops.copy_channels(r.out32, out, mode=0)
+
+    def _conv_paste_grad(self, r, dout, df, accumulate, prec):
+        if dout.f16:
+            ops.copy_channels(dout, r.dout32, mode=0)
+            dout = r.dout32
+        ops.conv2d(dout, r.raw, self.dA, 4, 2, 1, 1, alpha=0.25, w_bstride=self.L * 16 * self.C, precision=prec)
+        _lib.get().call('hv_transpose_batched', ptr(r.A.t), ptr(r.AT.t), self.B, self.L, self.L, stream())
+        _lib.get().call('hv_ca_raw_patches', ptr(dout.t), *self.dims, dout.ld, None, ptr(r.dOrawT), stream())
+        ops.conv2d(r.AT, r.dOrawT, df, 4, 2, 1, 1, transposed=True, alpha=0.25, w_bstride=self.C * 16 * self.L, accumulate=int(accumulate), precision=prec)
+
+    def _conv_score_grad(self, r, df, prec):      # through the normalised patch matching (patches act as both filters and inputs)
+        ops.conv2d(self.Gs, r.wpT, r.dwp, 1, 1, 0, 1, w_bstride=9 * self.C * self.L, precision=prec)
+        _lib.get().call('hv_ca_patches_backward', ptr(r.dwp.t), ptr(r.wp), ptr(self.coef), ptr(df.t), *self.dims, df.ld, 1, stream())
+
+    def _gemm_patches(self, r, f):
+        _lib.get().call('hv_ca_patches_h', ptr(f.t), f.f16, *self.dims, f.ld, ptr(r.fd.t), ptr(r.wp), ptr(r.wp_h), ptr(self.norm), ptr(self.rnorm), stream())
+        _lib.get().call('hv_ca_raw_patches_f16', ptr(f.t), f.f16, *self.dims, f.ld, ptr(r.raw_h), ptr(r.rawT_h), stream())
+
+    def _gemm_scores(self, r, prec):      # the 3x3 patches of the (zero-padded) map are both the conv's input columns and its filters: scores = rnorm (.) wp wp^T
+        _bgemm(r.wp_h, r.wp_h, self.S0.t, self.L, self.L, 9 * self.C, self.B, colscale=self.rnorm)
+
+    def _gemm_paste(self, r, out, prec):      # paste = (A rawT^T) folded: O[p][(c, tap)], then every output pixel sums the 4 taps that reach it
+        _bgemm(r.A_h, r.rawT_h, r.O, self.L, 16 * self.C, self.L, self.B, b_split=self.C)          # rows of rawT [c][tap] taken as (tap, c): O[p][tap][c]
+        _lib.get().call('hv_ca_fold_h', ptr(r.O), ptr(out.t), out.f16, *self.dims, out.ld, ctypes.c_float(0.25), 0, stream())
+
+    def _gemm_paste_grad(self, r, dout, df, accumulate, prec):
+        _lib.get().call('hv_ca_raw_patches_f16', ptr(dout.t), dout.f16, *self.dims, dout.ld, ptr(r.dOraw_h), ptr(r.dOrawT_h), stream())
+        _bgemm(r.dOraw_h, r.raw_h, self.dA.t, self.L, self.L, 16 * self.C, self.B, alpha=0.25)
+        _lib.get().call('hv_transpose_batched_h2h', ptr(r.A_h), ptr(r.AT_h), self.B, self.L, self.L, stream())
+        _bgemm(r.AT_h, r.dOrawT_h, r.O, self.L, 16 * self.C, self.L, self.B, b_split=self.C)      # d(raw patches)[l][tap][c] (the forward's O buffer is free by now)
+        _lib.get().call('hv_ca_fold_h', ptr(r.O), ptr(df.t), df.f16, *self.dims, df.ld, ctypes.c_float(0.25), int(bool(accumulate)), stream())
+
+    def _gemm_score_grad(self, r, df, prec):
+        _lib.get().call('hv_transpose_batched_f16', ptr(r.wp), ptr(r.wpT_h), self.B, self.L, 9 * self.C, stream())      # (the transpose of wp has this one reader)
+        _bgemm(self.Gs.t, r.wpT_h, r.dwp.t, self.L, 9 * self.C, self.L, self.B)
+        _lib.get().call('hv_ca_patches_backward', ptr(r.dwp.t), ptr(r.wp), ptr(self.coef), ptr(df.t), *self.dims, df.ld, 1, stream())
+
+    def _gram_patches(self, r, f):
+        _lib.get().call('hv_ca_gram_down', ptr(f.t), f.f16, *self.dims, f.ld, ptr(r.fd_h), ptr(r.fdT_h), ptr(r.q), stream())
+        _lib.get().call('hv_ca_raw_patches_f16', ptr(f.t), f.f16, *self.dims, f.ld, ptr(r.raw_h), ptr(r.rawT_h), stream())
+
+    def _gram_scores(self, r, prec):
+        _lib.get().call('hv_ca_gram_scores', ptr(r.fd_h), ptr(r.q), self.B, self.h, self.w, self.C, ptr(self.S0.t), ptr(self.norm), ptr(self.rnorm), stream())
+
+    def _gram_score_grad(self, r, df, prec):      # d fd = box(Gs) fd + (3x3 sum of coef) fd, added to the even positions of df: one K = L product instead of the L x 9C GEMM + col2im
+        _lib.get().call('hv_ca_gram_backward', ptr(self.Gs.t), ptr(r.fd_h), ptr(r.fdT_h), ptr(self.coef), self.B, self.h, self.w, self.C, ptr(df.t), df.ld, stream())
+
+    steps = dict(conv=(_conv_patches, _conv_scores, _conv_paste, _conv_paste_grad, _conv_score_grad), gemm=(_gemm_patches, _gemm_scores, _gemm_paste, _gemm_paste_grad, _gemm_score_grad),
+                 gram=(_gram_patches, _gram_scores, _gemm_paste, _gemm_paste_grad, _gram_score_grad))

@@ -785,3 +785,124 @@ def test_discriminator_head_normalisation_at_staging_is_bit_identical(norm, grou
     for k in a[3]:
         assert torch.equal(a[3][k], b[3][k]), k
     assert a[0].abs().max().item() > 0 and a[1].abs().max().item() > 0
+
+
+# ---------------------------------------------------------------- AttentionPlan: per-route buffers, one plan serving several routes
+def _attention_run(plan, case, prec, per_sample_mask=False, backward=True):
+    """One forward (+ backward) of `plan` on the case's inputs, stored as fp16 in the fp16 mode and as fp32 in the exact mode -> (out, df) tensors."""
+    from hvgan import ops
+    dt = torch.float16 if prec == 'fp16' else torch.float32
+    out, df = (ops.Act(torch.zeros_like(case['f'], dtype=dt)) for _ in range(2))
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv('HV_PRECISION', prec)
+        plan.forward(ops.Act(case['f'].to(dt)), case['mask'], out, prec, per_sample_mask=per_sample_mask)
+        if backward:
+            plan.backward(ops.Act(case['dout'].to(dt)), df, False, prec)
+    torch.cuda.synchronize()
+    return out.t, df.t
+
+
+@pytest.fixture(scope='module')
+def attention_case():
+    """B = 2, a 64 x 64 x 64 map and a (256, 256) image (the Gram tests' shape) with what a FRESH plan gives for them in the fp16 mode (Gram route) and in the
+    exact-fp32 mode (conv route) -- computed once; the tests below compare bit for bit against these and leave them unchanged."""
+    from hvgan import engine
+    dev = torch.device('cuda:0')
+    B, C, H = 2, 64, 64
+    gen = torch.Generator().manual_seed(31)
+    case = dict(B=B, C=C, H=H, L=(H // 2) ** 2, dev=dev, f=torch.randn(B, H, H, C, generator=gen).half().float().to(dev),
+                dout=(torch.randn(B, H, H, C, generator=gen) * 0.05).half().float().to(dev), mask=torch.zeros(B, 1, 4 * H, 4 * H, device=dev))
+    case['mask'][:, :, 4 * H // 3:4 * H // 3 + 40, :] = 1
+    case['new'] = lambda: engine.AttentionPlan(B, H, H, C, dev, (4 * H, 4 * H))
+    for prec, route in (('fp16', 'gram'), ('fp32', 'conv')):
+        plan = case['new']()
+        case[prec] = _attention_run(plan, case, prec)
+        assert plan.route == route and case[prec][0].abs().max().item() > 0 and case[prec][1].abs().max().item() > 0
+    return case
+
+
+@pytest.mark.parametrize('gram', [True, False])
+def test_attention_plan_holds_only_the_buffers_its_route_reads(gram, monkeypatch, attention_case):
+    """fp16 mode, a fresh plan after one forward + backward: on the Gram route (32 x 32 map: fused adjoint) none of the patch tables, of the conv route's fp32
+    tables or of dS0 exists on it; with CA_GRAM off the 3x3 patch tables do and the conv route's still do not.  Everything the calls allocated is the plan's
+    (memory_allocated grows by at most nbytes() + 1 MiB; inputs and outputs exist beforehand, a throw-away plan has taken the one-time allocations; the measured
+    plan allocates from a memory pool of its own, so that what the caching allocator counts for a table does not depend on the blocks earlier tests left behind), and the
+    Gram route's set stays within 24 B L^2 (five fp32 and two fp16 L x L tables) + 200 C B L bytes (five fp16 [L][16C] tables, fd_h, fdT_h and df32: 180; the
+    vectors and coef: < 20) -- every route's tables allocated at once come to about 36 B L^2 + 530 C B L."""
+    from hvgan import engine, ops
+    c = attention_case
+    B, C, L = c['B'], c['C'], c['L']
+    monkeypatch.setenv('HV_PRECISION', 'fp16')
+    monkeypatch.setattr(engine, 'CA_GRAM', gram)
+    f, dout = ops.Act(c['f'].half()), ops.Act(c['dout'].half())
+    out, df = (ops.Act(torch.zeros_like(f.t)) for _ in range(2))
+
+    def run(plan):
+        plan.forward(f, c['mask'], out, 'fp16')
+        plan.backward(dout, df, False, 'fp16')
+        torch.cuda.synchronize()
+    run(c['new']())
+    pool = torch.cuda.MemPool()      # (memory_allocated counts whole blocks: in the shared pool a table may get a cached block up to 1 MiB larger than it asked for)
+    before = torch.cuda.memory_allocated()
+    with torch.cuda.use_mem_pool(pool):
+        plan = c['new']()
+        run(plan)
+    grown = torch.cuda.memory_allocated() - before
+    held = {n for _, n in plan.owned}
+    print('route %s: nbytes %d, memory_allocated grew by %d, bound %d' % (plan.route, plan.nbytes(), grown, 24 * B * L * L + 200 * C * B * L))
+    assert plan.route == ('gram' if gram else 'gemm') and plan.gemm and plan.gram == gram
+    absent = set('raw rawT A AT dOrawT wpT dS0'.split()) | (set('wp dwp wp_h wpT_h'.split()) if gram else set())
+    assert not held & absent and not any(hasattr(plan, n) or hasattr(plan.sets[plan.route], n) for n in absent), held & absent
+    assert gram or {'wp', 'wp_h', 'wpT_h', 'dwp', 'fd'} <= held
+    assert set(plan.sets) == {plan.route} and 0 < plan.nbytes() and grown <= plan.nbytes() + (1 << 20), (grown, plan.nbytes())
+    if gram:
+        assert plan.nbytes() <= 24 * B * L * L + 200 * C * B * L, plan.nbytes()
+    del plan      # (before its pool)
+
+
+def test_attention_routes_served_by_one_plan_share_no_state(attention_case):
+    """One plan: fp16 mode (Gram route), then fp32 Acts in the exact mode (conv route), then the first call again -- every output and input gradient is bit for
+    bit what a fresh plan gives for that call, so nothing one route wrote is read by the other."""
+    c = attention_case
+    plan = c['new']()
+    first = _attention_run(plan, c, 'fp16')
+    assert plan.route == 'gram'
+    second = _attention_run(plan, c, 'fp32')
+    assert plan.route == 'conv' and set(plan.sets) == {'gram', 'conv'}
+    third = _attention_run(plan, c, 'fp16')
+    for got, want in ((first, c['fp16']), (second, c['fp32']), (third, first)):
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
+@pytest.mark.parametrize('case', ['before_any_forward', 'other_precision', 'after_per_sample_mask'])
+def test_attention_backward_is_refused_unless_it_follows_its_forward(case, attention_case):
+    """backward before any forward, backward(..., 'fp32') after an fp16-mode forward and backward after a per_sample_mask=True forward (its soft-max gradient
+    would read the shared-mask table the forward did not write) raise RuntimeError on the host; the plan then still gives a fresh plan's bits."""
+    from hvgan import ops
+    c = attention_case
+    plan = c['new']()
+    if case != 'before_any_forward':
+        _attention_run(plan, c, 'fp16', per_sample_mask=case == 'after_per_sample_mask', backward=False)
+    prec = 'fp32' if case == 'other_precision' else 'fp16'
+    dout, df = ops.Act(c['dout'].half()), ops.Act(torch.zeros_like(c['dout'], dtype=torch.float16))
+    with pytest.raises(RuntimeError, match='AttentionPlan'):
+        plan.backward(dout, df, False, prec)
+    torch.cuda.synchronize()
+    assert not df.t.any()
+    got = _attention_run(plan, c, 'fp16')
+    assert torch.equal(got[0], c['fp16'][0]) and torch.equal(got[1], c['fp16'][1])
+
+
+def test_attention_plan_refuses_to_allocate_inside_a_stream_capture(attention_case):
+    """A route the plan has not served yet, asked for while the current stream is capturing (a torch.cuda.graph region with nothing else in it): RuntimeError
+    naming the plan and the route -- a Python exception, nothing reaches the device -- and nothing is allocated; eagerly the plan then serves that route."""
+    c = attention_case
+    plan = c['new']()
+    _attention_run(plan, c, 'fp16')
+    held = set(plan.owned)
+    with pytest.raises(RuntimeError, match=r'AttentionPlan\(2, 64, 64, 64\): conv route'):
+        with torch.cuda.graph(torch.cuda.CUDAGraph()):
+            plan.buffers('conv', 'forward')
+    assert set(plan.owned) == held and not torch.cuda.is_current_stream_capturing()
+    got = _attention_run(plan, c, 'fp32')
+    assert plan.route == 'conv' and torch.equal(got[0], c['fp32'][0]) and torch.equal(got[1], c['fp32'][1])
