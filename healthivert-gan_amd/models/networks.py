@@ -145,6 +145,78 @@ CONV_BSTATS = True   # BatchNorm backward sums from the epilogue of the data gra
 HEAD_NORM = True     # (same bits) the last normalisation + LeakyReLU made where the logits layer stages its input (False: a test's reference)
 
 
+class _Stem:
+    """Layer 0 of a PatchGAN plan: conv + LeakyReLU straight off the input image.  The input tensor changes every call, so the node is bound per
+    forward (_DiscPlan.bind_input)."""
+    __slots__ = ('p', 'y', 'node')
+
+    def __init__(self, p, y):
+        self.p, self.y, self.node = p, y, None
+
+
+class _Normed:
+    """conv -> raw map z -> normalisation + LeakyReLU -> y.  Owns what its neighbours' kernels hand it or take from it; each hand-over is asked of the C
+    dispatch once and its buffer is allocated on that first use (a shape's eager warm-up step), never at construction."""
+    __slots__ = ('p', 'node', 'z', 'y', 'stats', 'norm', 'bparts_used', 'head_fused', '_fstats', '_bsums', '_head_ok')
+
+    def __init__(self, p, node, z, y, stats, norm):
+        self.p, self.node, self.z, self.y, self.stats, self.norm = p, node, z, y, stats, norm
+        self.bparts_used = 0          # partial-sum rows the last backward's normalisation took from its consumer's data gradient (0: it reduced itself)
+        self.head_fused = False       # the last forward normalised this layer's output where the logits layer stages it
+        self._fstats = None           # (partials, rows) of the forward statistics epilogue
+        self._bsums = {}              # statistics groups -> (partials, rows) of the backward sums
+        self._head_ok = {}            # statistics groups -> the dispatch serves head_call
+
+    def _partials(self, parts):
+        return torch.zeros(max(1, parts) * self.p.cout * 2, dtype=torch.float32, device=self.z.t.device), parts
+
+    def forward_stats(self, prec):
+        """-> (partials, rows): the BatchNorm statistics leave this conv's own epilogue where its kernel has one (the 4x4 stride-2 layers) and the
+        normalisation skips its reduction pass over z; (None, 0) otherwise.  With statistics groups the partials are per image tile, in image order:
+        the finalize sums each group's share."""
+        if self._fstats is None:
+            self._fstats = self._partials(int(self.node.stats_parts(prec)))
+        return self._fstats if self._fstats[1] else (None, 0)
+
+    def backward_sums(self, consumer, book, prec, mul_x, groups):
+        """-> (partials, rows): the sums of this batch normalisation's backward (sum g, sum g * xhat over the gradient `consumer`'s data gradient writes)
+        leave that launch's epilogue and the normalisation's backward skips its reduction pass over g and z; (None, 0) where that kernel has no such
+        epilogue.  Asked of the plain data gradient conv_backward issues (none when it accumulates -- not a whole sum, never the case in this chain).
+        A buffer per group count: a plan serves the batched fake | real pass (two groups) and a plain pass of the same size, and captured graphs of
+        both uses keep their own addresses."""
+        if groups not in self._bsums:
+            gx = consumer.dx_view(book, 'plain')
+            call = consumer.dx_call(book, prec, 'plain', gx, book.accumulates(gx), mul_x=mul_x, bn=(self.z, self.stats, groups, None))
+            self._bsums[groups] = self._partials(call.bstats_parts())
+        return self._bsums[groups] if self._bsums[groups][1] else (None, 0)
+
+    def head_call(self, head, prec, groups):
+        """-> the logits layer's call that applies this layer's normalisation + LeakyReLU where it stages its input (hv_conv_desc.xn_*; that kernel also
+        stores the normalised map y the backward reads) -- the normalisation call then only finalises the statistics --, or None where the C
+        dispatch has no such kernel (HV_HEAD_NORM=0: always) and the separate pass runs."""
+        nm = self.norm
+        bn = isinstance(nm, nn.BatchNorm2d)
+        xn = (self.stats, nm.weight if bn else None, nm.bias if bn else None, groups if bn else self.z.B, 'lrelu', self.y)
+        call = head.node.forward_call(prec, xn=xn, x_raw=self.z)
+        if groups not in self._head_ok:
+            self._head_ok[groups] = call.supported()
+        return call if self._head_ok[groups] else None
+
+
+class _Logits:
+    """The 1-channel logits layer.  Owns the 4-channel carrier of d loss / d logit its backward starts from."""
+    __slots__ = ('p', 'node', 'y', 'carrier')
+
+    def __init__(self, p, node, y, carrier):
+        self.p, self.node, self.y, self.carrier = p, node, y, carrier
+
+    @property
+    def loss_head_ready(self):
+        """The single-launch loss head (ops.gan_loss_pair) can write the carrier: fp16 storage, four channels."""
+        g = self.carrier
+        return g.f16 and g.t.shape[-1] == 4 and g.coff == 0
+
+
 class _DiscPlan:
     def __init__(self, net, B, H, W, device):
         self.B, self.H, self.W = B, H, W
@@ -158,25 +230,34 @@ class _DiscPlan:
         for li, L in enumerate(net._spec):
             ho, wo = ops.conv_out_size(h, 4, L['stride'], 1, 1), ops.conv_out_size(w, 4, L['stride'], 1, 1)
             p = net._pset_convs[li]
-            ent = dict(spec=L, p=p)
             if li == 0:
-                ent['y'] = z(ho, wo, p.cout)
-                ent['node'] = None     # built per call (input tensor changes)
+                ent = _Stem(p, z(ho, wo, p.cout))
             elif L['last']:
                 self.logits = torch.zeros(B, 1, ho, wo, dtype=torch.float32, device=device)
-                ent['y'] = Act(self.logits.view(B, ho, wo, 1))
-                ent['node'] = E.ConvNode(p, prev, ent['y'], L['stride'], 1, 1, 'none', use_bias=True)
-                self.g_logits = z(ho, wo, 1)
+                y = Act(self.logits.view(B, ho, wo, 1))
+                ent = _Logits(p, E.ConvNode(p, prev, y, L['stride'], 1, 1, 'none', use_bias=True), y, z(ho, wo, 1))
+                self.book.twins[id(y.t)] = ent.carrier.t      # the gradient of the logits lives in the carrier
             else:
-                ent['z'] = z(ho, wo, p.cout)
-                ent['y'] = z(ho, wo, p.cout)
-                ent['stats'] = torch.zeros(2 * B * p.cout, dtype=torch.float32, device=device)
-                ent['node'] = E.ConvNode(p, prev, ent['z'], L['stride'], 1, 1, 'none', use_bias=L['bias'])
-            prev = ent['y']
+                zraw = z(ho, wo, p.cout)
+                ent = _Normed(p, E.ConvNode(p, prev, zraw, L['stride'], 1, 1, 'none', use_bias=L['bias']), zraw, z(ho, wo, p.cout),
+                              torch.zeros(2 * B * p.cout, dtype=torch.float32, device=device), net.model[L['norm']])
+            prev = ent.y
             h, w = ho, wo
             self.layers.append(ent)
         self.dx = torch.zeros(B, 1, H, W, dtype=torch.float32, device=device)
         self.pending = None        # weakref to the autograd token of the nn.Module-API forward that owns these activations
+        self.x_in = None           # the input view of the last forward (bind_input)
+        self.training, self.groups = False, 1      # ... and its mode and statistics groups
+
+    def bind_input(self, x, training, groups):
+        """A forward on x (B,1,H,W) begins: the stem reads it, and its gradient lives in self.dx (the previous input's twin is dropped)."""
+        if self.x_in is not None:
+            self.book.twins.pop(id(self.x_in.t), None)
+        self.x_in = Act(x.view(self.B, self.H, self.W, 1))
+        self.book.twins[id(self.x_in.t)] = self.dx.view(self.B, self.H, self.W, 1)
+        stem = self.layers[0]
+        stem.node = E.ConvNode(stem.p, self.x_in, stem.y, 2, 1, 1, 'lrelu', use_bias=True)
+        self.training, self.groups = training, groups
 
 
 def _stat_momentum(m, order):
@@ -286,81 +367,57 @@ class NLayerDiscriminator(nn.Module):
         P.book.join()   # weight gradients of the previous backward still read this plan's activations on the side stream
         if prep:      # prep='if_stale': skipped when the tables in memory were written from the current weights (the train step: engine.ParamSet.prep)
             self.paramset().prep(x.device, power_iter=False, only_if_stale=(prep == 'if_stale'))
-        xin = Act(x.view(B, H, W, 1))
-        P.x_in = xin
-        head = None       # the logits layer's call when it normalises its input where it stages it
-        for li, ent in enumerate(P.layers):
-            L = ent['spec']
-            if li == 0:
-                ent['node'] = E.ConvNode(ent['p'], xin, ent['y'], L['stride'], 1, 1, 'lrelu', use_bias=True)
-                ent['node'].forward(prec)
-                continue
-            if L['last']:
-                (head or ent['node'].forward_call(prec)).launch()
-                break
-            nm = self.model[L['norm']]
-            # the layer below the logits: its normalisation + LeakyReLU is applied by the logits layer's kernel where it stages its input (hv_conv_desc.xn_*; that
-            # kernel also stores the normalised map the backward reads) -- the normalisation call below then only finalises the statistics.  Asked of the C
-            # dispatch (HV_HEAD_NORM=0: always the separate pass); the answer is recorded under ('head_xn', ...)
-            head = None
-            if HEAD_NORM and P.layers[li + 1]['spec']['last'] and ent['z'].f16:
-                xn = (ent['stats'], nm.weight if self.norm_kind == 'batch' else None, nm.bias if self.norm_kind == 'batch' else None,
-                      groups if self.norm_kind == 'batch' else B, 'lrelu', ent['y'])
-                head = P.layers[li + 1]['node'].forward_call(prec, xn=xn, x_raw=ent['z'])
-                ent[('head_xn', self.norm_kind, groups, prec)] = ok = head.supported()
-                head = head if ok else None
-            # BatchNorm statistics out of the conv's own epilogue where its kernel has one (the 4x4 stride-2 layers): the normalisation then
-            # skips its reduction pass over z
-            parts = 0
-            if self.norm_kind == 'batch' and training:      # (groups > 1: the partials are per image tile, in image order: the finalize sums each group's share)
-                if 'parts' not in ent:
-                    ent['parts'] = int(ent['node'].stats_parts(prec))
-                    ent['partials'] = torch.zeros(max(1, ent['parts']) * ent['p'].cout * 2, dtype=torch.float32, device=x.device)
-                parts = ent['parts']
-            ent['node'].forward(prec, stats=ent['partials'] if parts else None)
-            y_out = None if head is not None else ent['y']
-            if self.norm_kind == 'batch':
-                ops.norm_act_forward(ent['z'], y_out, 'batch', training, ent['stats'], nm.weight, nm.bias, nm.running_mean,
+        P.bind_input(x, training, groups)
+        bn = self.norm_kind == 'batch'
+        head = P.layers[-1]
+        P.layers[0].node.forward(prec)
+        for ent in P.layers[1:-1]:
+            nm = ent.norm
+            fused = ent.head_call(head, prec, groups) if (HEAD_NORM and ent is P.layers[-2] and ent.z.f16) else None      # (the layer below the logits)
+            ent.head_fused = fused is not None
+            partials, parts = ent.forward_stats(prec) if (bn and training) else (None, 0)
+            ent.node.forward(prec, stats=partials)
+            y_out = None if fused is not None else ent.y
+            if bn:
+                ops.norm_act_forward(ent.z, y_out, 'batch', training, ent.stats, nm.weight, nm.bias, nm.running_mean,
                                      nm.running_var, nm.num_batches_tracked, act='lrelu', eps=nm.eps, momentum=_stat_momentum(nm.momentum, stat_order),
-                                     groups=groups, partials=ent['partials'] if parts else None, n_partials=parts)
+                                     groups=groups, partials=partials, n_partials=parts)
             else:
-                ops.norm_act_forward(ent['z'], y_out, 'instance', training, ent['stats'], act='lrelu', eps=nm.eps)
-        P.training, P.groups = training, groups
+                ops.norm_act_forward(ent.z, y_out, 'instance', training, ent.stats, act='lrelu', eps=nm.eps)
+        (fused or head.node.forward_call(prec)).launch()
         return P
 
-    def loss_backward(self, P, target_is_real, mode, loss, grad_weight, need_dx=False, param_grads=True, accumulate=False, loss_weight=1.0, dz=None):
-        """GAN loss on P.logits + backward.  fp16 storage mode: the loss kernel writes d loss / d logit straight into the logits layer's gradient carrier
-        and sums its bias gradient (hv_gan_loss_head) -- the copy, the column-sum pass and its finalize leave the chain between forward and backward."""
-        last = P.layers[-1]
-        if P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
-            pl = last['p']
-            want_db = param_grads and pl.bias is not None and last['node'].use_bias
-            ops.gan_loss_pair(P.logits, target_is_real, loss, Act(P.g_logits.t, 4, 0), mode=mode, loss_weight=loss_weight, grad_weight=grad_weight,
-                              dbias=pl.bias.grad if want_db else None, dbias_accumulate=accumulate)
-            return self.run_backward(P, None, need_dx=need_dx, param_grads=param_grads, accumulate=accumulate, logits_ready=True)
+    def _loss_seed(self, P, ranges, mode, grad_weight, loss_weight=1.0, param_grads=True, accumulate=False, dz=None):
+        """GAN loss of each (rows, target_is_real, loss) range of P.logits -> (dlogits, logits_ready) for run_backward.  fp16 storage mode: ONE loss kernel
+        writes d loss / d logit straight into the logits layer's gradient carrier and sums its bias gradient (hv_gan_loss_head_pair) -- the copy, the
+        column-sum pass and its finalize leave the chain between forward and backward."""
+        head = P.layers[-1]
+        if head.loss_head_ready:
+            want_db = param_grads and head.p.bias is not None and head.node.use_bias
+            args = [a for rows, real, loss in ranges for a in (P.logits[rows], real, loss, Act(head.carrier.t[rows], 4, 0))]
+            ops.gan_loss_pair(*args, mode=mode, loss_weight=loss_weight, grad_weight=grad_weight, dbias=head.p.bias.grad if want_db else None,
+                              dbias_accumulate=accumulate)
+            return None, True
         if dz is None:
             dz = torch.empty_like(P.logits)
-        ops.gan_loss(P.logits, target_is_real, mode, loss=loss, loss_weight=loss_weight, dz=dz, grad_weight=grad_weight)
-        return self.run_backward(P, dz, need_dx=need_dx, param_grads=param_grads, accumulate=accumulate)
+        for rows, real, loss in ranges:
+            ops.gan_loss(P.logits[rows], real, mode, loss=loss, loss_weight=loss_weight, dz=dz[rows], grad_weight=grad_weight)
+        return dz, False
+
+    def loss_backward(self, P, target_is_real, mode, loss, grad_weight, need_dx=False, param_grads=True, accumulate=False, loss_weight=1.0, dz=None,
+                      backward=True):
+        """GAN loss on P.logits + backward (backward=False: the loss value only; the gradient it also writes is read by nobody)."""
+        dz, ready = self._loss_seed(P, [(slice(None), target_is_real, loss)], mode, grad_weight, loss_weight, param_grads, accumulate, dz)
+        if not backward:
+            return None
+        return self.run_backward(P, dz, need_dx=need_dx, param_grads=param_grads, accumulate=accumulate, logits_ready=ready)
 
     def loss_backward_halves(self, P, mode, loss_fake, loss_real, grad_weight, dz=None):
-        """The batched fake | real pass (run_forward(..., groups=2) on [fake; real]): GAN loss of each half against its own target + ONE backward.
-        fp16 storage mode: each half's loss kernel writes its part of the logits layer's gradient carrier and adds its bias gradient
-        (hv_gan_loss_head), as loss_backward does for a whole batch."""
-        last = P.layers[-1]
+        """The batched fake | real pass (run_forward(..., groups=2) on [fake; real]): GAN loss of each half against its own target + ONE backward
+        (fp16 storage mode: both halves in one launch -- four tiny dependent launches between forward and backward -> one)."""
         B = P.B // 2
-        if P.g_logits.f16 and P.g_logits.t.shape[-1] == 4 and P.g_logits.coff == 0:
-            pl = last['p']
-            want_db = pl.bias is not None and last['node'].use_bias
-            # both halves in one launch (four tiny dependent launches between forward and backward -> one)
-            ops.gan_loss_pair(P.logits[:B], False, loss_fake, Act(P.g_logits.t[:B], 4, 0), P.logits[B:], True, loss_real, Act(P.g_logits.t[B:], 4, 0),
-                              mode=mode, grad_weight=grad_weight, dbias=pl.bias.grad if want_db else None)
-            return self.run_backward(P, None, need_dx=False, param_grads=True, accumulate=False, logits_ready=True)
-        if dz is None:
-            dz = torch.empty_like(P.logits)
-        ops.gan_loss(P.logits[:B], False, mode, loss=loss_fake, dz=dz[:B], grad_weight=grad_weight)
-        ops.gan_loss(P.logits[B:], True, mode, loss=loss_real, dz=dz[B:], grad_weight=grad_weight)
-        return self.run_backward(P, dz, need_dx=False, param_grads=True, accumulate=False)
+        dz, ready = self._loss_seed(P, [(slice(0, B), False, loss_fake), (slice(B, None), True, loss_real)], mode, grad_weight, dz=dz)
+        return self.run_backward(P, dz, need_dx=False, param_grads=True, accumulate=False, logits_ready=ready)
 
     def run_backward(self, P, dlogits, need_dx=False, param_grads=True, accumulate=False, logits_ready=False):
         """dlogits: (B,1,Ho,Wo) gradient of the loss wrt the logits.  Fills kernel-layout weight gradients and the
@@ -369,65 +426,39 @@ class NLayerDiscriminator(nn.Module):
         book = P.book
         book.reset()
         B = P.B
-        last = P.layers[-1]
+        stem, head = P.layers[0], P.layers[-1]
         if not logits_ready:      # (loss_backward: the loss kernel already wrote the carrier and the logits layer's bias gradient)
-            ops.copy_channels(Act(dlogits.contiguous().view(B, last['y'].H, last['y'].W, 1)), P.g_logits, mode=0)
-        book.twins[id(last['y'].t)] = P.g_logits.t
-        # the input view changes every call: its gradient always lives in P.dx
-        book.twins.pop(getattr(P, '_in_id', None), None)
-        P._in_id = id(P.x_in.t)
-        book.twins[P._in_id] = P.dx.view(B, P.H, P.W, 1)
-        fuse0 = len(P.layers) > 1 and P.layers[0]['node'].act != 'none' and not P.layers[1]['node'].shift
+            ops.copy_channels(Act(dlogits.contiguous().view(B, head.y.H, head.y.W, 1)), head.carrier, mode=0)
+        bn = self.norm_kind == 'batch'
+        fuse0 = stem.node.act != 'none' and not P.layers[1].node.shift
         # a normalised layer's LeakyReLU' rides in the data-gradient epilogue of the layer that consumes its output z (one consumer), so the
         # normalisation's backward starts from the gradient at ITS output and never reads z
-        for li in range(len(P.layers) - 1, -1, -1):
-            ent = P.layers[li]
-            L, node = ent['spec'], ent['node']
-            prev_normed = li >= 2 and not P.layers[li - 1]['spec']['last'] and not node.shift       # layer li - 1 has a norm + LeakyReLU
-            if li == 0:
-                x4 = None
-                if param_grads:
-                    ops.copy_channels(P.x_in, P.x4, mode=0)
-                node.need_dx = need_dx
-                E.conv_backward(node, book, prec, dbias_accumulate=accumulate, wgrad_accumulate=accumulate, wgrad=param_grads,
-                                x_wg=P.x4 if param_grads else None, premultiplied=fuse0)
-                break
-            if not L['last']:
-                nm = self.model[L['norm']]
-                gy, gz = book.twin(ent['y']), book.twin(ent['z'])
-                bn = self.norm_kind == 'batch'
-                bparts = ent.get('bparts_used', 0)      # the consumer's data gradient (layer li + 1, a moment ago) summed for this normalisation
-                ops.norm_act_backward(gy, ent['y'], ent['z'], gz, self.norm_kind, P.training, ent['stats'],
-                                      gamma=nm.weight if bn else None, act='none',
-                                      dgamma=nm.weight.grad if (bn and param_grads) else None,
+        sums = (None, 0)      # (partials, rows) the data gradient of the layer above summed for this layer's normalisation (_Normed.backward_sums)
+        for li in range(len(P.layers) - 1, 0, -1):
+            ent, below = P.layers[li], P.layers[li - 1]
+            node = ent.node
+            prev_normed = li >= 2 and not node.shift       # layer li - 1 has a norm + LeakyReLU
+            if ent is not head:
+                nm = ent.norm
+                ent.bparts_used = sums[1]
+                ops.norm_act_backward(book.twin(ent.y), ent.y, ent.z, book.twin(ent.z), self.norm_kind, P.training, ent.stats,
+                                      gamma=nm.weight if bn else None, act='none', dgamma=nm.weight.grad if (bn and param_grads) else None,
                                       dbeta=nm.bias.grad if (bn and param_grads) else None, param_accumulate=accumulate,
-                                      groups=P.groups, partials=ent['bpartials'] if bparts else None, n_partials=bparts)
+                                      groups=P.groups, partials=sums[0], n_partials=sums[1])
             # the stem's output has one consumer (layer 1): its LeakyReLU' rides in layer 1's data-gradient epilogue
-            mul_x = P.layers[0]['node'].act if (li == 1 and fuse0) else ('lrelu' if prev_normed else None)
-            # ... and where layer li - 1 is batch-normalised, the sums of ITS backward (sum g, sum g * xhat over the gradient this launch writes) leave
-            # this data gradient's epilogue: the normalisation's backward then skips its reduction pass over g and z (HV_CONV_BSTATS=0: it reduces)
-            bn_arg = None
-            if prev_normed and mul_x and CONV_BSTATS and self.norm_kind == 'batch' and P.training:
-                pe = P.layers[li - 1]
-                bp = pe.setdefault('bparts', {})      # by statistics groups: a plan serves the batched fake | real pass (two groups) and a plain pass of the same size
-                if P.groups not in bp:
-                    # (asked of the plain data gradient conv_backward issues; none when it accumulates -- not a whole sum, never the case in this chain)
-                    gx = node.dx_view(book, 'plain')
-                    bp[P.groups] = node.dx_call(book, prec, 'plain', gx, book.accumulates(gx), mul_x=mul_x, bn=(pe['z'], pe['stats'], P.groups, None)).bstats_parts()
-                    # (a buffer per group count: captured graphs of both uses keep their own addresses)
-                    pe.setdefault('bpartials_by', {})[P.groups] = torch.zeros(max(1, bp[P.groups]) * pe['p'].cout * 2, dtype=torch.float32, device=pe['z'].t.device)
-                if bp[P.groups]:
-                    pe['bpartials'] = pe['bpartials_by'][P.groups]
-                    bn_arg = (pe['z'], pe['stats'], P.groups, pe['bpartials'])
-                pe['bparts_used'] = bp[P.groups] if bn_arg else 0
-            elif prev_normed:
-                P.layers[li - 1]['bparts_used'] = 0
-            E.conv_backward(node, book, prec, dbias_accumulate=accumulate, wgrad_accumulate=accumulate, wgrad=param_grads, dbias_done=bool(logits_ready and L['last']),
-                            mul_x=mul_x, bn=bn_arg)
-        if need_dx:
-            g = book.twin(P.x_in)
-            return g.t.view(B, 1, P.H, P.W)
-        return None
+            mul_x = stem.node.act if (li == 1 and fuse0) else ('lrelu' if prev_normed else None)
+            # ... and where layer li - 1 is batch-normalised, the sums of ITS backward leave this data gradient's epilogue (HV_CONV_BSTATS=0: it reduces)
+            sums = (None, 0)
+            if prev_normed and mul_x and CONV_BSTATS and bn and P.training:
+                sums = below.backward_sums(node, book, prec, mul_x, P.groups)
+            E.conv_backward(node, book, prec, dbias_accumulate=accumulate, wgrad_accumulate=accumulate, wgrad=param_grads, dbias_done=bool(logits_ready and ent is head),
+                            mul_x=mul_x, bn=(below.z, below.stats, P.groups, sums[0]) if sums[1] else None)
+        if param_grads:
+            ops.copy_channels(P.x_in, P.x4, mode=0)
+        stem.node.need_dx = need_dx
+        E.conv_backward(stem.node, book, prec, dbias_accumulate=accumulate, wgrad_accumulate=accumulate, wgrad=param_grads,
+                        x_wg=P.x4 if param_grads else None, premultiplied=fuse0)
+        return book.twin(P.x_in).t.view(B, 1, P.H, P.W) if need_dx else None
 
     def finish(self):
         for P in self._plans.values():

@@ -310,17 +310,11 @@ class Pix2PixModel(BaseModel):
         net = self._D[k][0]
         P = net.run_forward(self._d_images(k)[0], training=True, prep=True)
         dz = self._buf('dz%d' % k, P.logits)
-        if k != 2:   # D_2 sees a thresholded mask: no gradient path to G (reference :201,:324)
-            self._dxs[k] = net.loss_backward(P, True, self.opt.gan_mode, self._loss_slot(15 + k), self.grad_scale / 6.0, need_dx=True, param_grads=False,
-                                             loss_weight=1.0 / 6.0, dz=dz)
-        else:
-            # (only the loss value is wanted; in the fp16 mode the single-launch head serves it -- its gradient goes to the plan's carrier, which nothing reads)
-            g = P.g_logits
-            if g.f16 and g.t.shape[-1] == 4 and g.coff == 0:
-                ops.gan_loss_pair(P.logits, True, self._loss_slot(15 + k), ops.Act(g.t, 4, 0), mode=self.opt.gan_mode, loss_weight=1.0 / 6.0,
-                                  grad_weight=self.grad_scale / 6.0)
-            else:
-                ops.gan_loss(P.logits, True, self.opt.gan_mode, loss=self._loss_slot(15 + k), loss_weight=1.0 / 6.0, dz=dz, grad_weight=self.grad_scale / 6.0)
+        # D_2 sees a thresholded mask: no gradient path to G (reference :201,:324) -- only its loss value is wanted
+        dx = net.loss_backward(P, True, self.opt.gan_mode, self._loss_slot(15 + k), self.grad_scale / 6.0, need_dx=True, param_grads=False,
+                               loss_weight=1.0 / 6.0, dz=dz, backward=k != 2)
+        if k != 2:
+            self._dxs[k] = dx
 
     def backward_G(self, d_done=False):
         L = _lib.get()

@@ -512,7 +512,7 @@ def test_batchnorm_backward_sums_from_the_data_gradient_epilogue(groups, monkeyp
         dx = net.run_backward(P, dz, need_dx=True, param_grads=True)
         net.finish()
         torch.cuda.synchronize()
-        used = [ent.get('bparts_used', 0) for ent in P.layers[1:-1]]
+        used = [ent.bparts_used for ent in P.layers[1:-1]]
         assert all(u > 0 for u in used) if on else not any(used), (on, used)
         res[on] = ({k: p.grad.detach().clone() for k, p in net.named_parameters()}, dx.detach().clone())
     for k in res[True][0]:
@@ -526,7 +526,7 @@ def test_batchnorm_backward_sums_from_the_data_gradient_epilogue(groups, monkeyp
     dx2 = net.run_backward(P, torch.ones_like(P.logits), need_dx=True, param_grads=True)
     net.finish()
     torch.cuda.synchronize()
-    assert all(ent.get('bparts_used', 0) > 0 for ent in P.layers[1:-1]) and torch.isfinite(dx2).all()
+    assert all(ent.bparts_used > 0 for ent in P.layers[1:-1]) and torch.isfinite(dx2).all()
 
 
 @pytest.mark.parametrize('size', [64, 128])
@@ -769,7 +769,7 @@ def test_discriminator_head_normalisation_at_staging_is_bit_identical(norm, grou
         net.cuda().train()
         net.precision = 'fp16'
         P = net.run_forward(x, training=True, groups=groups)
-        used = any(k[0] == 'head_xn' and v for ent in P.layers for k, v in ent.items() if isinstance(k, tuple))
+        used = any(ent.head_fused for ent in P.layers[1:-1])
         assert used == on
         loss = torch.zeros((), device=dev)
         dz = torch.empty_like(P.logits)
@@ -785,6 +785,101 @@ def test_discriminator_head_normalisation_at_staging_is_bit_identical(norm, grou
     for k in a[3]:
         assert torch.equal(a[3][k], b[3][k]), k
     assert a[0].abs().max().item() > 0 and a[1].abs().max().item() > 0
+
+
+# ---------------------------------------------------------------- PatchGAN plan: one owner per layer, one plan serving both statistics-group counts
+def _disc_net(sd, ndf, norm):
+    from hvgan.models import networks
+    net = networks.define_D(1, ndf, 'basic', 3, norm, 'normal', 0.02, [])
+    net.load_state_dict(sd)
+    net.cuda().train()
+    net.precision = 'fp16'
+    return net
+
+
+def _disc_call(net, x, groups, sd=None):
+    """One training forward + backward of the explicit executor -> (plan, [logits, dx, parameter gradients, state dict afterwards])."""
+    if sd is not None:
+        net.load_state_dict(sd)
+    P = net.run_forward(x, training=True, groups=groups)
+    dz = torch.randn(P.logits.shape, generator=torch.Generator().manual_seed(5)).to(x.device) * 64.0
+    dx = net.run_backward(P, dz, need_dx=True, param_grads=True)
+    net.finish()
+    torch.cuda.synchronize()
+    return P, [P.logits.clone(), dx.clone(), {k: p.grad.clone() for k, p in net.named_parameters()}, {k: v.clone() for k, v in net.state_dict().items()}]
+
+
+def _assert_same_bits(got, want, what):
+    assert torch.isfinite(got[1]).all() and got[0].abs().max().item() > 0 and got[1].abs().max().item() > 0, what
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), what
+    for part in (2, 3):
+        for k in want[part]:
+            assert torch.equal(got[part][k], want[part][k]), (what, k)
+
+
+@pytest.fixture(scope='module')
+def disc_case():
+    """ndf 64 (the 128 / 256 / 512-channel kernels with the statistics and backward-sum epilogues), B = 4 at 72 x 56 (partial tiles in both 4x4 kernels): the
+    state dict, the input and what a freshly constructed network gives for one call with each statistics-group count."""
+    from hvgan.models import networks
+    torch.manual_seed(3)
+    sd = {k: v.clone() for k, v in networks.define_D(1, 64, 'basic', 3, 'batch', 'normal', 0.02, []).state_dict().items()}
+    x = torch.randn(4, 1, 72, 56, generator=torch.Generator().manual_seed(4)).cuda()
+    return dict(sd=sd, x=x, fresh={g: _disc_call(_disc_net(sd, 64, 'batch'), x, g)[1] for g in (1, 2)})
+
+
+def test_one_discriminator_plan_serves_both_group_counts_without_shared_state(disc_case):
+    """fp16 mode: forward + backward with two statistics groups, then one, then two again on ONE plan (the batched fake | real pass and a plain pass of equal
+    size share a plan in the train step), the same state dict reloaded before each: logits, input gradient, every parameter gradient and the running
+    statistics of each call are bit for bit those of a freshly constructed network's single call."""
+    net = _disc_net(disc_case['sd'], 64, 'batch')
+    plans = set()
+    for i, groups in enumerate((2, 1, 2)):
+        P, got = _disc_call(net, disc_case['x'], groups, sd=disc_case['sd'])
+        plans.add(id(P))
+        _assert_same_bits(got, disc_case['fresh'][groups], (i, groups))
+    assert len(plans) == 1
+
+
+def test_one_instance_norm_discriminator_plan_repeats_its_first_call_bit_for_bit():
+    """fp16 mode, instance normalisation (ndf 16, 64 x 64: the head-normalisation test's shape; no backward-sum epilogue): the second call on a plan -- which takes
+    the remembered answer on the fused head normalisation -- gives the bits of a freshly constructed network's single call."""
+    from hvgan.models import networks
+    torch.manual_seed(3)
+    sd = {k: v.clone() for k, v in networks.define_D(1, 16, 'basic', 3, 'instance', 'normal', 0.02, []).state_dict().items()}
+    x = torch.randn(4, 1, 64, 64, generator=torch.Generator().manual_seed(4)).cuda()
+    fresh = _disc_call(_disc_net(sd, 16, 'instance'), x, 1)[1]
+    net = _disc_net(sd, 16, 'instance')
+    for i in range(2):
+        _assert_same_bits(_disc_call(net, x, 1, sd=sd)[1], fresh, i)
+
+
+def test_rebinding_the_discriminator_input_leaves_nothing_behind(disc_case):
+    """Three forwards + backwards on one plan, each on a newly allocated input (all kept alive): the gradient book holds as many twins after the third as
+    after the first, and the third call's input gradient is bit for bit a fresh network's."""
+    net = _disc_net(disc_case['sd'], 64, 'batch')
+    xs = [torch.randn(4, 1, 72, 56, generator=torch.Generator().manual_seed(10 + i)).cuda() for i in range(3)]
+    twins = []
+    for x in xs:
+        P, got = _disc_call(net, x, 1)
+        twins.append(len(P.book.twins))
+    assert twins[2] == twins[0], twins
+    want = _disc_call(_disc_net(disc_case['sd'], 64, 'batch'), xs[2], 1)[1]
+    assert torch.equal(got[1], want[1]) and got[1].abs().max().item() > 0
+
+
+def test_discriminator_plan_layers_are_closed(disc_case):
+    """Every attribute of a plan's layer has its value from construction on, and a layer can hold no other: a training forward + backward with each
+    statistics-group count cannot have added one."""
+    net = _disc_net(disc_case['sd'], 64, 'batch')
+    P = net._plan(4, 72, 56, disc_case['x'].device)
+    assert all(hasattr(ent, a) for ent in P.layers for a in type(ent).__slots__)
+    for groups in (2, 1):
+        assert _disc_call(net, disc_case['x'], groups)[0] is P
+    for ent in P.layers:
+        assert not hasattr(ent, '__dict__'), type(ent).__name__
+        with pytest.raises(AttributeError):
+            ent.undeclared = 0
 
 
 # ---------------------------------------------------------------- AttentionPlan: per-route buffers, one plan serving several routes
