@@ -1,26 +1,55 @@
-// Relative height loss value (RHLV) of a generated vs the original vertebra label volume, on the device
-// (reference evaluation/RHLV_quantification.py:41-147 and the per-vertebra body of process_datasets_to_excel :160-178).
+// Relative height loss value (RHLV) of a generated vs the original vertebra label volume, on the device, in the sagittal view
+// (reference evaluation/RHLV_quantification.py:41-147 and the per-vertebra body of process_datasets_to_excel :160-178), the coronal view
+// (evaluation/RHLV_quantification_coronal.py, same lines) or both from one pass over the volumes (the six features of SVM_grading_2.5d.py).
 //
-// Integer / HBM-byte work: both volumes are read once (column counts per z-slice), everything after that is a few KB.
-//   rhlv_counts_kernel   grid (Z, 2): cnt[v][z][w] = #{h : vol_v[h][w][z] == label_index}, tot[v][z]   (lanes along w; a z-fastest
+// Integer / HBM-byte work: both volumes are read once into the column-count table both views start from, everything after that is a few KB.
+//   rhlv_counts_kernel   grid (Z, 2, N): cnt[v][z][w] = #{h : vol_v[h][w][z] == label_index}, tot[v][z]   (lanes along w; a z-fastest
 //                        variant with lanes along z serves the reference's [H][W][Z] arrays)
-//   rhlv_range_kernel    <<<1,256>>>: z-extent of the original vertebra -> centre, half-length -> [lo, hi) (numpy slice rules)
-//   rhlv_slice_kernel    grid (Z): thirds of the generated vertebra's column extent, centre columns, rescale ratios,
+//   rhlv_tot_kernel      grid (S, 2, N): voxels per slice of one view from the table (coronal: slice w = sum over z; sagittal after the z-fastest counts)
+//   rhlv_range_kernel    grid (1, views, N): slice extent of the original vertebra -> centre, half-length -> [lo, hi) (numpy slice rules)
+//   rhlv_slice_kernel    grid (S, views, N): thirds of the generated vertebra's column extent, centre columns, rescale ratios,
 //                        thresholded integer sums per (all | pre | mid | post) x (generated | original)
-//   rhlv_final_kernel    <<<1,64>>>: means over the slices, the four RHLVs and the relative height of the original
+//   rhlv_final_kernel    grid (1, views, N): means over the slices, the four RHLVs and the relative height of the original
+// A view (RhlvView) is a way to walk the one table: the sagittal view takes slices z with columns w, the coronal view slices w with columns z
+// (read strided: the table is at most 2*Z*W ints), and each carries its script's ratio arithmetic.  N > 1 is the batched form: blockIdx.z
+// picks the volume pair and its slab of the workspace.
 // All floating-point steps are doubles in the reference's operation order (-ffp-contract=off); the only deviation is that a
 // slice's selected heights are summed as integers and scaled once (sum(c)*r instead of sum(c*r)): ~1e-16 relative.
 #include "hv_common.h"
 
-struct RhlvRec { double ratio[4]; long long Sf[4], nf[4], Sl[4], nl[4]; };
+struct RhlvRec { double ratio[4]; long long Sf[4], nf[4], Sl[4], nl[4], raises; };
+
+struct RhlvView {
+    int S, C;                  // slices, columns per slice
+    int ss, sc;                // element strides of a slice / a column in one volume's table cnt[Z][W]
+    int coronal;               // the coronal script's ratios (no epsilon) and its max() of an empty third
+    int divisor, lo, hi;       // lo == INT_MIN: [lo, hi) from the original vertebra's extent and length_divisor
+    double thr;
+    long long tot, params, recs;   // byte offsets into a pair's workspace slab: tot[2][S], params[8], recs[S]
+};
+struct RhlvPlan {
+    RhlvView view[2];
+    int nviews, W, Z;
+    long long cnt, pair_bytes;     // byte offset of cnt[2][Z][W]; size of one pair's slab
+};
+
+__device__ __forceinline__ char* rhlv_slab(char* ws, const RhlvPlan& P) { return ws + (long long)blockIdx.z * P.pair_bytes; }
+// volume v (0 generated, 1 original) of pair blockIdx.z: from the device table of pointer pairs, or the single pair passed by value
+template <typename T>
+__device__ __forceinline__ const T* rhlv_volume_ptr(const T* fake, const T* label, const void* const* pairs, int v) {
+    return pairs ? (const T*)pairs[2 * (long long)blockIdx.z + v] : (v == 0 ? fake : label);
+}
 
 template <typename T>
-__global__ __launch_bounds__(256) void rhlv_counts_kernel(const T* __restrict__ fake, const T* __restrict__ label, long long sh, long long sw,
-                                                          long long sz, int H, int W, float label_index, int* __restrict__ cnt,
-                                                          int* __restrict__ tot) {
+__global__ __launch_bounds__(256) void rhlv_counts_kernel(const T* __restrict__ fake, const T* __restrict__ label, const void* const* __restrict__ pairs,
+                                                          const float* __restrict__ label_indices, long long sh, long long sw, long long sz, int H,
+                                                          float label_index, char* __restrict__ ws, RhlvPlan P) {
     __shared__ int red[256];
-    const int z = blockIdx.x, v = blockIdx.y, Z = gridDim.x;
-    const T* vol = v == 0 ? fake : label;
+    const int z = blockIdx.x, v = blockIdx.y, Z = P.Z, W = P.W;
+    const T* vol = rhlv_volume_ptr(fake, label, pairs, v);
+    if (label_indices) label_index = label_indices[blockIdx.z];
+    int* cnt = (int*)(rhlv_slab(ws, P) + P.cnt);
+    int* tot = (int*)(rhlv_slab(ws, P) + P.view[0].tot);       // view[0] is the sagittal one whenever it is asked for
     int mine = 0;
     for (int w = threadIdx.x; w < W; w += 256) {
         int c = 0;
@@ -32,6 +61,7 @@ __global__ __launch_bounds__(256) void rhlv_counts_kernel(const T* __restrict__ 
         cnt[((long long)v * Z + z) * W + w] = c;
         mine += c;
     }
+    if (P.view[0].coronal) return;                              // coronal only: its totals come from rhlv_tot_kernel
     red[threadIdx.x] = mine;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -42,14 +72,19 @@ __global__ __launch_bounds__(256) void rhlv_counts_kernel(const T* __restrict__ 
 }
 
 // the same for volumes whose z index is the fastest-varying one in memory (the reference's [H][W][Z] arrays): a lane owns one (w, z)
-// column and walks h, 64 consecutive lanes read 64 consecutive z -- coalesced.  grid (ceil(W*Z/256), 2); tot by rhlv_tot_kernel.
+// column and walks h, 64 consecutive lanes read 64 consecutive z -- coalesced.  grid (ceil(W*Z/256), 2, N); tot by rhlv_tot_kernel.
 template <typename T>
-__global__ __launch_bounds__(256) void rhlv_counts_zfast_kernel(const T* __restrict__ fake, const T* __restrict__ label, long long sh, long long sw,
-                                                                long long sz, int H, int W, int Z, float label_index, int* __restrict__ cnt) {
+__global__ __launch_bounds__(256) void rhlv_counts_zfast_kernel(const T* __restrict__ fake, const T* __restrict__ label,
+                                                                const void* const* __restrict__ pairs, const float* __restrict__ label_indices,
+                                                                long long sh, long long sw, long long sz, int H, float label_index,
+                                                                char* __restrict__ ws, RhlvPlan P) {
+    const int Z = P.Z, W = P.W;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)W * Z) return;
     const int v = blockIdx.y, w = (int)(i / Z), z = (int)(i - (long long)w * Z);
-    const T* p = (v == 0 ? fake : label) + (long long)w * sw + (long long)z * sz;
+    const T* p = rhlv_volume_ptr(fake, label, pairs, v) + (long long)w * sw + (long long)z * sz;
+    if (label_indices) label_index = label_indices[blockIdx.z];
+    int* cnt = (int*)(rhlv_slab(ws, P) + P.cnt);
     int c = 0;
     for (int h = 0; h < H; ++h) {
         const float val = (float)p[(long long)h * sh];
@@ -57,25 +92,33 @@ __global__ __launch_bounds__(256) void rhlv_counts_zfast_kernel(const T* __restr
     }
     cnt[((long long)v * Z + z) * W + w] = c;
 }
-__global__ __launch_bounds__(256) void rhlv_tot_kernel(const int* __restrict__ cnt, int W, int* __restrict__ tot) {
+// tot[v][s] of view `vi`: the table summed over the view's columns.  grid (S, 2, N)
+__global__ __launch_bounds__(256) void rhlv_tot_kernel(char* __restrict__ ws, RhlvPlan P, int vi) {
     __shared__ int red[256];
-    const int z = blockIdx.x, v = blockIdx.y, Z = gridDim.x;
+    const RhlvView& V = P.view[vi];
+    const int s = blockIdx.x, v = blockIdx.y;
+    const int* cv = (const int*)(rhlv_slab(ws, P) + P.cnt) + (long long)v * P.Z * P.W + (long long)s * V.ss;
+    int* tot = (int*)(rhlv_slab(ws, P) + V.tot);
     int mine = 0;
-    for (int w = threadIdx.x; w < W; w += 256) mine += cnt[((long long)v * Z + z) * W + w];
+    for (int c = threadIdx.x; c < V.C; c += 256) mine += cv[(long long)c * V.sc];
     red[threadIdx.x] = mine;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) tot[v * Z + z] = red[0];
+    if (threadIdx.x == 0) tot[v * V.S + s] = red[0];
 }
 
-// params: [0] lo, [1] hi, [2] center_z, [3] length, [4] valid (label has voxels)
-__global__ void rhlv_range_kernel(const int* __restrict__ tot, int Z, int length_divisor, int z_lo, int z_hi, int* __restrict__ params) {
+// params: [0] lo, [1] hi, [2] centre slice, [3] length, [4] valid (label has voxels)
+__global__ void rhlv_range_kernel(char* __restrict__ ws, RhlvPlan P) {
     if (threadIdx.x != 0) return;
+    const RhlvView& V = P.view[blockIdx.y];
+    const int* tot = (const int*)(rhlv_slab(ws, P) + V.tot);
+    int* params = (int*)(rhlv_slab(ws, P) + V.params);
+    const int Z = V.S;
     int lo, hi, cz = 0, len = 0, valid = 1;
-    if (z_lo == INT_MIN) {
+    if (V.lo == INT_MIN) {
         long long n = 0, sz = 0;
         int mn = Z, mx = -1;
         for (int z = 0; z < Z; ++z) {
@@ -85,10 +128,10 @@ __global__ void rhlv_range_kernel(const int* __restrict__ tot, int Z, int length
         if (n == 0) { valid = 0; lo = hi = 0; }
         else {
             cz = (int)((double)sz / (double)n);          // int(np.mean(loc))
-            len = (mx - mn) / length_divisor;           // (max_z - min_z) // length_divisor
+            len = (mx - mn) / V.divisor;                // (max_z - min_z) // length_divisor
             lo = cz - len; hi = cz + len;
         }
-    } else { lo = z_lo; hi = z_hi; cz = (z_lo + z_hi) / 2; len = (z_hi - z_lo) / 2; }
+    } else { lo = V.lo; hi = V.hi; cz = (V.lo + V.hi) / 2; len = (V.hi - V.lo) / 2; }
     // numpy slice normalisation of [lo:hi] on an axis of length Z
     if (lo < 0) lo = max(lo + Z, 0);
     if (hi < 0) hi = max(hi + Z, 0);
@@ -117,25 +160,30 @@ __device__ __forceinline__ int rhlv_block_max(int v, long long* sh) {
     return (int)sh[0];
 }
 
-__global__ __launch_bounds__(256) void rhlv_slice_kernel(const int* __restrict__ cnt, const int* __restrict__ tot, const int* __restrict__ params,
-                                                         int W, double thr, RhlvRec* __restrict__ recs) {
+__global__ __launch_bounds__(256) void rhlv_slice_kernel(char* __restrict__ ws, RhlvPlan P) {
     __shared__ long long sh[256];
-    const int z = blockIdx.x, Z = gridDim.x, tid = threadIdx.x;
-    RhlvRec* rec = recs + z;
-    const int* cf = cnt + (long long)z * W;
-    const int* cl = cnt + ((long long)Z + z) * W;
+    const RhlvView& V = P.view[blockIdx.y];
+    const int z = blockIdx.x, Z = V.S, W = V.C, tid = threadIdx.x;
+    if (z >= Z) return;                                  // the grid is as wide as the longer view
+    const long long sc = V.sc;
+    const int* tot = (const int*)(rhlv_slab(ws, P) + V.tot);
+    const int* params = (const int*)(rhlv_slab(ws, P) + V.params);
+    RhlvRec* rec = (RhlvRec*)(rhlv_slab(ws, P) + V.recs) + z;
+    const int* cf = (const int*)(rhlv_slab(ws, P) + P.cnt) + (long long)z * V.ss;     // column w of this slice: cf[w * sc]
+    const int* cl = cf + (long long)P.Z * P.W;
     const bool on = z >= params[0] && z < params[1] && tot[z] > 0 && tot[Z + z] > 0 && params[4];
     if (!on) {
         if (tid < 4) { rec->ratio[tid] = 1.0; rec->Sf[tid] = rec->nf[tid] = rec->Sl[tid] = rec->nl[tid] = 0; }
+        if (tid == 0) rec->raises = 0;
         return;
     }
     // column statistics of the generated and the original vertebra
     int ymin = W, ymax = -1;
     long long swf = 0, swl = 0;
     for (int w = tid; w < W; w += 256) {
-        if (cf[w] > 0) { ymin = min(ymin, w); ymax = max(ymax, w); }
-        swf += (long long)cf[w] * w;
-        swl += (long long)cl[w] * w;
+        if (cf[w * sc] > 0) { ymin = min(ymin, w); ymax = max(ymax, w); }
+        swf += (long long)cf[w * sc] * w;
+        swl += (long long)cl[w * sc] * w;
     }
     ymax = rhlv_block_max(ymax, sh);
     ymin = -rhlv_block_max(-ymin, sh);
@@ -146,45 +194,59 @@ __global__ __launch_bounds__(256) void rhlv_slice_kernel(const int* __restrict__
     const int t2 = (int)((double)ymin + (double)(2 * y_range) / 3.0);      // int(y_min + 2*y_range/3)
     const int ccf = (int)((double)swf / (double)tot[z]);                   // int(np.mean(loc))
     const int ccl = (int)((double)swl / (double)tot[Z + z]);
-    const int center_f_i = cf[ccf], center_l = cl[ccl];
+    const int center_f_i = cf[ccf * sc], center_l = cl[ccl * sc];
     const int r0[4] = {0, 0, t1, t2}, r1[4] = {W, t1, t2, W};
     double ratio[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         int mf = -1, ml = -1;
-        for (int w = r0[c] + tid; w < r1[c]; w += 256) { mf = max(mf, cf[w]); ml = max(ml, cl[w]); }
+        for (int w = r0[c] + tid; w < r1[c]; w += 256) { mf = max(mf, cf[w * sc]); ml = max(ml, cl[w * sc]); }
         mf = rhlv_block_max(mf, sh);
         ml = rhlv_block_max(ml, sh);
-        ratio[c] = (r1[c] > r0[c] && ml > mf) ? (double)ml / ((double)mf + 1e-6) : 1.0;
+        // sagittal: label.max() / (fake.max() + 1e-6) behind .size > 0 guards; coronal: label.max() / fake.max(), inf where a third of the
+        // generated vertebra is empty (0 * inf = nan then selects nothing below)
+        const double den = V.coronal ? (double)mf : (double)mf + 1e-6;
+        ratio[c] = (r1[c] > r0[c] && ml > mf) ? (double)ml / den : 1.0;
     }
+    // the coronal script takes max() of the pre and mid thirds unguarded: an empty one (the post third never is) raises ValueError
+    const long long raises = V.coronal && (t1 <= 0 || t2 <= t1);
     const double center_f = (double)center_f_i * ratio[0];
-    const double thr_f = center_f * thr, thr_l = (double)center_l * thr;
+    const double thr_f = center_f * V.thr, thr_l = (double)center_l * V.thr;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         long long Sf = 0, nf = 0, Sl = 0, nl = 0;
         for (int w = r0[c] + tid; w < r1[c]; w += 256) {
-            if ((double)cf[w] * ratio[c] > thr_f) { Sf += cf[w]; ++nf; }
-            if ((double)cl[w] > thr_l) { Sl += cl[w]; ++nl; }
+            if ((double)cf[w * sc] * ratio[c] > thr_f) { Sf += cf[w * sc]; ++nf; }
+            if ((double)cl[w * sc] > thr_l) { Sl += cl[w * sc]; ++nl; }
         }
         Sf = rhlv_block_sum(Sf, sh); nf = rhlv_block_sum(nf, sh);
         Sl = rhlv_block_sum(Sl, sh); nl = rhlv_block_sum(nl, sh);
         if (tid == 0) { rec->ratio[c] = ratio[c]; rec->Sf[c] = Sf; rec->nf[c] = nf; rec->Sl[c] = Sl; rec->nl[c] = nl; }
     }
+    if (tid == 0) rec->raises = raises;
 }
 
 // out[0..4] = all, pre, mid, post RHLV, relative height of the original; out[5..12] = the eight mean heights
-// (all_f, all_l, pre_f, pre_l, mid_f, mid_l, post_f, post_l); out[13] = 1 if the original vertebra exists, else 0
-__global__ void rhlv_final_kernel(const RhlvRec* __restrict__ recs, const int* __restrict__ params, int Z, double* __restrict__ out) {
+// (all_f, all_l, pre_f, pre_l, mid_f, mid_l, post_f, post_l); out[13] = 1 if the original vertebra exists, else 0;
+// 16-double records: out[14] = 1 if the reference would have raised (coronal view), out[15] = 0
+__global__ void rhlv_final_kernel(char* __restrict__ ws, RhlvPlan P, double* __restrict__ out, int out_len) {
     if (threadIdx.x != 0) return;
+    const RhlvView& V = P.view[blockIdx.y];
+    const RhlvRec* recs = (const RhlvRec*)(rhlv_slab(ws, P) + V.recs);
+    const int* params = (const int*)(rhlv_slab(ws, P) + V.params);
+    const int Z = V.S;
+    out += ((long long)blockIdx.z * P.nviews + blockIdx.y) * out_len;
     double m[8];
+    long long raises = 0;
     for (int c = 0; c < 4; ++c) {
         double sf = 0.0, sl = 0.0;
         long long nf = 0, nl = 0;
         for (int z = 0; z < Z; ++z) {
-            sf += (double)recs[z].Sf[c] * recs[z].ratio[c];
+            if (recs[z].nf[c] > 0) sf += (double)recs[z].Sf[c] * recs[z].ratio[c];      // nothing selected: nothing added (the ratio may be inf)
             sl += (double)recs[z].Sl[c];
             nf += recs[z].nf[c];
             nl += recs[z].nl[c];
+            raises |= recs[z].raises;
         }
         m[2 * c] = nf > 0 ? sf / (double)nf : 0.0;
         m[2 * c + 1] = nl > 0 ? sl / (double)nl : 0.0;
@@ -194,11 +256,76 @@ __global__ void rhlv_final_kernel(const RhlvRec* __restrict__ recs, const int* _
     out[4] = mn / (mx + 1e-6);
     for (int i = 0; i < 8; ++i) out[5 + i] = m[i];
     out[13] = (double)params[4];
+    if (out_len > 14) { out[14] = (double)raises; out[15] = 0.0; }
+}
+
+// One pair's workspace slab: recs per view | cnt[2][Z][W] | tot[2][S] per view | params[8] per view; view[0] is the sagittal one when asked for
+static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal, const hv_rhlv_view* coronal) {
+    RhlvPlan P = {};
+    P.W = W; P.Z = Z;
+    if (views & HV_RHLV_SAGITTAL) { RhlvView& V = P.view[P.nviews++]; V.S = Z; V.C = W; V.ss = W; V.sc = 1; V.coronal = 0; }
+    if (views & HV_RHLV_CORONAL) { RhlvView& V = P.view[P.nviews++]; V.S = W; V.C = Z; V.ss = 1; V.sc = W; V.coronal = 1; }
+    long long off = 0;
+    for (int i = 0; i < P.nviews; ++i) { P.view[i].recs = off; off += (long long)P.view[i].S * sizeof(RhlvRec); }
+    P.cnt = off; off += (long long)2 * Z * W * sizeof(int);
+    for (int i = 0; i < P.nviews; ++i) { P.view[i].tot = off; off += (long long)2 * P.view[i].S * sizeof(int); }
+    for (int i = 0; i < P.nviews; ++i) {
+        RhlvView& V = P.view[i];
+        V.params = off; off += 8 * sizeof(int);
+        const hv_rhlv_view* a = V.coronal ? coronal : sagittal;
+        if (a) { V.divisor = a->length_divisor; V.lo = a->lo; V.hi = a->hi; V.thr = a->height_threshold; }
+    }
+    P.pair_bytes = (off + 7) & ~7LL;
+    return P;
+}
+
+// the launch sequence of every entry: one pair passed by value (pairs == NULL, n_pairs 1) or a device table of n_pairs pointer pairs
+static int rhlv_run(const void* fake, const void* label, const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h,
+                    long long stride_w, long long stride_z, int H, float label_index, const RhlvPlan& P, double* out, int out_len, void* workspace,
+                    hipStream_t s) {
+    char* ws = (char*)workspace;
+    const void* const* pp = (const void* const*)pairs;
+    const bool zfast = stride_z == 1 && stride_w != 1;   // z fastest in memory: lanes along z
+    const dim3 grid = zfast ? dim3(hv_cdiv((long long)P.W * P.Z, 256), 2, n_pairs) : dim3(P.Z, 2, n_pairs);
+    if (zfast && dtype == 0)
+        hipLaunchKernelGGL((rhlv_counts_zfast_kernel<float>), grid, dim3(256), 0, s, (const float*)fake, (const float*)label, pp, label_indices, stride_h,
+                           stride_w, stride_z, H, label_index, ws, P);
+    else if (zfast)
+        hipLaunchKernelGGL((rhlv_counts_zfast_kernel<unsigned char>), grid, dim3(256), 0, s, (const unsigned char*)fake, (const unsigned char*)label, pp,
+                           label_indices, stride_h, stride_w, stride_z, H, label_index, ws, P);
+    else if (dtype == 0)
+        hipLaunchKernelGGL((rhlv_counts_kernel<float>), grid, dim3(256), 0, s, (const float*)fake, (const float*)label, pp, label_indices, stride_h,
+                           stride_w, stride_z, H, label_index, ws, P);
+    else
+        hipLaunchKernelGGL((rhlv_counts_kernel<unsigned char>), grid, dim3(256), 0, s, (const unsigned char*)fake, (const unsigned char*)label, pp,
+                           label_indices, stride_h, stride_w, stride_z, H, label_index, ws, P);
+    HV_LAUNCH_CHECK();
+    int smax = 0;
+    for (int i = 0; i < P.nviews; ++i) {
+        smax = P.view[i].S > smax ? P.view[i].S : smax;
+        if (!P.view[i].coronal && !zfast) continue;      // the lanes-along-w counts kernel left the sagittal totals
+        hipLaunchKernelGGL(rhlv_tot_kernel, dim3(P.view[i].S, 2, n_pairs), dim3(256), 0, s, ws, P, i);
+        HV_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(rhlv_range_kernel, dim3(1, P.nviews, n_pairs), dim3(64), 0, s, ws, P);
+    HV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rhlv_slice_kernel, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, ws, P);
+    HV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rhlv_final_kernel, dim3(1, P.nviews, n_pairs), dim3(64), 0, s, ws, P, out, out_len);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+static bool rhlv_views_ok(int views, const hv_rhlv_view* sagittal, const hv_rhlv_view* coronal) {
+    if (views < 1 || views > (HV_RHLV_SAGITTAL | HV_RHLV_CORONAL)) return false;
+    if ((views & HV_RHLV_SAGITTAL) && (!sagittal || sagittal->length_divisor <= 0)) return false;
+    if ((views & HV_RHLV_CORONAL) && (!coronal || coronal->length_divisor <= 0)) return false;
+    return true;
 }
 
 extern "C" size_t hv_rhlv_workspace_bytes(int W, int Z) {
     if (W <= 0 || Z <= 0) return 0;
-    return (size_t)2 * Z * W * sizeof(int) + (size_t)2 * Z * sizeof(int) + 64 + (size_t)Z * sizeof(RhlvRec) + 64;
+    return (size_t)rhlv_plan(W, Z, HV_RHLV_SAGITTAL, nullptr, nullptr).pair_bytes;
 }
 
 extern "C" int hv_rhlv(const void* fake, const void* label, int dtype, long long stride_h, long long stride_w, long long stride_z, int H, int W, int Z,
@@ -207,35 +334,35 @@ extern "C" int hv_rhlv(const void* fake, const void* label, int dtype, long long
     if (!fake || !label || !out || H <= 0 || W <= 0 || Z <= 0 || length_divisor <= 0 || (dtype != 0 && dtype != 1)) return HV_ERR_ARG;
     if (Z > 65535) return HV_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < hv_rhlv_workspace_bytes(W, Z) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    RhlvRec* recs = (RhlvRec*)ws; ws += (size_t)Z * sizeof(RhlvRec);
-    int* cnt = (int*)ws; ws += (size_t)2 * Z * W * sizeof(int);
-    int* tot = (int*)ws; ws += (size_t)2 * Z * sizeof(int);
-    int* params = (int*)ws;
-    if (stride_z == 1 && stride_w != 1) {   // z fastest in memory: lanes along z
-        const dim3 grid(hv_cdiv((long long)W * Z, 256), 2);
-        if (dtype == 0)
-            hipLaunchKernelGGL((rhlv_counts_zfast_kernel<float>), grid, dim3(256), 0, s, (const float*)fake, (const float*)label, stride_h, stride_w,
-                               stride_z, H, W, Z, label_index, cnt);
-        else
-            hipLaunchKernelGGL((rhlv_counts_zfast_kernel<unsigned char>), grid, dim3(256), 0, s, (const unsigned char*)fake, (const unsigned char*)label,
-                               stride_h, stride_w, stride_z, H, W, Z, label_index, cnt);
-        HV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(rhlv_tot_kernel, dim3(Z, 2), dim3(256), 0, s, cnt, W, tot);
-    } else if (dtype == 0) {
-        hipLaunchKernelGGL((rhlv_counts_kernel<float>), dim3(Z, 2), dim3(256), 0, s, (const float*)fake, (const float*)label, stride_h, stride_w, stride_z,
-                           H, W, label_index, cnt, tot);
-    } else {
-        hipLaunchKernelGGL((rhlv_counts_kernel<unsigned char>), dim3(Z, 2), dim3(256), 0, s, (const unsigned char*)fake, (const unsigned char*)label,
-                           stride_h, stride_w, stride_z, H, W, label_index, cnt, tot);
-    }
-    HV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rhlv_range_kernel, dim3(1), dim3(64), 0, s, tot, Z, length_divisor, z_lo, z_hi, params);
-    HV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rhlv_slice_kernel, dim3(Z), dim3(256), 0, s, cnt, tot, params, W, height_threshold, recs);
-    HV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rhlv_final_kernel, dim3(1), dim3(64), 0, s, recs, params, Z, out);
-    HV_LAUNCH_CHECK();
-    return HV_OK;
+    const hv_rhlv_view sagittal = {length_divisor, z_lo, z_hi, height_threshold};
+    return rhlv_run(fake, label, nullptr, nullptr, 1, dtype, stride_h, stride_w, stride_z, H, label_index,
+                    rhlv_plan(W, Z, HV_RHLV_SAGITTAL, &sagittal, nullptr), out, 14, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t hv_rhlv_views_workspace_bytes(int W, int Z, int views, int n_pairs) {
+    if (W <= 0 || Z <= 0 || n_pairs <= 0 || views < 1 || views > (HV_RHLV_SAGITTAL | HV_RHLV_CORONAL)) return 0;
+    return (size_t)rhlv_plan(W, Z, views, nullptr, nullptr).pair_bytes * n_pairs;
+}
+
+extern "C" int hv_rhlv_views(const void* fake, const void* label, int dtype, long long stride_h, long long stride_w, long long stride_z, int H, int W,
+                             int Z, float label_index, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal, double* out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (!fake || !label || !out || H <= 0 || W <= 0 || Z <= 0 || (dtype != 0 && dtype != 1) || !rhlv_views_ok(views, h_sagittal, h_coronal))
+        return HV_ERR_ARG;
+    if (Z > 65535 || W > 65535) return HV_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < hv_rhlv_views_workspace_bytes(W, Z, views, 1) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
+    return rhlv_run(fake, label, nullptr, nullptr, 1, dtype, stride_h, stride_w, stride_z, H, label_index,
+                    rhlv_plan(W, Z, views, h_sagittal, h_coronal), out, 16, workspace, (hipStream_t)stream);
+}
+
+extern "C" int hv_rhlv_views_batch(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                                   long long stride_z, int H, int W, int Z, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
+                                   double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pairs || !label_indices || !out || n_pairs <= 0 || H <= 0 || W <= 0 || Z <= 0 || (dtype != 0 && dtype != 1) ||
+        !rhlv_views_ok(views, h_sagittal, h_coronal))
+        return HV_ERR_ARG;
+    if (Z > 65535 || W > 65535 || n_pairs > 65535) return HV_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < hv_rhlv_views_workspace_bytes(W, Z, views, n_pairs) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
+    return rhlv_run(nullptr, nullptr, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, 0.f,
+                    rhlv_plan(W, Z, views, h_sagittal, h_coronal), out, 16, workspace, (hipStream_t)stream);
 }

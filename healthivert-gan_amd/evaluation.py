@@ -1,19 +1,31 @@
-"""Device-side RHLV quantification (reference evaluation/RHLV_quantification.py), SURVEY.md section 8f row f4.
+"""Device-side RHLV quantification (reference evaluation/RHLV_quantification.py and evaluation/RHLV_quantification_coronal.py),
+SURVEY.md section 8f row f4.
 
-Same entry points as the reference module, on device tensors:
+Same entry points as the reference modules, on device tensors:
   calculate_rhlv(segmentation_fake, segmentation_label, center_z, length, vertebra, height_threshold)   (:120-147)
   rhlv_volume(vol_fake, vol_label, label_index, length_divisor, height_threshold)       per-vertebra body of :160-178
+each with view='sagittal' (the default: hv_rhlv) or view='coronal' (the coronal script's slicing `[:, z, :]` AND its own arithmetic: rescale
+ratios without the sagittal script's + 1e-6, ValueError where it takes max() of an empty third), and for the 2.5D grade
+(evaluation/SVM_grading_2.5d.py: Pre / Mid / Post RHLV of both views):
+  rhlv_volume_25d(vol_fake, vol_label, label_index, ...)   both views from one pass over the volumes, one readback
+  rhlv_dataset(fakes, labels, label_indices, ...)          N pairs of equal shape: one launch sequence per chunk, one readback in all
+  svm_features(records, file1='sagittal')                  the six feature columns in SVM_grading_2.5d.py's order
 Volumes are [H, W, Z] tensors (any strides; float32 or uint8) already resident in HBM, e.g. the label volume infer.process_volume
-just produced; the result is read back as five Python floats.  The file I/O / Excel part of the reference stays on the host.
+just produced.  The file I/O / Excel part of the reference and the SVM stay on the host.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import lib as _lib
 from . import ops
 
 INT_MIN = -2147483648
+SAGITTAL, CORONAL = 1, 2          # HV_RHLV_SAGITTAL, HV_RHLV_CORONAL
+VIEWS = {'sagittal': SAGITTAL, 'coronal': CORONAL}
+EMPTY_THIRD = ('rhlv (coronal view): a slice of the generated vertebra is too narrow for non-empty pre and mid thirds -- '
+               'the reference raises here (max() of an empty array)')
 
 
 def _prep(v, device):
@@ -23,8 +35,7 @@ def _prep(v, device):
     return t.to(device)
 
 
-def _run(fake, label, label_index, length_divisor, z_lo, z_hi, height_threshold):
-    L = _lib.get()
+def _pair(fake, label):
     dev = fake.device if isinstance(fake, torch.Tensor) and fake.is_cuda else torch.device('cuda', torch.cuda.current_device())
     f, l = _prep(fake, dev), _prep(label, dev)
     if l.dtype != f.dtype:
@@ -32,27 +43,124 @@ def _run(fake, label, label_index, length_divisor, z_lo, z_hi, height_threshold)
     _lib.require_gpu(f, l)
     if f.shape != l.shape or f.dim() != 3 or f.stride() != l.stride():
         raise ValueError('rhlv: two [H, W, Z] volumes of equal shape and strides expected')
+    return f, l, dev
+
+
+def _geometry(f):
+    """dtype code, strides and shape of a volume as the C entries take them."""
+    return (0 if f.dtype == torch.float32 else 1, ctypes.c_longlong(f.stride(0)), ctypes.c_longlong(f.stride(1)), ctypes.c_longlong(f.stride(2)),
+            f.shape[0], f.shape[1], f.shape[2])
+
+
+def _run(fake, label, label_index, length_divisor, z_lo, z_hi, height_threshold):
+    L = _lib.get()
+    f, l, dev = _pair(fake, label)
     H, W, Z = f.shape
     out = torch.zeros(14, dtype=torch.float64, device=dev)
     need = L.size('hv_rhlv_workspace_bytes', W, Z)
     ws, _ = ops._ws(need, dev, slot=3)
-    L.call('hv_rhlv', _lib.ptr(f), _lib.ptr(l), 0 if f.dtype == torch.float32 else 1, ctypes.c_longlong(f.stride(0)), ctypes.c_longlong(f.stride(1)),
-           ctypes.c_longlong(f.stride(2)), H, W, Z, ctypes.c_float(label_index), int(length_divisor), int(z_lo), int(z_hi),
+    L.call('hv_rhlv', _lib.ptr(f), _lib.ptr(l), *_geometry(f), ctypes.c_float(label_index), int(length_divisor), int(z_lo), int(z_hi),
            ctypes.c_double(height_threshold), _lib.ptr(out), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream())
     return out
 
 
-def calculate_rhlv(segmentation_fake, segmentation_label, center_z, length, vertebra=None, height_threshold=0.64):
-    """-> (all_rhlv, pre_rhlv, mid_rhlv, post_rhlv, relative_height_label): binary volumes, slices [center_z-length, center_z+length)."""
-    o = _run(segmentation_fake, segmentation_label, -1.0, 1, int(center_z) - int(length), int(center_z) + int(length), height_threshold).cpu()
+def _view_args(L, views, length_divisor, lo, hi, height_threshold):
+    """-> (hv_rhlv_view or None for the sagittal view, the same for the coronal view); height_threshold: one value or a (sagittal, coronal) pair."""
+    thr = tuple(height_threshold) if isinstance(height_threshold, (tuple, list)) else (height_threshold, height_threshold)
+    return tuple(ctypes.byref(L.hv_rhlv_view(int(length_divisor), int(lo), int(hi), float(t))) if views & bit else None
+                 for bit, t in zip((SAGITTAL, CORONAL), thr))
+
+
+def _run_views(fake, label, label_index, views, length_divisor, lo, hi, height_threshold):
+    """hv_rhlv_views -> [views][16] float64 on the device (sagittal first)."""
+    L = _lib.get()
+    f, l, dev = _pair(fake, label)
+    H, W, Z = f.shape
+    out = torch.zeros(bin(views).count('1'), 16, dtype=torch.float64, device=dev)
+    need = L.size('hv_rhlv_views_workspace_bytes', W, Z, views, 1)
+    ws, _ = ops._ws(need, dev, slot=3)
+    sag, cor = _view_args(L, views, length_divisor, lo, hi, height_threshold)
+    L.call('hv_rhlv_views', _lib.ptr(f), _lib.ptr(l), *_geometry(f), ctypes.c_float(label_index), views, sag, cor, _lib.ptr(out), _lib.ptr(ws),
+           ctypes.c_size_t(ws.numel()), _lib.stream())
+    return out
+
+
+def _results(o, return_means):
+    """One 14- or 16-double record on the host -> what rhlv_volume returns; ValueError where the reference would have raised."""
+    if o[13] == 0:
+        return None
+    if len(o) > 14 and o[14] != 0:
+        raise ValueError(EMPTY_THIRD)
+    res = tuple(float(v) for v in o[:5])
+    return (res, [float(v) for v in o[5:13]]) if return_means else res
+
+
+def calculate_rhlv(segmentation_fake, segmentation_label, center_z, length, vertebra=None, height_threshold=0.64, view='sagittal'):
+    """-> (all_rhlv, pre_rhlv, mid_rhlv, post_rhlv, relative_height_label): binary volumes, slices [center_z-length, center_z+length)
+    along axis 2 (view='sagittal') or axis 1 (view='coronal', the coronal script)."""
+    lo, hi = int(center_z) - int(length), int(center_z) + int(length)
+    if VIEWS[view] == SAGITTAL:
+        o = _run(segmentation_fake, segmentation_label, -1.0, 1, lo, hi, height_threshold).cpu()
+    else:
+        o = _run_views(segmentation_fake, segmentation_label, -1.0, CORONAL, 1, lo, hi, height_threshold)[0].cpu()
+        if o[14] != 0:
+            raise ValueError(EMPTY_THIRD)
     return tuple(float(v) for v in o[:5])
 
 
-def rhlv_volume(vol_fake, vol_label, label_index, length_divisor=5, height_threshold=0.64, return_means=False):
+def rhlv_volume(vol_fake, vol_label, label_index, length_divisor=5, height_threshold=0.64, return_means=False, view='sagittal'):
     """Label volumes carrying vertebra ids -> the five values of calculate_rhlv for vertebra `label_index`, or None if the original
     volume does not contain it (the reference's `continue`)."""
-    o = _run(vol_fake, vol_label, float(label_index), length_divisor, INT_MIN, 0, height_threshold).cpu()
-    if o[13] == 0:
+    if VIEWS[view] == SAGITTAL:
+        o = _run(vol_fake, vol_label, float(label_index), length_divisor, INT_MIN, 0, height_threshold).cpu()
+    else:
+        o = _run_views(vol_fake, vol_label, float(label_index), CORONAL, length_divisor, INT_MIN, 0, height_threshold)[0].cpu()
+    return _results(o, return_means)
+
+
+def rhlv_volume_25d(vol_fake, vol_label, label_index, length_divisor=5, height_threshold=0.64, return_means=False):
+    """Both views of rhlv_volume from one pass over the volumes and one readback -> {'sagittal': ..., 'coronal': ...}, or None if the
+    original volume does not contain the vertebra.  height_threshold: one value or a (sagittal, coronal) pair."""
+    o = _run_views(vol_fake, vol_label, float(label_index), SAGITTAL | CORONAL, length_divisor, INT_MIN, 0, height_threshold).cpu()
+    if o[0, 13] == 0:
         return None
-    res = tuple(float(v) for v in o[:5])
-    return (res, [float(v) for v in o[5:13]]) if return_means else res
+    return {'sagittal': _results(o[0], return_means), 'coronal': _results(o[1], return_means)}
+
+
+def rhlv_dataset(fakes, labels, label_indices, length_divisor=5, height_threshold=0.64, chunk=256):
+    """rhlv_volume_25d over N resident volume pairs of equal shape, dtype and strides (lists of device tensors, one vertebra id per pair):
+    one launch sequence per `chunk` pairs (hv_rhlv_views_batch), nothing read back until the end.
+    -> (records, present): float64 numpy [N, 2, 16] ([:, 0] sagittal, [:, 1] coronal: hv_rhlv_views' records -- five results, eight means,
+    vertebra present, "the coronal script would have raised", spare) and bool [N], False where the original lacks the vertebra (the
+    reference's `continue`; that row's numbers mean nothing).  Nothing raises per vertebra: check records[:, 1, 14]."""
+    L = _lib.get()
+    n = len(fakes)
+    if n == 0 or len(labels) != n or len(label_indices) != n:
+        raise ValueError('rhlv_dataset: equally many (at least one) generated volumes, original volumes and label indices expected')
+    dev = fakes[0].device
+    geo = (fakes[0].shape, fakes[0].stride(), fakes[0].dtype)
+    for t in list(fakes) + list(labels):
+        _lib.require_gpu(t)
+        if t.dim() != 3 or (t.shape, t.stride(), t.dtype) != geo or t.dtype not in (torch.float32, torch.uint8) or t.device != dev:
+            raise ValueError('rhlv_dataset: [H, W, Z] float32 or uint8 device volumes of one shape, dtype and stride pattern expected')
+    H, W, Z = geo[0]
+    views = SAGITTAL | CORONAL
+    table = torch.tensor([p for f, l in zip(fakes, labels) for p in (f.data_ptr(), l.data_ptr())], dtype=torch.int64).to(dev)
+    ids = torch.tensor([float(i) for i in label_indices], dtype=torch.float32).to(dev)
+    out = torch.zeros(n, 2, 16, dtype=torch.float64, device=dev)
+    chunk = max(1, min(int(chunk), n))
+    ws, _ = ops._ws(L.size('hv_rhlv_views_workspace_bytes', W, Z, views, chunk), dev, slot=3)
+    sag, cor = _view_args(L, views, length_divisor, INT_MIN, 0, height_threshold)
+    for i in range(0, n, chunk):
+        m = min(chunk, n - i)
+        L.call('hv_rhlv_views_batch', _lib.ptr(table[2 * i:]), _lib.ptr(ids[i:]), m, *_geometry(fakes[0]), views, sag, cor, _lib.ptr(out[i:]),
+               _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream())
+    rec = out.cpu().numpy()
+    return rec, rec[:, 0, 13] != 0
+
+
+def svm_features(records, file1='sagittal'):
+    """records [N, 2, 16] of rhlv_dataset -> [N, 6]: Pre / Mid / Post RHLV of the view the caller feeds SVM_grading_2.5d.py as `file1`, then the
+    other view's (its `_2` columns)."""
+    first = 0 if VIEWS[file1] == SAGITTAL else 1
+    return np.concatenate([records[:, first, 1:4], records[:, 1 - first, 1:4]], axis=1)

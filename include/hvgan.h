@@ -510,6 +510,33 @@ int hv_rhlv(const void* fake, const void* label, int dtype, long long stride_h, 
             float label_index, int length_divisor, int z_lo, int z_hi, double height_threshold, double* out, void* workspace,
             size_t workspace_bytes, void* stream);
 
+/* ---- RHLV in the sagittal and / or the coronal view from one pass over the volumes (the six features of evaluation/SVM_grading_2.5d.py:
+ * reference evaluation/RHLV_quantification.py and evaluation/RHLV_quantification_coronal.py, :41-147 and the per-vertebra body of
+ * process_datasets_to_excel) ----
+ * Volumes, dtype, strides and label_index as for hv_rhlv.  Both scripts start from the table cnt[z][w] = #{h : vol[h][w][z] is the vertebra}, which
+ * is built once; the sagittal view walks it as slices z with columns w, the coronal view (the reference's [:, z, :]) as slices w with columns z,
+ * its range taken from the original vertebra's extent along w.  `views`: HV_RHLV_SAGITTAL, HV_RHLV_CORONAL or both; h_sagittal / h_coronal (host)
+ * carry each requested view's length_divisor, explicit slice range [lo, hi) (lo == INT_MIN: derived like the reference) and height_threshold.
+ * The coronal view follows the coronal script's own arithmetic: rescale ratio label.max() / fake.max() without the sagittal script's + 1e-6
+ * (inf where a third of the generated vertebra is empty: those columns then select nothing), and where a participating slice's pre or mid third
+ * of columns is empty the script raises ValueError (max() of an empty array) -- the record's flag says so.
+ * out (device): one 16-double record per requested view, sagittal first: hv_rhlv's 14 values, [14] = 1.0 if the reference would have raised
+ * (coronal view only), [15] = 0.  hv_rhlv_views_batch: n_pairs pairs of equal shape, dtype and strides; pairs = DEVICE table
+ * {fake_0, label_0, fake_1, label_1, ...} of volume pointers, label_indices = DEVICE [n_pairs]; out [n_pairs][views][16]; nothing is read back,
+ * and n_pairs == 1 gives hv_rhlv_views' bits.  workspace: hv_rhlv_views_workspace_bytes(W, Z, views, n_pairs) bytes, 8-byte aligned. */
+enum { HV_RHLV_SAGITTAL = 1, HV_RHLV_CORONAL = 2 };
+typedef struct {
+    int length_divisor, lo, hi;
+    double height_threshold;
+} hv_rhlv_view;
+size_t hv_rhlv_views_workspace_bytes(int W, int Z, int views, int n_pairs);
+int hv_rhlv_views(const void* fake, const void* label, int dtype, long long stride_h, long long stride_w, long long stride_z, int H, int W, int Z,
+                  float label_index, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal, double* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int hv_rhlv_views_batch(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                        long long stride_z, int H, int W, int Z, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
+                        double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- batch assembly on the device (reference data/aligned_dataset.py:204-280, AlignedDataset.__getitem__) ----
  * One item = one sagittal slice of a vertebra volume whose four uint8 planes [H][W] are resident on the device: ct = ct_data.astype(uint8)
  * (:245), vert = component-filtered vertebra mask * 255 (:247-248), normal = the patient's normal vertebrae as 0/255 (:190-196), cam =

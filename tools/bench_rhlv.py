@@ -1,4 +1,11 @@
-"""RHLV quantification of one 256 x 256 x 64 label-volume pair: device (hv_rhlv, volumes resident in HBM) vs the CPU oracle."""
+"""RHLV quantification of 256 x 256 x 64 label-volume pairs resident in HBM:
+  * one pair, sagittal view: device (hv_rhlv) vs the CPU oracle;
+  * one pair, both views (the 2.5D grade's six features): rhlv_volume_25d (one pass over the volumes, one readback) vs two rhlv_volume
+    calls, the second on the permuted view -- the only way to both views before hv_rhlv_views (its coronal numbers follow the sagittal
+    script's arithmetic, so it is a timing yardstick only);
+  * a dataset of 64 pairs: rhlv_dataset (one launch sequence, one readback) vs 64 rhlv_volume_25d calls.
+Device-only times are hipEvent brackets around back-to-back launches; the end-to-end times (`wall`) include the readbacks and are
+medians of repeated wall-clock measurements."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -9,17 +16,34 @@ from oracle import restate as R
 
 fake, label = synth.make_rhlv_pair(seed=7, H=256, W=256, Z=64, empty_ends=6)
 f, l = torch.from_numpy(fake).float().cuda(), torch.from_numpy(label).float().cuda()
-for _ in range(3):
-    evaluation._run(f, l, 20.0, 5, evaluation.INT_MIN, 0, 0.64)
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-N = 50
-for _ in range(N):
-    evaluation._run(f, l, 20.0, 5, evaluation.INT_MIN, 0, 0.64)
-e1.record()
-torch.cuda.synchronize()
-us = e0.elapsed_time(e1) / N * 1e3
+
+
+def device_us(fn, n=50, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n * 1e3
+
+
+def wall_us(fn, n=20, warm=3):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e6)
+    return float(np.median(ts))
+
+
+us = device_us(lambda: evaluation._run(f, l, 20.0, 5, evaluation.INT_MIN, 0, 0.64))
 t0 = time.perf_counter()
 ref, _ = R.rhlv_volume(fake, label, 20)
 cpu_ms = (time.perf_counter() - t0) * 1e3
@@ -27,3 +51,40 @@ got = evaluation.rhlv_volume(f, l, 20)
 byt = 2 * fake.size * 4
 print('hv_rhlv 256x256x64 pair: %.1f us per pair (%.1f GB/s of the %.1f MB read once), CPU oracle %.1f ms; max |d| %.2e'
       % (us, byt / us / 1e3, byt / 1e6, cpu_ms, max(abs(a - b) for a, b in zip(got, ref))))
+
+# (a) both views of one pair
+fp, lp = f.permute(0, 2, 1), l.permute(0, 2, 1)
+both = evaluation.SAGITTAL | evaluation.CORONAL
+
+
+def two_calls_device():
+    evaluation._run(f, l, 20.0, 5, evaluation.INT_MIN, 0, 0.64)
+    evaluation._run(fp, lp, 20.0, 5, evaluation.INT_MIN, 0, 0.64)
+
+
+def two_calls():
+    return evaluation.rhlv_volume(f, l, 20), evaluation.rhlv_volume(fp, lp, 20)
+
+
+one_dev = device_us(lambda: evaluation._run_views(f, l, 20.0, both, 5, evaluation.INT_MIN, 0, 0.64))
+two_dev = device_us(two_calls_device)
+one_wall = wall_us(lambda: evaluation.rhlv_volume_25d(f, l, 20))
+two_wall = wall_us(two_calls)
+print('2.5D, one 256x256x64 pair: rhlv_volume_25d %.1f us device / %.1f us wall; two rhlv_volume calls (second on the permuted view) '
+      '%.1f us device / %.1f us wall' % (one_dev, one_wall, two_dev, two_wall))
+
+# (b) a dataset of 64 resident pairs
+N = 64
+fakes, labels = [], []
+for i in range(N):
+    a, b = synth.make_rhlv_pair(seed=100 + i, H=256, W=256, Z=64, empty_ends=6, collapse=0.05 * (i % 8))
+    fakes.append(torch.from_numpy(a).float().cuda())
+    labels.append(torch.from_numpy(b).float().cuda())
+ids = [20] * N
+rec, present = evaluation.rhlv_dataset(fakes, labels, ids)
+single = evaluation.rhlv_volume_25d(fakes[5], labels[5], 20)
+assert present.all() and tuple(rec[5, 0, :5]) == single['sagittal'] and tuple(rec[5, 1, :5]) == single['coronal']
+batch_wall = wall_us(lambda: evaluation.rhlv_dataset(fakes, labels, ids), n=10)
+loop_wall = wall_us(lambda: [evaluation.rhlv_volume_25d(a, b, 20) for a, b in zip(fakes, labels)], n=10)
+print('2.5D dataset of %d 256x256x64 pairs: rhlv_dataset %.1f us per pair wall (one readback); %d rhlv_volume_25d calls %.1f us per pair wall'
+      % (N, batch_wall / N, N, loop_wall / N))
