@@ -236,7 +236,7 @@ class ParamSet:
 
 class ConvNode:
     """conv (+bias +activation) between two NHWC views; knows how to run forward and backward."""
-    __slots__ = ('p', 'x', 'y', 'k', 's', 'pad', 'd', 'act', 'shift', 'need_dx', 'transposed', 'use_bias', 'dx_c', 'pool_to', 'split')
+    __slots__ = ('p', 'x', 'y', 'k', 's', 'pad', 'd', 'act', 'shift', 'need_dx', 'transposed', 'use_bias', 'dx_c', 'pool_to', 'split', 'full')
 
     def __init__(self, p, x, y, s=1, pad=0, d=1, act='none', shift=0, need_dx=True, transposed=False, use_bias=True, dx_c=None):
         self.p, self.x, self.y, self.k, self.s, self.pad, self.d = p, x, y, p.k, s, pad, d
@@ -244,13 +244,14 @@ class ConvNode:
         # dx_c: only the first dx_c input channels' gradient is wanted (a concat input whose tail channels are network inputs): the data
         # gradient is then a convolution with fewer output channels (the first dx_c rows of the transposed filter table)
         self.dx_c = dx_c
-        # pool_to = (Act low, activation of low's producer): x is a concat buffer whose first dx_c channels are the nearest x2 up-sampling of `low`;
-        # set by the owner of the plan when the pooled data gradient can serve it (dx_call form 'pool_to')
+        # pool_to = (Act low, activation of low's producer): x is a concat buffer whose first dx_c channels are the nearest x2 up-sampling of `low`.  Set once by
+        # the layer's owner; conv_backward takes the pooled data gradient (dx_call form 'pool_to') where pooled() says the dispatch serves it
         self.pool_to = None
         # split = (Act low, Act x1): x is the concat [nearest x2 up-sampling of low (p.split_k channels) | x1 (one channel) | padding]; where the
         # filters-in-LDS kernel serves the shape the forward reads `low` with the fused up-sampling and adds x1's taps in its epilogue, so the
         # up-sampled part of x is only materialised for the backward (split_forward() tells)
         self.split = None
+        self.full = None      # full_scratch()
 
     def forward_call(self, prec, xn=None, x_raw=None):
         """The call that runs this node's forward (ops.ConvCall).  Where `split` is set and the dispatch serves that form (the x1 kernel exists for two
@@ -301,6 +302,13 @@ class ConvNode:
             mul = (Act(self.x.t, p.cin_fwd, self.x.coff), mul_x)
         return ops.ConvCall(Act(gy.t, p.coutP, gy.coff), p.w_bwd, dst, self.k, self.s, self.pad, self.d, transposed=form != 'src', pool2=form in ('pool', 'pool_to'),
                             accumulate=int(accumulate), precision=prec, w_h=p.w_bwd_h, w_t=p.w_bwd_t, mul=mul, bn=bn, wuse=(p, 'use_bwd'))
+
+    def full_scratch(self):
+        """Full-resolution buffer for the data gradient of a node with fused up-sampling (dx_call form 'full'): built where that fallback first runs."""
+        if self.full is None:
+            x = self.x
+            self.full = Act(torch.zeros(x.B, x.H * 2, x.W * 2, x.ld, dtype=x.t.dtype, device=x.t.device), self.p.cin_fwd, 0)
+        return self.full
 
     def pooled(self, book, prec, form='pool', mul_x=None):
         """Can the data gradient leave 2x2-pooled in `form` ('pool' or 'pool_to')?  Asked of the call conv_backward would launch."""
@@ -356,10 +364,7 @@ class GradBook:
         self.written = set()
         self.side = None          # side HIP stream for weight gradients (they overlap the data-gradient chain)
         self._side_of = None      # ... of this parent stream
-        # block deferral (round 4): while `defer_wgrad` is set, conv_backward queues its weight gradient here instead of launching it; the owner of the
-        # plan launches the whole block later on ONE side stream (one fork, one join) beside an independent part of the backward
-        self.defer_wgrad = False
-        self.deferred = []
+        self.wgrad_block = WgradBlock()
 
     def fork(self):
         """Side stream, ordered after everything queued so far on the current stream."""
@@ -395,6 +400,52 @@ class GradBook:
         return acc
 
 
+class WgradBlock:
+    """Weight gradients of one backward that run as a block on ONE side stream beside an independent part of the backward (round 4): they only feed the
+    optimiser.  open() decides once per backward whether it may fork (no side streams at all under SERIAL, no fork nested in a NO_FORK_STREAMS stream); while the
+    block collects, conv_backward queues its weight gradient here instead of launching it (its operands -- the layer's input and the finished gradient of its
+    output -- stay as they are until the next backward); launch() is one fork: the queue in order on the side stream, then that stream's last slab fold; join()
+    is the one join.  A backward that does not fork never collects: everything runs in line where it is issued."""
+    __slots__ = ('side', 'collecting', 'queue', 'later', 'pset')
+
+    def __init__(self):
+        self.side, self.collecting, self.queue, self.later, self.pset = None, False, [], [], None
+
+    def open(self, pset, device):
+        """Start of a backward of the network whose parameters are `pset`: collecting starts here where the backward may fork."""
+        fork = not SERIAL and torch.cuda.current_stream().cuda_stream not in NO_FORK_STREAMS
+        self.side = named_stream('generator-wgrad-block', device) if fork else None
+        self.collecting, self.queue, self.later, self.pset = fork, [], [], pset
+
+    def add(self, run):
+        self.queue.append(run)
+
+    def before_next_block(self, run):
+        """`run` writes an operand that only weight gradients of the block AFTER the next launch read: it heads that block's queue (off the critical path of the
+        backward, in front of its readers on their stream) -- or runs now where this backward does not fork."""
+        if self.collecting:
+            self.later.append(run)
+        else:
+            run()
+
+    def launch(self, keep_collecting=False):
+        # (several side streams with the launches dealt round-robin, HV_G_WGRAD_STREAMS 2 / 3, measured slower in round 5: 6.94 -> 6.98-7.36 ms)
+        if self.side is None:
+            return
+        self.side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.side):
+            for run in self.queue:
+                run()
+            self.pset.fold_chain().flush()      # the side stream's last slab fold, on that stream (before the join)
+        self.queue, self.later, self.collecting = self.later, [], keep_collecting
+
+    def join(self):
+        assert not self.queue and not self.later, 'WgradBlock.join(): queued weight gradients were never launched'
+        if self.side is not None:
+            torch.cuda.current_stream().wait_stream(self.side)
+        self.side, self.collecting = None, False
+
+
 def _wgrad(node, p, xin, gfull, accumulate, prec, dbias=None, dbias_accumulate=False):
     # the split-K slab fold of this weight gradient rides in the NEXT weight gradient of the network on this stream (ops.FoldChain; the last one is
     # launched by ParamSet.finish_backward / the owner of a side stream) -- round 4's 62 fold launches per step were each a dependent 5-us node
@@ -408,7 +459,7 @@ def _wgrad(node, p, xin, gfull, accumulate, prec, dbias=None, dbias_accumulate=F
                          dbias=dbias, dbias_accumulate=dbias_accumulate, chain=chain)
 
 
-def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=False, tmp_full=None, wgrad=True, x_wg=None, premultiplied=False,
+def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=False, wgrad=True, x_wg=None, premultiplied=False,
                   mul_x=None, dbias_done=False, bn=None):
     """Backward of one ConvNode: activation gradient (+bias gradient), weight gradient, data gradient.
     x_wg: channel-padded copy of the input for the weight-gradient kernel (1-channel image inputs).
@@ -434,20 +485,21 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
         xin = Act(xs.t, p.cin_wg, xs.coff)
         # the weight gradient only feeds the optimiser: queue it on the side stream so that it overlaps the data-gradient
         # chain (joined by GradBook.join() before the gradients are finalised / the activations are overwritten)
-        if book.defer_wgrad:      # (its operands -- the layer's input and the finished gradient of its output -- stay as they are until the next backward)
-            book.deferred.append(lambda node=node, p=p, xin=xin, gfull=gfull, acc=wgrad_accumulate, db=p.bias.grad if fuse_dbias else None, dba=dbias_accumulate:
+        if book.wgrad_block.collecting:
+            book.wgrad_block.add(lambda node=node, p=p, xin=xin, gfull=gfull, acc=wgrad_accumulate, db=p.bias.grad if fuse_dbias else None, dba=dbias_accumulate:
                                  _wgrad(node, p, xin, gfull, acc, prec, dbias=db, dbias_accumulate=dba))
         else:
             # (in line: per-layer forks to a side stream lost their A/B twice -- 8.25 -> 8.15 ms at the end of round 3, 7.36 -> 7.6-7.8 ms in round 4 -- and are gone;
-            # the refinement generator's weight gradients go to a side stream as ONE block, see defer_wgrad)
+            # the refinement generator's weight gradients go to a side stream as ONE block, see WgradBlock)
             _wgrad(node, p, xin, gfull, wgrad_accumulate, prec, dbias=p.bias.grad if fuse_dbias else None, dbias_accumulate=dbias_accumulate)
     if not node.need_dx:
         return
     # (pool_to / fused up-sampling: the gradient of the up-sampled tensor leaves 2x2 sum-pooled from the conv's own epilogue where the dispatch serves it --
-    # no full-resolution gradient in memory, no hv_copy_channels mode 3 pass; the owner of pool_to runs its producer premultiplied)
+    # no full-resolution gradient in memory, no hv_copy_channels mode 3 pass; the owner of pool_to, who asked the same memoised question, runs its producer
+    # premultiplied)
     if node.transposed:
         form = 'src'
-    elif node.pool_to is not None:
+    elif node.pool_to is not None and node.pooled(book, prec, 'pool_to'):
         form = 'pool_to'
     elif node.shift:
         form = 'pool' if node.pooled(book, prec, 'pool', mul_x) else 'full'
@@ -455,7 +507,7 @@ def conv_backward(node, book, prec, dbias_accumulate=False, wgrad_accumulate=Fal
         form = 'plain'
     if form == 'full':
         assert not mul_x
-        full = tmp_full() if callable(tmp_full) else tmp_full      # (the full-resolution buffer is only built where this fallback runs)
+        full = node.full_scratch()
         node.dx_call(book, prec, 'full', full, False).launch()
         gx = node.dx_view(book, 'plain')
         ops.copy_channels(full, gx, mode=3, accumulate=book.mark(gx))
@@ -494,7 +546,7 @@ def chain_link(n, nxt, book, prec):
     return not n.shift or n.pooled(book, prec, 'pool', nxt.act)
 
 
-def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=False, stop_before=None):
+def conv_backward_chain(nodes, book, prec, premultiplied_first=False, stop_before=None):
     """Backward of a PURE chain of ConvNodes given in backward order: nodes[i].x is exactly the output buffer of nodes[i+1] and
     nothing else reads or writes that buffer's gradient.  Inside the chain the data gradient of nodes[i] is multiplied by
     act'(output of nodes[i+1]) in its conv epilogue, so nodes[i+1] starts from its pre-activation gradient: the in-place
@@ -505,7 +557,7 @@ def conv_backward_chain(nodes, book, prec, tmp_full=None, premultiplied_first=Fa
     for i, n in enumerate(nodes):
         nxt = nodes[i + 1] if i + 1 < len(nodes) else stop_before
         link = chain_link(n, nxt, book, prec)
-        conv_backward(n, book, prec, premultiplied=pre, mul_x=nxt.act if link else None, tmp_full=(tmp_full or {}).get(id(n)))
+        conv_backward(n, book, prec, premultiplied=pre, mul_x=nxt.act if link else None)
         pre = link
 
 

@@ -199,115 +199,152 @@ def offsets_to_flow(argmax, B, h, w, rate):
 
 
 # ================================================================================================ generator plan
+def _buffers(c):
+    """The NHWC buffers of both generators at width c, stated once: (name -> channels) per resolution (side >> 0, 1, 2), and the channel ranges of them that
+    layers write or read under a name of their own (name -> (buffer, first channel, channels))."""
+    full = dict(c_in=3, c1=c, cat19=2 * c + 1, c19=2 * c, c15=c, c16=c // 2, f_in=4, f1=c, p1=c, a15=c, cat17=c // 2 + 1)
+    half = dict(c2=2 * c, c3=2 * c, cat20=4 * c + 1, c20=4 * c, c13=2 * c, c14=2 * c, f2=c, f3=2 * c, p2=c, p3=2 * c, a13=2 * c, a14=2 * c)
+    quarter = dict(c4=4 * c, f4=2 * c, cat11=8 * c, **{n: 4 * c for n in 'c5 c6 c7 c8 c9 c10 c11 c12 f5 f6 f7 f8 f9 p4 p5 p6 ca p9 a11 a12 a19'.split()})
+    views = dict(f10=('cat11', 0, 4 * c), p10=('cat11', 4 * c, 4 * c), a16=('cat17', 0, c // 2))      # cat11 = [conv10_atrous | pmconv10], cat17 = [allconv16 | x_stage1]
+    return (full, half, quarter), views
+
+
+_IMAGES = ('x_stage1', 'coarse_seg', 'x_stage2', 'fine_seg')      # the heads' outputs: (B,1,H,W) fp32 in every mode (reference API)
+
+
+def _layers(c):
+    """The two generators as data: generator -> chain -> rows (reference layer, input buffer, output buffer, stride, pad, dilation, activation[, ConvNode flags:
+    need_dx, dx_c, shift]) in forward order.  A chain is a run of layers the executors walk as one; _GenPlan builds one ConvNode per row."""
+    e = (1, 1, 1, 'elu')
+    dil = lambda r: (1, r, r, 'elu')
+    down = (2, 1, 1, 'elu')
+    return {
+        'coarse_generator': dict(
+            enc=[('conv1', 'c_in', 'c1', 1, 2, 1, 'elu', dict(need_dx=False)), ('conv2_downsample', 'c1', 'c2', *down), ('conv3', 'c2', 'c3', *e),
+                 ('conv4_downsample', 'c3', 'c4', *down), ('conv5', 'c4', 'c5', *e), ('conv6', 'c5', 'c6', *e), ('conv7_atrous', 'c6', 'c7', *dil(2)),
+                 ('conv8_atrous', 'c7', 'c8', *dil(4)), ('conv9_atrous', 'c8', 'c9', *dil(8)), ('conv10_atrous', 'c9', 'c10', *dil(16))],      # c10 feeds the height head
+            mid=[('conv11', 'c10', 'c11', *e), ('conv12', 'c11', 'c12', *e)],
+            up20=[('conv20', 'cat20', 'c20', *e, dict(dx_c=4 * c))],      # [up(c12) | CAM at half size]; the CAM channel is an input: no gradient
+            dec20=[('conv13', 'c20', 'c13', *e), ('conv14', 'c13', 'c14', *e)],
+            up19=[('conv19', 'cat19', 'c19', *e, dict(dx_c=2 * c))],      # [up(c14) | CAM]
+            dec19=[('conv15', 'c19', 'c15', *e), ('conv16', 'c15', 'c16', *e)],
+            heads=[('conv17', 'c16', 'x_stage1', 1, 1, 1, 'clamp'), ('conv18', 'c16', 'coarse_seg', 1, 1, 1, 'sigmoid')]),
+        'fine_generator': dict(
+            dilated=[('conv1', 'f_in', 'f1', 1, 2, 1, 'elu'), ('conv2_downsample', 'f1', 'f2', *down), ('conv3', 'f2', 'f3', *e), ('conv4_downsample', 'f3', 'f4', *down),
+                     ('conv5', 'f4', 'f5', *e), ('conv6', 'f5', 'f6', *e), ('conv7_atrous', 'f6', 'f7', *dil(2)), ('conv8_atrous', 'f7', 'f8', *dil(4)),
+                     ('conv9_atrous', 'f8', 'f9', *dil(8)), ('conv10_atrous', 'f9', 'f10', *dil(16))],
+            pm_in=[('pmconv1', 'f_in', 'p1', 1, 2, 1, 'elu')],      # (on its own: the backward runs it after the branches join)
+            pm=[('pmconv2_downsample', 'p1', 'p2', *down), ('pmconv3', 'p2', 'p3', *e), ('pmconv4_downsample', 'p3', 'p4', *down), ('pmconv5', 'p4', 'p5', *e),
+                ('pmconv6', 'p5', 'p6', 1, 1, 1, 'relu')],
+            pm_out=[('pmconv9', 'ca', 'p9', *e), ('pmconv10', 'p9', 'p10', *e)],      # behind the attention block (p6 -> ca)
+            merge=[('allconv11', 'cat11', 'a11', *e)],      # a11 feeds the height head
+            trunk=[('allconv12', 'a11', 'a12', *e), ('allconv19', 'a12', 'a19', *e), ('allconv13', 'a19', 'a13', *e, dict(shift=1)), ('allconv14', 'a13', 'a14', *e),
+                   ('allconv15', 'a14', 'a15', *e, dict(shift=1)), ('allconv16', 'a15', 'a16', *e)],
+            heads=[('allconv17', 'cat17', 'x_stage2', 1, 1, 1, 'clamp'), ('allconv18', 'cat17', 'fine_seg', 1, 1, 1, 'sigmoid')])}
+
+
+# the coarse layers that read [nearest x2 up-sampling of a low-resolution map | CAM channel]: layer -> (its chain, the layer that produces the low map, hv_copy_channels
+# mode that resamples the CAM image to the layer's resolution)
+_UP_CONCAT = {'coarse_generator.conv19': ('up19', 'coarse_generator.conv14', 0), 'coarse_generator.conv20': ('up20', 'coarse_generator.conv12', 2)}
+
+
+class _UpConcat:
+    """One layer of _UP_CONCAT.  Where the dispatch serves it (ConvNode.split_forward) the forward reads `low` with the fused up-sampling and takes the CAM channel in
+    its epilogue (hv_conv_desc.x1), so the up-sampled part of the concat buffer `cat` is only built for the layer's weight gradient; where the pooled data gradient
+    serves the shape (fp16 mode) the gradient of `low` comes 2x2-pooled and times act' straight from the convolution's epilogue."""
+    __slots__ = ('node', 'low', 'cat', 'k', 'cam_mode', 'pooled')
+
+    def __init__(self, node, producer, cam_mode):
+        self.node, self.low, self.cat, self.k, self.cam_mode = node, producer.y, node.x, node.dx_c, cam_mode
+        assert self.low.C == self.k and self.cat.C == self.k + 1
+        self.pooled = None      # the dispatch's answer in the last backward
+        node.split = (self.low, self.cat.slice(self.k, 1))
+        node.pool_to = (self.low, producer.act)
+
+    def forward(self, cam, prec):
+        if not self.node.split_forward(prec):
+            ops.copy_channels(self.low, self.cat.slice(0, self.k), mode=1)
+        ops.copy_channels(cam, self.cat.slice(self.k, 1), mode=self.cam_mode)
+        self.node.forward(prec)
+
+    def materialise(self, prec):
+        """The up-sampled part of the concat buffer for the weight gradient, where the forward did not build it."""
+        if self.node.split_forward(prec):
+            ops.copy_channels(self.low, self.cat.slice(0, self.k), mode=1)
+
+    def backward(self, above, book, prec, premultiplied_first):
+        """Backward of the pure chain `above` (backward order) that ends in this layer, then of the layer.  -> True where the gradient of `low` left pooled and
+        times act' (its producer then starts premultiplied); otherwise full-resolution gradient + adjoint-of-up-sampling pass."""
+        self.pooled = self.node.pooled(book, prec, 'pool_to')
+        E.conv_backward_chain([*above, self.node], book, prec, premultiplied_first=premultiplied_first)
+        if not self.pooled:
+            g = book.twin(self.low)
+            ops.copy_channels(book.twin(self.cat).slice(0, self.k), g, mode=3, accumulate=book.mark(g))
+        return self.pooled
+
+
+class _Head:
+    """One 1-channel head: its output's gradient lives in a channel-padded carrier ([B,H,W,4], channel 0 live), registered as the output's twin once."""
+    __slots__ = ('node', 'carrier')
+
+    def __init__(self, node, book):
+        y, x = node.y, node.x
+        self.node = node
+        self.carrier = Act(torch.zeros(y.B, y.H, y.W, ops.cpad(1), dtype=x.t.dtype, device=x.t.device), 1, 0)
+        book.twins[id(y.t)] = self.carrier.t
+
+    def fused_seed(self, seed):
+        """seed -> act' -> carrier -> bias gradient in one pass (instead of: copy, in-place act' pass, column sums)?"""
+        return bool(self.carrier.f16 and seed.dtype == torch.float32 and seed.is_contiguous() and self.node.p.bias is not None and self.node.use_bias)
+
+    def backward(self, seed, book, prec, mul_x=None):
+        """seed (B,1,H,W) -> padded carrier -> activation/bias gradient -> wgrad + dgrad."""
+        node, carrier = self.node, self.carrier
+        if self.fused_seed(seed):
+            ops.head_seed_backward(seed, node.y, Act(carrier.t, 4, 0), node.act, dbias=node.p.bias.grad)
+            E.conv_backward(node, book, prec, premultiplied=True, dbias_done=True, mul_x=mul_x)
+            return
+        ops.copy_channels(Act(seed.view(carrier.B, carrier.H, carrier.W, 1)), carrier, mode=0)
+        E.conv_backward(node, book, prec, mul_x=mul_x)
+
+
 class _GenPlan:
-    """Buffers + node list of Generator for one (B, H, W)."""
+    """Buffers, nodes and layer owners of Generator for one (B, H, W), built from _buffers / _layers: `a` name -> Act, `node` reference layer name -> ConvNode,
+    `chain` (generator, chain) -> its nodes in forward order, `up` / `head` reference layer name -> owner."""
+    __slots__ = ('B', 'H', 'W', 'dev', 'book', 'a', 'node', 'chain', 'up', 'head', 'attn', 'x_stage1', 'coarse_seg', 'x_stage2', 'fine_seg', 'c_pool', 'pred1',
+                 'f_pool', 'pred2', 'd_xs1_total', 'd_cs_total', 'mask_img', 'generation')
 
     def __init__(self, gen, B, H, W, device):
-        cg, fg = gen.coarse_generator, gen.fine_generator
         c = gen.cnum
         self.B, self.H, self.W, self.dev = B, H, W, device
         dt = ops.storage_dtype(gen.precision)        # fp16 buffers in the fp16 mode; the (B,1,H,W) image outputs stay fp32
-        z = lambda h, w, C: Act(torch.zeros(B, h, w, ops.cpad(C), dtype=dt, device=device), C, 0)
-        img = lambda: torch.zeros(B, 1, H, W, dtype=torch.float32, device=device)
-        H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
         self.book = E.GradBook()
-        P = gen._pset_convs
-        N = E.ConvNode
-        # ---------------- coarse
-        self.c_in = z(H, W, 3)
-        a = {}
-        a['c1'] = z(H, W, c); a['c2'] = z(H2, W2, 2 * c); a['c3'] = z(H2, W2, 2 * c); a['c4'] = z(H4, W4, 4 * c)
-        for n in ('c5', 'c6', 'c7', 'c8', 'c9', 'c10', 'c11', 'c12'):
-            a[n] = z(H4, W4, 4 * c)
-        a['cat20'] = z(H2, W2, 4 * c + 1); a['c20'] = z(H2, W2, 4 * c); a['c13'] = z(H2, W2, 2 * c); a['c14'] = z(H2, W2, 2 * c)
-        a['cat19'] = z(H, W, 2 * c + 1); a['c19'] = z(H, W, 2 * c); a['c15'] = z(H, W, c); a['c16'] = z(H, W, c // 2)
-        self.x_stage1, self.coarse_seg = img(), img()
-        xs1 = Act(self.x_stage1.view(B, H, W, 1)); cs = Act(self.coarse_seg.view(B, H, W, 1))
-        self.c_nodes = [
-            N(P['coarse_generator.conv1'], self.c_in, a['c1'], 1, 2, 1, 'elu', need_dx=False),
-            N(P['coarse_generator.conv2_downsample'], a['c1'], a['c2'], 2, 1, 1, 'elu'),
-            N(P['coarse_generator.conv3'], a['c2'], a['c3'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv4_downsample'], a['c3'], a['c4'], 2, 1, 1, 'elu'),
-            N(P['coarse_generator.conv5'], a['c4'], a['c5'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv6'], a['c5'], a['c6'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv7_atrous'], a['c6'], a['c7'], 1, 2, 2, 'elu'),
-            N(P['coarse_generator.conv8_atrous'], a['c7'], a['c8'], 1, 4, 4, 'elu'),
-            N(P['coarse_generator.conv9_atrous'], a['c8'], a['c9'], 1, 8, 8, 'elu'),
-            N(P['coarse_generator.conv10_atrous'], a['c9'], a['c10'], 1, 16, 16, 'elu'),
-            N(P['coarse_generator.conv11'], a['c10'], a['c11'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv12'], a['c11'], a['c12'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv20'], a['cat20'], a['c20'], 1, 1, 1, 'elu', dx_c=4 * c),      # (the CAM channel is an input: no gradient)
-            N(P['coarse_generator.conv13'], a['c20'], a['c13'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv14'], a['c13'], a['c14'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv19'], a['cat19'], a['c19'], 1, 1, 1, 'elu', dx_c=2 * c),
-            N(P['coarse_generator.conv15'], a['c19'], a['c15'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv16'], a['c15'], a['c16'], 1, 1, 1, 'elu'),
-            N(P['coarse_generator.conv17'], a['c16'], xs1, 1, 1, 1, 'clamp'),
-            N(P['coarse_generator.conv18'], a['c16'], cs, 1, 1, 1, 'sigmoid'),
-        ]
-        self.c_nodes[12].split = (a['c12'], a['cat20'].slice(4 * c, 1))      # conv20 = [up(c12) | CAM at 128^2]
-        self.c_nodes[15].split = (a['c14'], a['cat19'].slice(2 * c, 1))      # conv19 = [up(c14) | CAM]
-        self.c_pool = torch.zeros(B, 4 * c, device=device); self.pred1 = torch.zeros(B, 1, device=device)
-        # ---------------- fine
-        self.f_in = z(H, W, 4)
-        a['f1'] = z(H, W, c); a['f2'] = z(H2, W2, c); a['f3'] = z(H2, W2, 2 * c); a['f4'] = z(H4, W4, 2 * c)
-        for n in ('f5', 'f6', 'f7', 'f8', 'f9'):
-            a[n] = z(H4, W4, 4 * c)
-        a['cat11'] = z(H4, W4, 8 * c)
-        a['p1'] = z(H, W, c); a['p2'] = z(H2, W2, c); a['p3'] = z(H2, W2, 2 * c)
-        for n in ('p4', 'p5', 'p6', 'ca', 'p9'):
-            a[n] = z(H4, W4, 4 * c)
-        for n in ('a11', 'a12', 'a19'):
-            a[n] = z(H4, W4, 4 * c)
-        a['a13'] = z(H2, W2, 2 * c); a['a14'] = z(H2, W2, 2 * c); a['a15'] = z(H, W, c)
-        a['cat17'] = z(H, W, c // 2 + 1)
-        self.x_stage2, self.fine_seg = img(), img()
-        xs2 = Act(self.x_stage2.view(B, H, W, 1)); fs = Act(self.fine_seg.view(B, H, W, 1))
-        hallu, pm = a['cat11'].slice(0, 4 * c), a['cat11'].slice(4 * c, 4 * c)
-        a16 = a['cat17'].slice(0, c // 2)
-        fp = 'fine_generator.'
-        self.f_nodes_conv = [
-            N(P[fp + 'conv1'], self.f_in, a['f1'], 1, 2, 1, 'elu'),
-            N(P[fp + 'conv2_downsample'], a['f1'], a['f2'], 2, 1, 1, 'elu'),
-            N(P[fp + 'conv3'], a['f2'], a['f3'], 1, 1, 1, 'elu'),
-            N(P[fp + 'conv4_downsample'], a['f3'], a['f4'], 2, 1, 1, 'elu'),
-            N(P[fp + 'conv5'], a['f4'], a['f5'], 1, 1, 1, 'elu'),
-            N(P[fp + 'conv6'], a['f5'], a['f6'], 1, 1, 1, 'elu'),
-            N(P[fp + 'conv7_atrous'], a['f6'], a['f7'], 1, 2, 2, 'elu'),
-            N(P[fp + 'conv8_atrous'], a['f7'], a['f8'], 1, 4, 4, 'elu'),
-            N(P[fp + 'conv9_atrous'], a['f8'], a['f9'], 1, 8, 8, 'elu'),
-            N(P[fp + 'conv10_atrous'], a['f9'], hallu, 1, 16, 16, 'elu'),
-        ]
-        self.f_nodes_pm = [
-            N(P[fp + 'pmconv1'], self.f_in, a['p1'], 1, 2, 1, 'elu'),
-            N(P[fp + 'pmconv2_downsample'], a['p1'], a['p2'], 2, 1, 1, 'elu'),
-            N(P[fp + 'pmconv3'], a['p2'], a['p3'], 1, 1, 1, 'elu'),
-            N(P[fp + 'pmconv4_downsample'], a['p3'], a['p4'], 2, 1, 1, 'elu'),
-            N(P[fp + 'pmconv5'], a['p4'], a['p5'], 1, 1, 1, 'elu'),
-            N(P[fp + 'pmconv6'], a['p5'], a['p6'], 1, 1, 1, 'relu'),
-        ]
-        self.f_nodes_pm2 = [
-            N(P[fp + 'pmconv9'], a['ca'], a['p9'], 1, 1, 1, 'elu'),
-            N(P[fp + 'pmconv10'], a['p9'], pm, 1, 1, 1, 'elu'),
-        ]
-        self.f_nodes_merge = [
-            N(P[fp + 'allconv11'], a['cat11'], a['a11'], 1, 1, 1, 'elu'),
-            N(P[fp + 'allconv12'], a['a11'], a['a12'], 1, 1, 1, 'elu'),
-            N(P[fp + 'allconv19'], a['a12'], a['a19'], 1, 1, 1, 'elu'),
-            N(P[fp + 'allconv13'], a['a19'], a['a13'], 1, 1, 1, 'elu', shift=1),
-            N(P[fp + 'allconv14'], a['a13'], a['a14'], 1, 1, 1, 'elu'),
-            N(P[fp + 'allconv15'], a['a14'], a['a15'], 1, 1, 1, 'elu', shift=1),
-            N(P[fp + 'allconv16'], a['a15'], a16, 1, 1, 1, 'elu'),
-            N(P[fp + 'allconv17'], a['cat17'], xs2, 1, 1, 1, 'clamp'),
-            N(P[fp + 'allconv18'], a['cat17'], fs, 1, 1, 1, 'sigmoid'),
-        ]
-        self.f_pool = torch.zeros(B, 4 * c, device=device); self.pred2 = torch.zeros(B, 1, device=device)
-        self.a = a
-        self.attn = fg.contextul_attention.plan(B, H4, W4, 4 * c, device, (H, W))
-        # full-resolution scratch for the data gradients of the two fused-upsample convolutions
-        self.tmp_up = {}
-        # 4-channel padded carriers for the 1-channel head gradients
-        self.g_head = {n: z(H, W, 1) for n in ('c17', 'c18', 'f17', 'f18')}
+        levels, views = _buffers(c)
+        a = self.a = {n: Act(torch.zeros(B, H >> lv, W >> lv, ops.cpad(C), dtype=dt, device=device), C, 0) for lv, bufs in enumerate(levels) for n, C in bufs.items()}
+        a.update({n: a[src].slice(coff, C) for n, (src, coff, C) in views.items()})
+        for n in _IMAGES:
+            setattr(self, n, torch.zeros(B, 1, H, W, dtype=torch.float32, device=device))
+            a[n] = Act(getattr(self, n).view(B, H, W, 1))
+        self.node, self.chain = {}, {}
+        for gname, chains in _layers(c).items():
+            for chain, rows in chains.items():
+                for layer, src, dst, s, pad, d, act, *flags in rows:
+                    self.node['%s.%s' % (gname, layer)] = E.ConvNode(gen._pset_convs['%s.%s' % (gname, layer)], a[src], a[dst], s, pad, d, act, **(flags[0] if flags else {}))
+                self.chain[gname, chain] = tuple(self.node['%s.%s' % (gname, row[0])] for row in rows)
+        self.up = {n: _UpConcat(self.node[n], self.node[producer], cam_mode) for n, (_, producer, cam_mode) in _UP_CONCAT.items()}
+        self.head = {n: _Head(node, self.book) for n, node in self.node.items() if node.p.cout == 1}
+        self.c_pool, self.f_pool = torch.zeros(B, 4 * c, device=device), torch.zeros(B, 4 * c, device=device)
+        self.pred1, self.pred2 = torch.zeros(B, 1, device=device), torch.zeros(B, 1, device=device)
+        self.attn = gen.fine_generator.contextul_attention.plan(B, H // 4, W // 4, 4 * c, device, (H, W))
+        # x_stage1 / coarse_seg also feed the refinement generator: their seeds plus what its backward adds
+        self.d_xs1_total, self.d_cs_total = torch.zeros_like(self.x_stage1), torch.zeros_like(self.coarse_seg)
+        self.mask_img = None      # the last forward's mask
+        self.generation = 0       # forwards through the nn.Module API (_GeneratorFn refuses a stale backward)
+
+    def forward(self, prec, gname, *chains):
+        for chain in chains:
+            for n in self.chain[gname, chain]:
+                n.forward(prec)
 
 
 class Generator(nn.Module):
@@ -326,6 +363,8 @@ class Generator(nn.Module):
         self._eval_graphs = {}
         self.use_graph = os.environ.get('HV_GRAPH', '1') != '0'
         self._pset_convs = None
+        self.time_fine = None          # bench.py: a list that receives a pair of HIP events around each refinement-generator forward
+        self._fine_graph_keep = None
 
     # ---------------------------------------------------------------- parameters
     def paramset(self):
@@ -336,10 +375,12 @@ class Generator(nn.Module):
                 for n, m in g.named_children():
                     if isinstance(m, Conv2dBlock):
                         convs['%s.%s' % (gname, n)] = m.params('%s.%s' % (gname, n), cin_fwd=ops.cpad(m.cin))
-            # conv19 / conv20 read [up-sampled feature map | CAM]: their first 2c / 4c input channels also as a filter table of their own, so that the
+            # the _UP_CONCAT layers read [up-sampled feature map | CAM]: their first dx_c input channels also as a filter table of their own, so that the
             # forward can read the small map with the fused up-sampling and take the CAM channel in its epilogue (ConvNode.split, hv_conv_desc.x1)
-            for n, k2 in (('coarse_generator.conv19', 2 * self.cnum), ('coarse_generator.conv20', 4 * self.cnum)):
-                if n in convs and k2 % 32 == 0 and convs[n].cin == k2 + 1:
+            chains = _layers(self.cnum)['coarse_generator']
+            for n, (chain, _, _) in _UP_CONCAT.items():
+                k2 = chains[chain][0][-1]['dx_c']
+                if k2 % 32 == 0 and convs[n].cin == k2 + 1:
                     convs[n].split_k = k2
             self._pset_convs = convs
             cg, fg = self.coarse_generator, self.fine_generator
@@ -370,29 +411,20 @@ class Generator(nn.Module):
         x = x.contiguous().float(); mask = mask.contiguous().float(); CAM = CAM.contiguous().float()
         ratio = slice_ratio.to(device=dev, dtype=torch.float64).contiguous()
         P.mask_img = mask
-        cg, fg = self.coarse_generator, self.fine_generator
-        c = self.cnum
-        a = P.a
+        cg, cgn, a = self.coarse_generator, 'coarse_generator', P.a
         cam = Act(CAM.view(B, H, W, 1))
         # ---- coarse
-        ops.gen_input(x, None, mask, ratio, P.c_in, 0)
-        for n in P.c_nodes[:10]:
-            n.forward(prec)
+        ops.gen_input(x, None, mask, ratio, a['c_in'], 0)
+        P.forward(prec, cgn, 'enc')
         ops.gap_fc_sigmoid(a['c10'], cg.fc_height.weight, cg.fc_height.bias, P.c_pool, P.pred1)
-        P.c_nodes[10].forward(prec); P.c_nodes[11].forward(prec)
+        P.forward(prec, cgn, 'mid')
         # (split layers read c12 / c14 themselves: the up-sampled part of the concat buffer is then built by the backward, on its side stream)
-        if not P.c_nodes[12].split_forward(prec):
-            ops.copy_channels(a['c12'], a['cat20'].slice(0, 4 * c), mode=1)
-        ops.copy_channels(cam, a['cat20'].slice(4 * c, 1), mode=2)
-        for n in P.c_nodes[12:15]:
-            n.forward(prec)
-        if not P.c_nodes[15].split_forward(prec):
-            ops.copy_channels(a['c14'], a['cat19'].slice(0, 2 * c), mode=1)
-        ops.copy_channels(cam, a['cat19'].slice(2 * c, 1), mode=0)
-        for n in P.c_nodes[15:]:
-            n.forward(prec)
+        P.up['coarse_generator.conv20'].forward(cam, prec)
+        P.forward(prec, cgn, 'dec20')
+        P.up['coarse_generator.conv19'].forward(cam, prec)
+        P.forward(prec, cgn, 'dec19', 'heads')
         # ---- fine
-        tf = getattr(self, 'time_fine', None)
+        tf = self.time_fine
         if tf is not None and not torch.cuda.is_current_stream_capturing():     # bench.py: HIP events around the refinement generator
             tf.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             tf[-1][0].record()
@@ -405,30 +437,25 @@ class Generator(nn.Module):
 
     def _fine_forward(self, P, x, mask, ratio, prec, per_sample_mask=False):
         """FineGenerator.forward (reference models/inpaint_networks.py:169-232) over the plan's buffers: reads x, mask, P.coarse_seg, P.x_stage1."""
-        B, _, H, W = x.shape
-        fg, c, a = self.fine_generator, self.cnum, P.a
-        ops.gen_input(x, P.coarse_seg, mask, ratio, P.f_in, 1)
+        fg, fgn, a = self.fine_generator, 'fine_generator', P.a
+        ops.gen_input(x, P.coarse_seg, mask, ratio, a['f_in'], 1)
         # the dilated-conv branch and the attention branch only share their input: two streams (two branches of the step graph)
         side = E.branch_stream()
         main = torch.cuda.current_stream()
         if side is not None:
             side.wait_stream(main)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            for n in P.f_nodes_pm:
-                n.forward(prec)
+            P.forward(prec, fgn, 'pm_in', 'pm')
             P.attn.forward(a['p6'], mask, a['ca'], prec, want_argmax=True, per_sample_mask=per_sample_mask)
-            for n in P.f_nodes_pm2:
-                n.forward(prec)
-        for n in P.f_nodes_conv:
-            n.forward(prec)
+            P.forward(prec, fgn, 'pm_out')
+        P.forward(prec, fgn, 'dilated')
         if side is not None:
             main.wait_stream(side)
-        P.f_nodes_merge[0].forward(prec)
+        P.forward(prec, fgn, 'merge')
         ops.gap_fc_sigmoid(a['a11'], fg.fc_height.weight, fg.fc_height.bias, P.f_pool, P.pred2)
-        for n in P.f_nodes_merge[1:7]:
-            n.forward(prec)
-        ops.copy_channels(Act(P.x_stage1.view(B, H, W, 1)), a['cat17'].slice(c // 2, 1), mode=0)
-        P.f_nodes_merge[7].forward(prec); P.f_nodes_merge[8].forward(prec)
+        P.forward(prec, fgn, 'trunk')
+        ops.copy_channels(a['x_stage1'], a['cat17'].slice(a['a16'].C, 1), mode=0)
+        P.forward(prec, fgn, 'heads')
 
     def fine_forward_graph(self, P, x, mask, slice_ratio):
         """bench.py: the refinement generator's training forward alone as ONE captured hipGraph over the buffers of plan P (which a full
@@ -442,148 +469,86 @@ class Generator(nn.Module):
         self._fine_graph_keep = (x, mask, ratio)
         return g
 
-    def _tmp_up(self, P, node):
-        key = id(node)
-        if key not in P.tmp_up:
-            x = node.x
-            P.tmp_up[key] = Act(torch.zeros(x.B, x.H * 2, x.W * 2, x.ld, dtype=x.t.dtype, device=x.t.device), node.p.cin_fwd, 0)
-        return P.tmp_up[key]
-
-    def _head_backward(self, P, node, seed, gname, prec, book, mul_x=None):
-        """1-channel head: seed (B,1,H,W) -> padded carrier -> activation/bias gradient -> wgrad + dgrad."""
-        carrier = P.g_head[gname]                       # [B,H,W,4], channel 0 live
-        book.twins[id(node.y.t)] = carrier.t            # the head's output gradient lives in the carrier
-        pn = node.p
-        if carrier.f16 and seed.dtype == torch.float32 and seed.is_contiguous() and pn.bias is not None and node.use_bias:
-            # seed -> act' -> carrier -> bias gradient in one pass (was: copy, in-place act' pass, column sums)
-            ops.head_seed_backward(seed, node.y, Act(carrier.t, 4, 0), node.act, dbias=pn.bias.grad)
-            E.conv_backward(node, book, prec, premultiplied=True, dbias_done=True, mul_x=mul_x)
-            return
-        ops.copy_channels(Act(seed.view(P.B, P.H, P.W, 1)), carrier, mode=0)
-        E.conv_backward(node, book, prec, mul_x=mul_x)
-
     def run_backward(self, P, d_coarse_seg, d_fine_seg, d_x_stage1, d_x_stage2, d_pred1, d_pred2):
         """Gradients of a scalar loss wrt the six differentiable outputs -> .grad of every parameter.
         All seeds are dense fp32 device tensors shaped like the outputs (None = zero)."""
         prec = ops.precision_id(self.precision)
-        B, H, W, c = P.B, P.H, P.W, self.cnum
-        book = P.book
+        B, H, W = P.B, P.H, P.W
+        book, a, N, head = P.book, P.a, P.node, P.head
         book.reset()
-        a = P.a
         cg, fg = self.coarse_generator, self.fine_generator
+        coarse, fine = (lambda chain: reversed(P.chain['coarse_generator', chain])), (lambda chain: reversed(P.chain['fine_generator', chain]))
+        up19, up20 = P.up['coarse_generator.conv19'], P.up['coarse_generator.conv20']
         zero = lambda t, ref: torch.zeros_like(ref) if t is None else t.contiguous().float()
         d_fine_seg, d_x_stage2 = zero(d_fine_seg, P.fine_seg), zero(d_x_stage2, P.x_stage2)
         d_coarse_seg, d_x_stage1 = zero(d_coarse_seg, P.coarse_seg), zero(d_x_stage1, P.x_stage1)
         d_pred1, d_pred2 = zero(d_pred1, P.pred1), zero(d_pred2, P.pred2)
-        M = P.f_nodes_merge
-        # the concat inputs of the split layers (forward: never built) for their weight gradients: up-sampled now, beside the head kernels -- or, where the
-        # layer's weight gradient goes to the side stream, on that stream right in front of it: 35 + 20 us of copies (67 + 33 MB written) off the head of
-        # the backward's critical path
-        late_copies = []
-        wg_block_now = not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
-        for node, low, cat, k2 in ((P.c_nodes[15], a['c14'], a['cat19'], 2 * c), (P.c_nodes[12], a['c12'], a['cat20'], 4 * c)):
-            if node.split_forward(prec):
-                if wg_block_now:
-                    late_copies.append(lambda low=low, cat=cat, k2=k2: ops.copy_channels(low, cat.slice(0, k2), mode=1))
-                else:
-                    ops.copy_channels(low, cat.slice(0, k2), mode=1)
         # the refinement generator's weight gradients as ONE block on a side stream beside the coarse generator's whole backward (round 4):
         # they only feed the optimiser, and the coarse backward -- a chain of small launches that leave most of a CU's registers and LDS free -- does not
         # depend on them.  One fork and one join (per-layer forks cost more than they returned and are gone).  Measured against it, three
         # same-box pairs each: a first block launched before the two branches (three streams busy there) +0.13 ms; the coarse generator's own weight
         # gradients in two more blocks +0.14 ms -- both removed.
-        wg_block = not E.SERIAL and torch.cuda.current_stream().cuda_stream not in E.NO_FORK_STREAMS
-        book.defer_wgrad = bool(wg_block)
-        wg_side = E.named_stream('generator-wgrad-block', d_x_stage2.device) if wg_block else None
-        def launch_block():
-            # (several side streams with the launches dealt round-robin, HV_G_WGRAD_STREAMS 2 / 3, measured slower in round 5: 6.94 -> 6.98-7.36 ms)
-            wg_side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(wg_side):
-                for launch in book.deferred:
-                    launch()
-                self.paramset().fold_chain().flush()      # the side stream's last slab fold, on that stream (before the join)
-            book.deferred = []
+        wg = book.wgrad_block
+        wg.open(self.paramset(), d_x_stage2.device)
+        # the concat inputs of the split layers (forward: never built) for their weight gradients: up-sampled now, beside the head kernels -- or, where the
+        # layer's weight gradient goes to the side stream, on that stream right in front of it: 35 + 20 us of copies (67 + 33 MB written) off the head of
+        # the backward's critical path
+        wg.before_next_block(lambda: up19.materialise(prec))
+        wg.before_next_block(lambda: up20.materialise(prec))
         # ---- fine: heads
-        self._head_backward(P, M[7], d_x_stage2, 'f17', prec, book)
-        self._head_backward(P, M[8], d_fine_seg, 'f18', prec, book)
-        gcat17 = book.twin(a['cat17'])
-        # x_stage1 also feeds the fine heads (channel c/2 of cat17)
-        if 'd_xs1_total' not in P.__dict__:      # (setdefault(..., torch.zeros_like(...)) built and filled the default on every call: a fill kernel per step)
-            P.d_xs1_total, P.d_cs_total = torch.zeros_like(P.x_stage1), torch.zeros_like(P.coarse_seg)
-        d_xs1_total = P.d_xs1_total
-        ops.add_channels(Act(d_x_stage1.view(B, H, W, 1)), gcat17.slice(c // 2, 1), Act(d_xs1_total.view(B, H, W, 1)))
+        head['fine_generator.allconv17'].backward(d_x_stage2, book, prec)
+        head['fine_generator.allconv18'].backward(d_fine_seg, book, prec)
+        # x_stage1 also feeds the fine heads (the channel of cat17 behind allconv16's)
+        ops.add_channels(Act(d_x_stage1.view(B, H, W, 1)), book.twin(a['cat17']).slice(a['a16'].C, 1), Act(P.d_xs1_total.view(B, H, W, 1)))
         # pure links (single producer, single consumer): the consumer's data gradient applies the producer's act'
-        # (M[5] and M[3] read their input up-sampled: they link too where their data gradient can leave pooled, otherwise the chain breaks there)
-        E.conv_backward_chain([M[6], M[5], M[4], M[3], M[2], M[1]], book, prec, stop_before=M[0],
-                              tmp_full={id(M[5]): lambda: self._tmp_up(P, M[5]), id(M[3]): lambda: self._tmp_up(P, M[3])})
-        # a11 (allconv11's output, input of M[1]) also feeds the height head: both writers of its gradient apply elu'(a11)
-        pre11 = E.chain_link(M[1], M[0], book, prec)
+        # (allconv15 and allconv13 read their input up-sampled: they link too where their data gradient can leave pooled, otherwise the chain breaks there)
+        allconv11, allconv12 = N['fine_generator.allconv11'], N['fine_generator.allconv12']
+        E.conv_backward_chain(list(fine('trunk')), book, prec, stop_before=allconv11)
+        # a11 (allconv11's output, input of allconv12) also feeds the height head: both writers of its gradient apply elu'(a11)
+        pre11 = E.chain_link(allconv12, allconv11, book, prec)
         ops.gap_fc_sigmoid_backward(d_pred2, P.pred2, P.f_pool, fg.fc_height.weight, book.twin(a['a11']),
-                                    fg.fc_height.weight.grad, fg.fc_height.bias.grad, mul=(a['a11'], M[0].act) if pre11 else None)
+                                    fg.fc_height.weight.grad, fg.fc_height.bias.grad, mul=(a['a11'], allconv11.act) if pre11 else None)
         # cat11 = [conv10_atrous | pmconv10], both ELU: allconv11's data gradient applies elu' for both producers
-        E.conv_backward(M[0], book, prec, premultiplied=pre11, mul_x='elu')
+        E.conv_backward(allconv11, book, prec, premultiplied=pre11, mul_x='elu')
         # the two branches run concurrently; both end in the gradient of f_in: the attention branch stops before its first conv,
         # which is run after the join (assign / accumulate order of the shared buffer stays that of the single-stream schedule)
         side = E.branch_stream()
         main = torch.cuda.current_stream()
-        pm_rev = list(reversed(P.f_nodes_pm))
+        pmconv1, pmconv2 = N['fine_generator.pmconv1'], N['fine_generator.pmconv2_downsample']
         if side is not None:
             side.wait_stream(main)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-            E.conv_backward_chain(list(reversed(P.f_nodes_pm2)), book, prec, premultiplied_first=True)
+            E.conv_backward_chain(list(fine('pm_out')), book, prec, premultiplied_first=True)
             gp6 = book.twin(a['p6'])
             P.attn.backward(book.twin(a['ca']), gp6, book.mark(gp6), prec)
-            E.conv_backward_chain(pm_rev if side is None else pm_rev[:-1], book, prec, stop_before=None if side is None else pm_rev[-1])
+            E.conv_backward_chain([*fine('pm'), *(fine('pm_in') if side is None else ())], book, prec, stop_before=None if side is None else pmconv1)
             if side is not None:
                 self.paramset().fold_chain().flush()      # (weight gradients issued in line on the branch stream: their last slab fold, before the join)
-        E.conv_backward_chain(list(reversed(P.f_nodes_conv)), book, prec, premultiplied_first=True)
+        E.conv_backward_chain(list(fine('dilated')), book, prec, premultiplied_first=True)
         if side is not None:
             main.wait_stream(side)
-            E.conv_backward(pm_rev[-1], book, prec, premultiplied=E.chain_link(pm_rev[-2], pm_rev[-1], book, prec))
+            E.conv_backward(pmconv1, book, prec, premultiplied=E.chain_link(pmconv2, pmconv1, book, prec))
         # coarse_seg enters the fine generator as channel 1 of its input
-        d_cs_total = P.d_cs_total
-        ops.add_channels(Act(d_coarse_seg.view(B, H, W, 1)), book.twin(P.f_in).slice(1, 1), Act(d_cs_total.view(B, H, W, 1)))
-        if wg_block:
-            book.defer_wgrad = True      # (the first coarse layers' weight gradients join the side streams' queue behind this block: see below)
-            launch_block()
-            book.deferred.extend(late_copies)          # (in front of the coarse weight gradients that read them, on their stream)
+        ops.add_channels(Act(d_coarse_seg.view(B, H, W, 1)), book.twin(a['f_in']).slice(1, 1), Act(P.d_cs_total.view(B, H, W, 1)))
+        wg.launch(keep_collecting=True)      # (the first coarse layers' weight gradients queue up behind this block: see below)
         # ---- coarse
-        C = P.c_nodes
         # both heads read c16 (output of conv16, ELU): each applies elu'(c16) to its share of the gradient
-        self._head_backward(P, C[18], d_xs1_total, 'c17', prec, book, mul_x='elu')
-        self._head_backward(P, C[19], d_cs_total, 'c18', prec, book, mul_x='elu')
-        # conv19 / conv20 read [up-sampled c14 / c12 | CAM]: where the pooled data gradient serves the shape (fp16 mode) the gradient of the small tensor
-        # comes 2x2-pooled and times elu' straight from the conv's epilogue; otherwise full-resolution gradient + adjoint-of-up-sampling pass
-        def pooled(node, low):
-            node.pool_to = (low, 'elu')
-            if not node.pooled(book, prec, 'pool_to'):
-                node.pool_to = None
-            return node.pool_to is not None
-        p19 = pooled(C[15], a['c14'])
-        E.conv_backward_chain([C[17], C[16], C[15]], book, prec, premultiplied_first=True)
-        if not p19:
-            g14 = book.twin(a['c14'])
-            ops.copy_channels(book.twin(a['cat19']).slice(0, 2 * c), g14, mode=3, accumulate=book.mark(g14))
+        head['coarse_generator.conv17'].backward(P.d_xs1_total, book, prec, mul_x='elu')
+        head['coarse_generator.conv18'].backward(P.d_cs_total, book, prec, mul_x='elu')
         # Round 5: the coarse generator's first backward layers -- its heads and the 256 x 256 / 128 x 128 decoder, the most expensive weight
         # gradients of the chain -- hand their weight gradients to the side stream too (ONE more fork: it queues them behind the refinement generator's
         # block), so that the main stream walks these layers with data gradients only; the rest of the coarse backward keeps its weight gradients in line
         # (everything on the side stream made the block outlast the chain: +0.14 ms, round 4)
-        p20 = pooled(C[12], a['c12'])
-        E.conv_backward_chain([C[14], C[13], C[12]], book, prec, premultiplied_first=p19)
-        if not p20:
-            g12 = book.twin(a['c12'])
-            ops.copy_channels(book.twin(a['cat20']).slice(0, 4 * c), g12, mode=3, accumulate=book.mark(g12))
-        if wg_block:      # (behind the heads and the 256 x 256 / 128 x 128 decoder)
-            book.defer_wgrad = False
-            launch_block()
-        E.conv_backward_chain([C[11], C[10]], book, prec, premultiplied_first=p20, stop_before=C[9])
-        pre10 = E.chain_link(C[10], C[9], book, prec)      # c10 feeds conv11 and the height head: both apply elu'(c10)
+        p19 = up19.backward(coarse('dec19'), book, prec, True)
+        p20 = up20.backward(coarse('dec20'), book, prec, p19)
+        wg.launch()      # (behind the heads and the 256 x 256 / 128 x 128 decoder)
+        conv10, conv11 = N['coarse_generator.conv10_atrous'], N['coarse_generator.conv11']
+        E.conv_backward_chain(list(coarse('mid')), book, prec, premultiplied_first=p20, stop_before=conv10)
+        pre10 = E.chain_link(conv11, conv10, book, prec)      # c10 feeds conv11 and the height head: both apply elu'(c10)
         ops.gap_fc_sigmoid_backward(d_pred1, P.pred1, P.c_pool, cg.fc_height.weight, book.twin(a['c10']),
-                                    cg.fc_height.weight.grad, cg.fc_height.bias.grad, mul=(a['c10'], C[9].act) if pre10 else None)
-        E.conv_backward_chain(list(reversed(C[:10])), book, prec, premultiplied_first=pre10)
-        book.join()     # side-stream weight gradients
-        if wg_side is not None:
-            torch.cuda.current_stream().wait_stream(wg_side)
+                                    cg.fc_height.weight.grad, cg.fc_height.bias.grad, mul=(a['c10'], conv10.act) if pre10 else None)
+        E.conv_backward_chain(list(coarse('enc')), book, prec, premultiplied_first=pre10)
+        wg.join()     # side-stream weight gradients
         self.paramset().finish_backward(accumulate=False)
         self.paramset().attach_grads()
 
@@ -606,38 +571,34 @@ class Generator(nn.Module):
             o = tuple(t.clone() for t in outs)
         return o[0], o[1], o[2], o[3], flow, o[4], o[5]
 
-
-def _generator_eval_replay(self, x, mask, CAM, slice_ratio):
-    """Eval-mode forward as a captured hipGraph per input shape: the ~250 launches of a bs=1 inference call (launch-bound when
-    issued eagerly: the reference's eval loop runs ~130 of them per volume) become one graph launch.  Inputs are copied into
-    the graph's fixed buffers; the weights are re-prepared from the current parameters inside the graph on every replay."""
-    key = (tuple(x.shape), x.device.index, next(self.parameters()).data_ptr())
-    ent = self._eval_graphs.get(key)
-    if ent is None:
-        dev = x.device
-        static = [x.detach().to(dev, torch.float32).contiguous().clone(), mask.detach().to(dev, torch.float32).contiguous().clone(),
-                  CAM.detach().to(dev, torch.float32).contiguous().clone(), slice_ratio.detach().to(dev, torch.float64).contiguous().clone()]
-        self.run_forward(*static)                       # eager warm-up: plan buffers, weight tables, kernel attributes
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(g, stream=E.named_stream('capture', dev), capture_error_mode='thread_local'):
-                P = self.run_forward(*static)
-        except RuntimeError:
-            self.use_graph = False
+    def _eval_replay(self, x, mask, CAM, slice_ratio):
+        """Eval-mode forward as a captured hipGraph per input shape: the ~250 launches of a bs=1 inference call (launch-bound when
+        issued eagerly: the reference's eval loop runs ~130 of them per volume) become one graph launch.  Inputs are copied into
+        the graph's fixed buffers; the weights are re-prepared from the current parameters inside the graph on every replay."""
+        key = (tuple(x.shape), x.device.index, next(self.parameters()).data_ptr())
+        ent = self._eval_graphs.get(key)
+        if ent is None:
+            dev = x.device
+            static = [x.detach().to(dev, torch.float32).contiguous().clone(), mask.detach().to(dev, torch.float32).contiguous().clone(),
+                      CAM.detach().to(dev, torch.float32).contiguous().clone(), slice_ratio.detach().to(dev, torch.float64).contiguous().clone()]
+            self.run_forward(*static)                       # eager warm-up: plan buffers, weight tables, kernel attributes
             torch.cuda.synchronize(dev)
-            return self.run_forward(x, mask, CAM, slice_ratio)
-        if len(self._eval_graphs) >= 8:                 # a handful of shapes at most (bs=1 loop, batched stages)
-            self._eval_graphs.clear()
-        ent = self._eval_graphs[key] = (g, static, P)
-    g, static, P = ent
-    for dst, src in zip(static, (x, mask, CAM, slice_ratio)):
-        dst.copy_(src, non_blocking=True)
-    g.replay()
-    return P
-
-
-Generator._eval_replay = _generator_eval_replay
+            g = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(g, stream=E.named_stream('capture', dev), capture_error_mode='thread_local'):
+                    P = self.run_forward(*static)
+            except RuntimeError:
+                self.use_graph = False
+                torch.cuda.synchronize(dev)
+                return self.run_forward(x, mask, CAM, slice_ratio)
+            if len(self._eval_graphs) >= 8:                 # a handful of shapes at most (bs=1 loop, batched stages)
+                self._eval_graphs.clear()
+            ent = self._eval_graphs[key] = (g, static, P)
+        g, static, P = ent
+        for dst, src in zip(static, (x, mask, CAM, slice_ratio)):
+            dst.copy_(src, non_blocking=True)
+        g.replay()
+        return P
 
 
 class _GeneratorFn(torch.autograd.Function):
@@ -647,7 +608,7 @@ class _GeneratorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, gen, plan, *outs):
         ctx.gen, ctx.plan = gen, plan
-        plan.generation = ctx.generation = getattr(plan, 'generation', 0) + 1
+        plan.generation = ctx.generation = plan.generation + 1
         return tuple(t.clone() for t in outs)
 
     @staticmethod

@@ -1001,3 +1001,171 @@ def test_attention_plan_refuses_to_allocate_inside_a_stream_capture(attention_ca
     assert set(plan.owned) == held and not torch.cuda.is_current_stream_capturing()
     got = _attention_run(plan, c, 'fp32')
     assert plan.route == 'conv' and torch.equal(got[0], c['fp32'][0]) and torch.equal(got[1], c['fp32'][1])
+
+
+# ---------------------------------------------------------------- generator plan: named layers, one owner per concat layer / head / weight-gradient block
+UP19, UP20 = 'coarse_generator.conv19', 'coarse_generator.conv20'
+
+
+def _gen_net(sd, ngf, prec):
+    from hvgan.models.inpaint_networks import Generator
+    net = Generator({'input_dim': 1, 'ngf': ngf}, True)
+    net.load_state_dict(sd)
+    net.cuda().train()
+    net.precision = prec
+    return net
+
+
+def _gen_call(net, case, sd=None):
+    """One training forward + backward of the explicit executor -> (plan, {name: clone} of the six outputs and every parameter gradient)."""
+    if sd is not None:
+        net.load_state_dict(sd)
+    P = net.run_forward(*case['args'], training=True)
+    net.run_backward(P, *case['seeds'])
+    torch.cuda.synchronize()
+    got = {n: getattr(P, n).clone() for n in ('coarse_seg', 'fine_seg', 'x_stage1', 'x_stage2', 'pred1', 'pred2')}
+    got.update({'grad ' + k: p.grad.clone() for k, p in net.named_parameters()})
+    return P, got
+
+
+def _gen_same_bits(got, want, what):
+    assert got.keys() == want.keys()
+    for k, w in want.items():
+        assert torch.isfinite(w).all() and w.abs().max().item() > 0, (what, k)
+        assert torch.equal(got[k], w), (what, k, (got[k].float() - w.float()).abs().max().item())
+
+
+def _takes_split_and_pooled(net, size):
+    """Asks the dispatch, as the executors do: does a B = 2 plan of `net` at size x size read both concat layers in the split form, and do both data
+    gradients leave pooled?"""
+    dev = torch.device('cuda:0')
+    net.paramset().prep(dev, power_iter=False)      # (the split form reads a filter table that exists once the parameter set is on the device)
+    P = net._plan(2, size, size, dev)
+    P.book.reset()
+    return all(up.node.split_forward(net.precision) and up.node.pooled(P.book, net.precision, 'pool_to') for up in P.up.values())
+
+
+# The dispatch serves the split form and the pooled data gradient of both concat layers from 8 x 8 on (asked of it size by size), but below 64 x 64 the fp16-mode
+# generator does not run at all: the attention block is then off its GEMM routes (h * w % 32) and its score convolution with per-sample filters is refused
+# (HV_ERR_UNSUPPORTED, nothing launched; the same before the plan had named layers).  64 is the smallest size divisible by 8 at which both facts hold AND the
+# generator runs.
+GEN_FP16_SIZE = 64
+
+
+@pytest.fixture(scope='module')
+def gen_cases():
+    """'fp32': the G1 mini generator (ngf 4, B = 2, 64 x 64: no split form, no pooled data gradient).  'fp16': ngf 16 -- the width Pix2PixModel gives the generator
+    that tests/test_step_gpu.make_opt's options build, and the only one whose concat layers (32 / 64 + 1 channels) have the split form at all -- at B = 2 and
+    GEN_FP16_SIZE.  Each with its
+    state dict, inputs, seeds and what a freshly constructed network gives for one call under the default scheduling."""
+    from hvgan.models.inpaint_networks import Generator
+    dev = torch.device('cuda:0')
+    g1 = load_golden('g1_generator_mini')
+    cases = {'fp32': dict(ngf=4, size=64, sd=g1['sd'], args=[g1[k].to(dev) for k in ('x', 'mask', 'cam', 'ratio')])}
+    torch.manual_seed(11)
+    sd = {k: v.clone() for k, v in Generator({'input_dim': 1, 'ngf': 16}, True).state_dict().items()}
+    size = GEN_FP16_SIZE
+    assert _takes_split_and_pooled(_gen_net(sd, 16, 'fp16'), size) and _takes_split_and_pooled(_gen_net(sd, 16, 'fp16'), 8)
+    g = torch.Generator().manual_seed(12)
+    mask = torch.zeros(2, 1, size, size)
+    mask[:, :, 3 * size // 8:5 * size // 8] = 1
+    cases['fp16'] = dict(ngf=16, size=size, sd=sd, args=[(torch.rand(2, 1, size, size, generator=g) * 2 - 1).to(dev), mask.to(dev),
+                                                        torch.rand(2, 1, size, size, generator=g).to(dev), torch.rand(2, generator=g, dtype=torch.float64).to(dev)])
+    for prec, c in cases.items():
+        g = torch.Generator().manual_seed(13)
+        c['seeds'] = [torch.randn(2, 1, c['size'], c['size'], generator=g).to(dev) for _ in range(4)] + [torch.randn(2, 1, generator=g).to(dev) for _ in range(2)]
+        c['fresh'] = _gen_call(_gen_net(c['sd'], c['ngf'], prec), c)[1]
+    return cases
+
+
+def test_generator_plan_and_its_owners_are_closed():
+    """G1 mini generator (ngf 4, B = 2, 64 x 64, fp32): every declared slot of the plan, of each concat-layer owner and of each head owner has a value once
+    _plan() returns; a training forward + backward and an eval forward can add none, because none of these objects has a __dict__ (assigning an undeclared
+    attribute raises).  By construction this cannot pass before the plan declared its slots: it then grew mask_img, the summed-seed buffers and
+    generation as the executors ran, and had neither `up` nor `head`."""
+    g = load_golden('g1_generator_mini')
+    net = _gen(g)
+    dev = torch.device('cuda:0')
+    args = [g[k].to(dev) for k in ('x', 'mask', 'cam', 'ratio')]
+    net.paramset()
+    P = net._plan(2, 64, 64, dev)
+    objs = [P, P.book.wgrad_block] + list(P.up.values()) + list(P.head.values())
+    assert len(P.up) == 2 and len(P.head) == 4
+    declared = lambda: all(hasattr(o, a) for o in objs for a in type(o).__slots__)
+    assert declared()
+    assert net.run_forward(*args, training=True) is P
+    net.run_backward(P, *[g['coef'][str(i)].to(dev) for i in range(6)])
+    net.eval()
+    assert net.run_forward(*args, training=False) is P
+    torch.cuda.synchronize()
+    assert declared()
+    for o in objs:
+        assert not hasattr(o, '__dict__'), type(o).__name__
+        with pytest.raises(AttributeError):
+            o.undeclared = 0
+
+
+@pytest.mark.parametrize('prec', ['fp16', 'fp32'])
+def test_one_generator_plan_repeats_a_fresh_networks_call_bit_for_bit(prec, gen_cases):
+    """Three run_forward + run_backward calls on ONE network (one plan), the same state dict reloaded before each: outputs, pred1 / pred2 and every parameter
+    gradient of each call are bit for bit those of a freshly constructed network's single call, and the gradient book holds as many twins after the third call
+    as after the first -- nothing is carried from one call to the next (a queue of deferred weight gradients, a pooled answer, a re-registered twin).  fp16:
+    both concat layers take the split forward and the pooled data gradient (asserted); fp32 at G1's shape: neither exists, so the materialised concat and the
+    full-resolution gradient + adjoint copy run (asserted)."""
+    c = gen_cases[prec]
+    net = _gen_net(c['sd'], c['ngf'], prec)
+    twins = []
+    for i in range(3):
+        P, got = _gen_call(net, c, sd=c['sd'])
+        _gen_same_bits(got, c['fresh'], (prec, i))
+        twins.append(len(P.book.twins))
+        for up in P.up.values():
+            assert up.node.split_forward(prec) == (prec == 'fp16') and up.pooled is (prec == 'fp16'), (prec, i, up.node.p.name, up.pooled)
+    assert len(net._plans) == 1 and twins[2] == twins[0], twins
+
+
+def test_generator_weight_gradients_in_line_and_on_the_side_stream_agree(gen_cases, monkeypatch):
+    """The fp16 case above under engine.SERIAL (one stream: every weight gradient in line where it is issued, the refinement generator's two branches one after the
+    other) against the default scheduling (weight-gradient blocks on the side stream, two branch streams): fresh networks, the same state dict.  The two
+    schedules do NOT give equal bits, and did not before the plan had named layers either (measured there on this very case: the outputs agree bit for bit, the
+    parameter gradients of both generators differ in their last bits, e.g. coarse conv1's bias by 1.9e-3 absolute on values of order 1).  So, with no tolerance
+    of this test's own: both runs' parameter gradients against the fp32-mode gradient of the same weights, inputs and seeds at the fp16 gradient gates of
+    DESIGN.md section 2 -- relative L2 of 6 % for matrices and 16 % for pixel-sum vectors (biases) -- and the outputs of the two runs bit for bit."""
+    from hvgan import engine
+    c = gen_cases['fp16']
+    ref = _gen_call(_gen_net(c['sd'], c['ngf'], 'fp32'), c)[1]
+    monkeypatch.setattr(engine, 'SERIAL', True)
+    P, serial = _gen_call(_gen_net(c['sd'], c['ngf'], 'fp16'), c)
+    assert engine.branch_stream() is None and all(up.pooled for up in P.up.values())
+    worst = {}
+    for what, got in (('default', c['fresh']), ('SERIAL', serial)):
+        for k, r in ref.items():
+            if k.startswith('grad '):
+                kind = 'matrix' if r.dim() > 1 else 'vector'
+                assert r.norm().item() > 0, k
+                rel = (got[k].double() - r.double()).norm().item() / r.double().norm().item()
+                worst[what, kind] = max(worst.get((what, kind), (0.0, k)), (rel, k))
+    print('relative L2 against the fp32-mode gradient, worst per kind:', worst)
+    for (what, kind), (rel, k) in worst.items():
+        assert rel <= (0.06 if kind == 'matrix' else 0.16), (what, kind, k, rel)
+    for k in ('coarse_seg', 'fine_seg', 'x_stage1', 'x_stage2', 'pred1', 'pred2'):
+        assert torch.equal(serial[k], c['fresh'][k]), k
+
+
+def test_generator_refuses_a_stale_backward_through_the_module_api():
+    """Two module calls of the same shape share one activation plan: backward() on the first call's outputs raises (its activations are overwritten), on the
+    second's it runs.  The count of forwards is a declared attribute of the plan."""
+    g = load_golden('g1_generator_mini')
+    net = _gen(g)
+    net.train()
+    dev = torch.device('cuda:0')
+    args = [g[k].to(dev) for k in ('x', 'mask', 'cam', 'ratio')]
+    first, second = net(*args), net(*args)
+    P = net._plan(2, 64, 64, dev)
+    assert len(net._plans) == 1 and P.generation == 2
+    with pytest.raises(RuntimeError, match='later forward pass of the same shape'):
+        first[2].sum().backward()
+    second[2].sum().backward()
+    torch.cuda.synchronize()
+    grads = [p.grad for k, p in net.named_parameters() if k.startswith('coarse_generator.conv1.')]
+    assert grads and all(torch.isfinite(q).all() and q.abs().max().item() > 0 for q in grads)
