@@ -44,8 +44,15 @@ extern "C" size_t hv_norm_workspace_bytes(int B, int HW, int C) {
     size_t pa = 0, pb = 0;
     for (int vec = 0; vec < 2; ++vec) {
         if (vec ? !n_vec_ok(C) : !(n_pow2(C) && C <= 256)) continue;
-        const NormPlan a = norm_plan(B, HW, C, HV_NORM_BATCH, 1, vec), b = norm_plan(B, HW, C, HV_NORM_INSTANCE, 1, vec);
-        if ((size_t)a.G * a.nchunk > pa) pa = (size_t)a.G * a.nchunk;
+        // batch norm: every split of the batch into equal groups (hv_norm_desc.groups is not an argument here).  The cap on the chunks per group depends on G,
+        // so a split can keep more chunks in all than the one-group and the per-image plan, which the cap shrinks (B = 12, HW = 209 * 209, C = 8, groups = 4,
+        // scalar path: 4 * 512, just at its cap, against 512 and 12 * 152)
+        for (int g = 1; g <= B; ++g) {
+            if (B % g) continue;
+            const NormPlan a = norm_plan(B, HW, C, HV_NORM_BATCH, g, vec);
+            if ((size_t)a.G * a.nchunk > pa) pa = (size_t)a.G * a.nchunk;
+        }
+        const NormPlan b = norm_plan(B, HW, C, HV_NORM_INSTANCE, 1, vec);
         if ((size_t)b.G * b.nchunk > pb) pb = (size_t)b.G * b.nchunk;
     }
     return (pa > pb ? pa : pb) * 2 * C * sizeof(double) + (size_t)B * 2 * C * sizeof(float) + 64;

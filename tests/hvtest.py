@@ -23,6 +23,15 @@ def to_act(x_nchw, CP=None, dtype=torch.float32):
     return ops.Act(t.to(dev()).to(dtype).contiguous(), C, 0)
 
 
+def to_act_view(x_nchw, ld=None, coff=0, fill=0.0):
+    """CPU (B,C,H,W) of the storage dtype -> device Act over channels [coff, coff + C) of an ld-wide buffer whose other channels hold `fill`."""
+    B, C, H, W = x_nchw.shape
+    ld = C if ld is None else ld
+    t = torch.full((B, H, W, ld), fill, dtype=x_nchw.dtype)
+    t[..., coff:coff + C] = x_nchw.permute(0, 2, 3, 1)
+    return ops.Act(t.to(dev()).contiguous(), C, coff)
+
+
 def from_act(a):
     """device Act -> CPU (B,C,H,W)."""
     return a.t[..., a.coff:a.coff + a.C].permute(0, 3, 1, 2).contiguous().float().cpu()
