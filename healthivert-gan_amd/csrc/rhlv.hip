@@ -10,14 +10,29 @@
 //   rhlv_slice_kernel    grid (S, views, N): thirds of the generated vertebra's column extent, centre columns, rescale ratios,
 //                        thresholded integer sums per (all | pre | mid | post) x (generated | original)
 //   rhlv_final_kernel    grid (1, views, N): means over the slices, the four RHLVs and the relative height of the original
+// and, for the hv_rhlv_maps entries only, the per-column picture those numbers are folded from (two more launches, any views and pairs):
+//   rhlv_map_kernel      grid (S, views, N): one row per slice of the whole-slice ("all") heights and what was selected from them
+//   rhlv_profile_kernel  grid (ceil((S + C) / 256), views, N): one lane per column / per slice, the selected heights averaged along the other axis
 // A view (RhlvView) is a way to walk the one table: the sagittal view takes slices z with columns w, the coronal view slices w with columns z
 // (read strided: the table is at most 2*Z*W ints), and each carries its script's ratio arithmetic.  N > 1 is the batched form: blockIdx.z
 // picks the volume pair and its slab of the workspace.
 // All floating-point steps are doubles in the reference's operation order (-ffp-contract=off); the only deviation is that a
 // slice's selected heights are summed as integers and scaled once (sum(c)*r instead of sum(c*r)): ~1e-16 relative.
+//
+// A map row (slice s of a view, column c), from the slice's RhlvMapRec {ratio_all, thr_f, thr_l, t1, t2, on}:
+//   height_fake[s][c]  = cnt_fake[s][c] * ratio_all          (all_height_fake * all_scale_ratio, :93)
+//   height_label[s][c] = cnt_label[s][c]                     (:70)
+//   flags[s][c]        = region (bits 0-1: 0 pre c < t1, 1 mid c < t2, 2 post) | sel_f << 2 | sel_l << 3 | 1 << 4 (the script visits the slice),
+//                        sel_f = height_fake > thr_f (:99), sel_l = height_label > thr_l (:100)
+//   loss[s][c]         = (height_fake - height_label) / (height_fake + 1e-6) where sel_f, else NaN    (:139 per column)
+// A slice the script does not visit (outside [lo, hi), or empty in either volume) is a row of NaN losses, zero heights and zero flags.
+// A profile is {sum of selected height_fake / their number, the same of height_label, (pf - pl) / (pf + 1e-6)}, NaN where nothing is
+// selected; each lane walks its slices or columns in ascending order and recomputes the heights from the table, so the profiles do not
+// depend on which maps were asked for, on the launch shape or on the batch.
 #include "hv_common.h"
 
 struct RhlvRec { double ratio[4]; long long Sf[4], nf[4], Sl[4], nl[4], raises; };
+struct RhlvMapRec { double ratio, thr_f, thr_l; int t1, t2, on, pad; };   // what rhlv_map_kernel / rhlv_profile_kernel need of a slice
 
 struct RhlvView {
     int S, C;                  // slices, columns per slice
@@ -31,6 +46,7 @@ struct RhlvPlan {
     RhlvView view[2];
     int nviews, W, Z;
     long long cnt, pair_bytes;     // byte offset of cnt[2][Z][W]; size of one pair's slab
+    long long maprecs[2];          // per view: byte offset of RhlvMapRec[S] (the hv_rhlv_maps entries only)
 };
 
 __device__ __forceinline__ char* rhlv_slab(char* ws, const RhlvPlan& P) { return ws + (long long)blockIdx.z * P.pair_bytes; }
@@ -160,6 +176,8 @@ __device__ __forceinline__ int rhlv_block_max(int v, long long* sh) {
     return (int)sh[0];
 }
 
+// MAPS: also leave the slice's RhlvMapRec (the hv_rhlv_maps entries); the other entries run the instantiation without it
+template <bool MAPS>
 __global__ __launch_bounds__(256) void rhlv_slice_kernel(char* __restrict__ ws, RhlvPlan P) {
     __shared__ long long sh[256];
     const RhlvView& V = P.view[blockIdx.y];
@@ -169,12 +187,14 @@ __global__ __launch_bounds__(256) void rhlv_slice_kernel(char* __restrict__ ws, 
     const int* tot = (const int*)(rhlv_slab(ws, P) + V.tot);
     const int* params = (const int*)(rhlv_slab(ws, P) + V.params);
     RhlvRec* rec = (RhlvRec*)(rhlv_slab(ws, P) + V.recs) + z;
+    RhlvMapRec* mrec = MAPS ? (RhlvMapRec*)(rhlv_slab(ws, P) + P.maprecs[blockIdx.y]) + z : nullptr;
     const int* cf = (const int*)(rhlv_slab(ws, P) + P.cnt) + (long long)z * V.ss;     // column w of this slice: cf[w * sc]
     const int* cl = cf + (long long)P.Z * P.W;
     const bool on = z >= params[0] && z < params[1] && tot[z] > 0 && tot[Z + z] > 0 && params[4];
     if (!on) {
         if (tid < 4) { rec->ratio[tid] = 1.0; rec->Sf[tid] = rec->nf[tid] = rec->Sl[tid] = rec->nl[tid] = 0; }
         if (tid == 0) rec->raises = 0;
+        if (MAPS && tid == 0) { mrec->ratio = 1.0; mrec->thr_f = mrec->thr_l = 0.0; mrec->t1 = mrec->t2 = mrec->on = mrec->pad = 0; }
         return;
     }
     // column statistics of the generated and the original vertebra
@@ -212,6 +232,7 @@ __global__ __launch_bounds__(256) void rhlv_slice_kernel(char* __restrict__ ws, 
     const long long raises = V.coronal && (t1 <= 0 || t2 <= t1);
     const double center_f = (double)center_f_i * ratio[0];
     const double thr_f = center_f * V.thr, thr_l = (double)center_l * V.thr;
+    if (MAPS && tid == 0) { mrec->ratio = ratio[0]; mrec->thr_f = thr_f; mrec->thr_l = thr_l; mrec->t1 = t1; mrec->t2 = t2; mrec->on = 1; mrec->pad = 0; }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         long long Sf = 0, nf = 0, Sl = 0, nl = 0;
@@ -259,8 +280,90 @@ __global__ void rhlv_final_kernel(char* __restrict__ ws, RhlvPlan P, double* __r
     if (out_len > 14) { out[14] = (double)raises; out[15] = 0.0; }
 }
 
-// One pair's workspace slab: recs per view | cnt[2][Z][W] | tot[2][S] per view | params[8] per view; view[0] is the sagittal one when asked for
-static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal, const hv_rhlv_view* coronal) {
+// Output pointers of one view for n_pairs pairs, each NULL = not wanted: loss / hf / hl / flags [N][S][C], colp [N][3][C], slicep [N][3][S],
+// range [N][2]
+struct RhlvMapOut { double *loss, *hf, *hl; unsigned char* flags; double *colp, *slicep; int* range; };
+struct RhlvMapOuts { RhlvMapOut view[2]; };
+
+__global__ __launch_bounds__(256) void rhlv_map_kernel(const char* __restrict__ ws, RhlvPlan P, RhlvMapOuts O) {
+    const RhlvView& V = P.view[blockIdx.y];
+    const RhlvMapOut& o = O.view[blockIdx.y];
+    const int s = blockIdx.x, S = V.S, C = V.C;
+    if (s >= S) return;                                  // the grid is as wide as the longer view
+    const char* slab = ws + (long long)blockIdx.z * P.pair_bytes;
+    const RhlvMapRec r = ((const RhlvMapRec*)(slab + P.maprecs[blockIdx.y]))[s];
+    const int* cf = (const int*)(slab + P.cnt) + (long long)s * V.ss;
+    const int* cl = cf + (long long)P.Z * P.W;
+    const long long sc = V.sc, row = ((long long)blockIdx.z * S + s) * C;
+    if (s == 0 && threadIdx.x == 0 && o.range) {
+        const int* params = (const int*)(slab + V.params);
+        o.range[2 * (long long)blockIdx.z] = params[0];
+        o.range[2 * (long long)blockIdx.z + 1] = params[1];
+    }
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double hf = 0.0, hl = 0.0, loss = __builtin_nan("");
+        unsigned flags = 0;
+        if (r.on) {
+            hf = (double)cf[c * sc] * r.ratio;
+            hl = (double)cl[c * sc];
+            const bool sel_f = hf > r.thr_f, sel_l = hl > r.thr_l;
+            flags = (c < r.t1 ? 0u : c < r.t2 ? 1u : 2u) | (sel_f ? 4u : 0u) | (sel_l ? 8u : 0u) | 16u;
+            if (sel_f) loss = (hf - hl) / (hf + 1e-6);
+        }
+        if (o.hf) o.hf[row + c] = hf;
+        if (o.hl) o.hl[row + c] = hl;
+        if (o.loss) o.loss[row + c] = loss;
+        if (o.flags) o.flags[row + c] = (unsigned char)flags;
+    }
+}
+
+// lanes [0, C): column c over the slices of [lo, hi); lanes [C, C + S): slice s over its columns.  Sequential sums in ascending order.
+__global__ __launch_bounds__(256) void rhlv_profile_kernel(const char* __restrict__ ws, RhlvPlan P, RhlvMapOuts O) {
+    const RhlvView& V = P.view[blockIdx.y];
+    const RhlvMapOut& o = O.view[blockIdx.y];
+    const int S = V.S, C = V.C;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S + C) return;
+    const bool column = i < C;
+    double* out = column ? o.colp : o.slicep;
+    if (!out) return;
+    const char* slab = ws + (long long)blockIdx.z * P.pair_bytes;
+    const RhlvMapRec* recs = (const RhlvMapRec*)(slab + P.maprecs[blockIdx.y]);
+    const int* params = (const int*)(slab + V.params);
+    const int* cf = (const int*)(slab + P.cnt);
+    const int* cl = cf + (long long)P.Z * P.W;
+    const long long ss = V.ss, sc = V.sc;
+    double sf = 0.0, sl = 0.0;
+    long long nf = 0, nl = 0;
+    if (column) {
+        for (int s = params[0]; s < params[1]; ++s) {
+            const RhlvMapRec r = recs[s];
+            if (!r.on) continue;
+            const double hf = (double)cf[s * ss + i * sc] * r.ratio, hl = (double)cl[s * ss + i * sc];
+            if (hf > r.thr_f) { sf += hf; ++nf; }
+            if (hl > r.thr_l) { sl += hl; ++nl; }
+        }
+    } else {
+        const int s = i - C;
+        const RhlvMapRec r = recs[s];
+        if (r.on)
+            for (int c = 0; c < C; ++c) {
+                const double hf = (double)cf[s * ss + c * sc] * r.ratio, hl = (double)cl[s * ss + c * sc];
+                if (hf > r.thr_f) { sf += hf; ++nf; }
+                if (hl > r.thr_l) { sl += hl; ++nl; }
+            }
+    }
+    const int n = column ? C : S, j = column ? i : i - C;
+    const double pf = nf > 0 ? sf / (double)nf : __builtin_nan(""), pl = nl > 0 ? sl / (double)nl : __builtin_nan("");
+    out += (long long)blockIdx.z * 3 * n;
+    out[j] = pf;
+    out[n + j] = pl;
+    out[2 * n + j] = (pf - pl) / (pf + 1e-6);
+}
+
+
+// One pair's workspace slab: recs per view | cnt[2][Z][W] | tot[2][S] per view | params[8] per view | maprecs per view (maps only); view[0] is the sagittal one when asked for
+static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal, const hv_rhlv_view* coronal, bool maps = false) {
     RhlvPlan P = {};
     P.W = W; P.Z = Z;
     if (views & HV_RHLV_SAGITTAL) { RhlvView& V = P.view[P.nviews++]; V.S = Z; V.C = W; V.ss = W; V.sc = 1; V.coronal = 0; }
@@ -275,6 +378,10 @@ static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal,
         const hv_rhlv_view* a = V.coronal ? coronal : sagittal;
         if (a) { V.divisor = a->length_divisor; V.lo = a->lo; V.hi = a->hi; V.thr = a->height_threshold; }
     }
+    for (int i = 0; i < P.nviews; ++i) {
+        P.maprecs[i] = -1;
+        if (maps) { P.maprecs[i] = off; off += (long long)P.view[i].S * sizeof(RhlvMapRec); }
+    }
     P.pair_bytes = (off + 7) & ~7LL;
     return P;
 }
@@ -282,7 +389,7 @@ static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal,
 // the launch sequence of every entry: one pair passed by value (pairs == NULL, n_pairs 1) or a device table of n_pairs pointer pairs
 static int rhlv_run(const void* fake, const void* label, const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h,
                     long long stride_w, long long stride_z, int H, float label_index, const RhlvPlan& P, double* out, int out_len, void* workspace,
-                    hipStream_t s) {
+                    hipStream_t s, const RhlvMapOuts* maps = nullptr) {
     char* ws = (char*)workspace;
     const void* const* pp = (const void* const*)pairs;
     const bool zfast = stride_z == 1 && stride_w != 1;   // z fastest in memory: lanes along z
@@ -309,10 +416,17 @@ static int rhlv_run(const void* fake, const void* label, const void* pairs, cons
     }
     hipLaunchKernelGGL(rhlv_range_kernel, dim3(1, P.nviews, n_pairs), dim3(64), 0, s, ws, P);
     HV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rhlv_slice_kernel, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, ws, P);
+    if (maps) hipLaunchKernelGGL(rhlv_slice_kernel<true>, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, ws, P);
+    else hipLaunchKernelGGL(rhlv_slice_kernel<false>, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, ws, P);
     HV_LAUNCH_CHECK();
     hipLaunchKernelGGL(rhlv_final_kernel, dim3(1, P.nviews, n_pairs), dim3(64), 0, s, ws, P, out, out_len);
     HV_LAUNCH_CHECK();
+    if (maps) {
+        hipLaunchKernelGGL(rhlv_map_kernel, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, (const char*)ws, P, *maps);
+        HV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rhlv_profile_kernel, dim3(hv_cdiv((long long)P.W + P.Z, 256), P.nviews, n_pairs), dim3(256), 0, s, (const char*)ws, P, *maps);
+        HV_LAUNCH_CHECK();
+    }
     return HV_OK;
 }
 
@@ -365,4 +479,52 @@ extern "C" int hv_rhlv_views_batch(const void* pairs, const float* label_indices
     if (!workspace || workspace_bytes < hv_rhlv_views_workspace_bytes(W, Z, views, n_pairs) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
     return rhlv_run(nullptr, nullptr, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, 0.f,
                     rhlv_plan(W, Z, views, h_sagittal, h_coronal), out, 16, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t hv_rhlv_maps_workspace_bytes(int W, int Z, int views, int n_pairs) {
+    if (W <= 0 || Z <= 0 || n_pairs <= 0 || views < 1 || views > (HV_RHLV_SAGITTAL | HV_RHLV_CORONAL)) return 0;
+    return (size_t)rhlv_plan(W, Z, views, nullptr, nullptr, true).pair_bytes * n_pairs;
+}
+
+// the requested views' output pointers in plan order (sagittal first)
+static RhlvMapOuts rhlv_map_outs(int views, const hv_rhlv_map_out* sagittal, const hv_rhlv_map_out* coronal) {
+    RhlvMapOuts O = {};
+    int n = 0;
+    for (int bit = HV_RHLV_SAGITTAL; bit <= HV_RHLV_CORONAL; bit <<= 1) {
+        if (!(views & bit)) continue;
+        const hv_rhlv_map_out* a = bit == HV_RHLV_SAGITTAL ? sagittal : coronal;
+        RhlvMapOut& o = O.view[n++];
+        if (a) {
+            o.loss = a->loss; o.hf = a->height_fake; o.hl = a->height_label; o.flags = a->flags;
+            o.colp = a->column_profile; o.slicep = a->slice_profile; o.range = a->range;
+        }
+    }
+    return O;
+}
+
+extern "C" int hv_rhlv_maps(const void* fake, const void* label, int dtype, long long stride_h, long long stride_w, long long stride_z, int H, int W,
+                            int Z, float label_index, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
+                            const hv_rhlv_map_out* h_sagittal_out, const hv_rhlv_map_out* h_coronal_out, double* out, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (!fake || !label || !out || H <= 0 || W <= 0 || Z <= 0 || (dtype != 0 && dtype != 1) || !rhlv_views_ok(views, h_sagittal, h_coronal))
+        return HV_ERR_ARG;
+    if (Z > 65535 || W > 65535) return HV_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < hv_rhlv_maps_workspace_bytes(W, Z, views, 1) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
+    const RhlvMapOuts O = rhlv_map_outs(views, h_sagittal_out, h_coronal_out);
+    return rhlv_run(fake, label, nullptr, nullptr, 1, dtype, stride_h, stride_w, stride_z, H, label_index,
+                    rhlv_plan(W, Z, views, h_sagittal, h_coronal, true), out, 16, workspace, (hipStream_t)stream, &O);
+}
+
+extern "C" int hv_rhlv_maps_batch(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                                  long long stride_z, int H, int W, int Z, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
+                                  const hv_rhlv_map_out* h_sagittal_out, const hv_rhlv_map_out* h_coronal_out, double* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (!pairs || !label_indices || !out || n_pairs <= 0 || H <= 0 || W <= 0 || Z <= 0 || (dtype != 0 && dtype != 1) ||
+        !rhlv_views_ok(views, h_sagittal, h_coronal))
+        return HV_ERR_ARG;
+    if (Z > 65535 || W > 65535 || n_pairs > 65535) return HV_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < hv_rhlv_maps_workspace_bytes(W, Z, views, n_pairs) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
+    const RhlvMapOuts O = rhlv_map_outs(views, h_sagittal_out, h_coronal_out);
+    return rhlv_run(nullptr, nullptr, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, 0.f,
+                    rhlv_plan(W, Z, views, h_sagittal, h_coronal, true), out, 16, workspace, (hipStream_t)stream, &O);
 }

@@ -10,6 +10,10 @@ ratios without the sagittal script's + 1e-6, ValueError where it takes max() of 
   rhlv_volume_25d(vol_fake, vol_label, label_index, ...)   both views from one pass over the volumes, one readback
   rhlv_dataset(fakes, labels, label_indices, ...)          N pairs of equal shape: one launch sequence per chunk, one readback in all
   svm_features(records, file1='sagittal')                  the six feature columns in SVM_grading_2.5d.py's order
+and what the reference's README draws from those scripts' per-column heights (the distribution of height loss over the vertebra's
+cross-section and the curve of height loss along it), left on the device:
+  height_loss_map(vol_fake, vol_label, label_index, ...)       per view: loss / height maps [S, C], flags, column and slice profiles
+  height_loss_dataset(fakes, labels, label_indices, ...)       the same stacked over N pairs of equal shape
 Volumes are [H, W, Z] tensors (any strides; float32 or uint8) already resident in HBM, e.g. the label volume infer.process_volume
 just produced.  The file I/O / Excel part of the reference and the SVM stay on the host.
 """
@@ -164,3 +168,131 @@ def svm_features(records, file1='sagittal'):
     other view's (its `_2` columns)."""
     first = 0 if VIEWS[file1] == SAGITTAL else 1
     return np.concatenate([records[:, first, 1:4], records[:, 1 - first, 1:4]], axis=1)
+
+
+# ---------------------------------------------------------------- per-column height-loss maps and profiles (hv_rhlv_maps)
+FLAG_REGION, FLAG_SEL_FAKE, FLAG_SEL_LABEL, FLAG_VISITED = 3, 4, 8, 16      # bits of a `flags` element: region 0 pre / 1 mid / 2 post
+
+
+def _view_bits(views):
+    names = (views,) if isinstance(views, str) else tuple(views)
+    if not names or len(set(names)) != len(names) or any(v not in VIEWS for v in names):
+        raise ValueError("height_loss_map: views must name 'sagittal', 'coronal' or both")
+    return sum(VIEWS[v] for v in names)
+
+
+def _map_buffers(bits, n, W, Z, dev):
+    """Output buffers of hv_rhlv_maps(_batch) for n pairs -> ({view: dict of device tensors with a leading [n] axis}, ranges int32 [2, n, 2])."""
+    tensors = {}
+    ranges = torch.empty(2, n, 2, dtype=torch.int32, device=dev)          # a requested view's rows are always written
+    for j, name in enumerate(VIEWS):
+        if not bits & VIEWS[name]:
+            continue
+        S, C = (Z, W) if name == 'sagittal' else (W, Z)
+        t = {k: torch.empty(n, S, C, dtype=torch.float64, device=dev) for k in ('loss', 'height_fake', 'height_label')}
+        t['flags'] = torch.empty(n, S, C, dtype=torch.uint8, device=dev)
+        t['column_profile'] = torch.empty(n, 3, C, dtype=torch.float64, device=dev)
+        t['slice_profile'] = torch.empty(n, 3, S, dtype=torch.float64, device=dev)
+        t['range'] = ranges[j]
+        tensors[name] = t
+    return tensors, ranges
+
+
+def _map_args(L, tensors, i=0):
+    """-> the hv_rhlv_map_out of the sagittal and of the coronal view (None where not asked for), writing from pair i on."""
+    order = ('loss', 'height_fake', 'height_label', 'flags', 'column_profile', 'slice_profile', 'range')
+    return tuple(ctypes.byref(L.hv_rhlv_map_out(*(tensors[name][k][i:].data_ptr() for k in order))) if name in tensors else None
+                 for name in VIEWS)
+
+
+def _map_view(t, i=None):
+    """The raw buffers of one view -> the named tensors (pair i of a batch, or the whole [N, ...] stack)."""
+    pick = (lambda a: a) if i is None else (lambda a: a[i])
+    cp, sp = pick(t['column_profile']), pick(t['slice_profile'])
+    return {'loss': pick(t['loss']), 'height_fake': pick(t['height_fake']), 'height_label': pick(t['height_label']), 'flags': pick(t['flags']),
+            'profile_fake': cp[..., 0, :], 'profile_label': cp[..., 1, :], 'curve': cp[..., 2, :],
+            'slice_profile_fake': sp[..., 0, :], 'slice_profile_label': sp[..., 1, :], 'slice_curve': sp[..., 2, :]}
+
+
+def _run_maps(fake, label, label_index, views, length_divisor, lo, hi, height_threshold, buffers=None):
+    """hv_rhlv_maps -> ([views][16] float64 records, {view: raw output buffers}, ranges), all on the device, nothing read back.
+    buffers: (records, tensors, ranges) of an earlier call on the same shapes to write into instead of allocating (tools/bench_rhlv.py)."""
+    L = _lib.get()
+    f, l, dev = _pair(fake, label)
+    H, W, Z = f.shape
+    ws, _ = ops._ws(L.size('hv_rhlv_maps_workspace_bytes', W, Z, views, 1), dev, slot=3)
+    sag, cor = _view_args(L, views, length_divisor, lo, hi, height_threshold)
+    if buffers is None:
+        buffers = (torch.zeros(bin(views).count('1'), 16, dtype=torch.float64, device=dev),) + _map_buffers(views, 1, W, Z, dev)
+    out, tensors, ranges = buffers
+    so, co = _map_args(L, tensors)
+    L.call('hv_rhlv_maps', _lib.ptr(f), _lib.ptr(l), *_geometry(f), ctypes.c_float(label_index), views, sag, cor, so, co, _lib.ptr(out), _lib.ptr(ws),
+           ctypes.c_size_t(ws.numel()), _lib.stream())
+    return out, tensors, ranges
+
+
+def height_loss_map(vol_fake, vol_label, label_index, length_divisor=5, height_threshold=0.64, views=('sagittal', 'coronal')):
+    """The per-column heights behind rhlv_volume / rhlv_volume_25d, from the same single pass over the volumes (hv_rhlv_maps).
+    -> {view: {...}, 'records': float64 numpy [len(views), 16]}, or None if the original volume does not contain the vertebra.  Per view, with
+    S slices of C columns (sagittal: S = Z, C = W; coronal: S = W, C = Z), all DEVICE tensors -- only the records and the ranges are read back:
+      loss, height_fake, height_label   [S, C] float64: height_fake = column count * the slice's whole-slice rescale ratio, height_label = column
+                                        count, loss = (height_fake - height_label) / (height_fake + 1e-6) where the script selects the generated
+                                        column, NaN elsewhere; a slice the script does not visit is NaN / 0
+      flags                             [S, C] uint8: FLAG_REGION bits (0 pre, 1 mid, 2 post), FLAG_SEL_FAKE, FLAG_SEL_LABEL, FLAG_VISITED
+      profile_fake, profile_label, curve                           [C]: mean selected height per column over the slices, and its relative loss
+      slice_profile_fake, slice_profile_label, slice_curve         [S]: the same per slice over its columns
+      range                             (lo, hi): the slices the script walks
+    The selected height_fake (height_label) of a whole map average to the view's record [5] ([6]), the means rhlv_volume reports.
+    height_threshold: one value or a (sagittal, coronal) pair.  ValueError where the coronal script would have raised."""
+    out, tensors, ranges = _run_maps(vol_fake, vol_label, float(label_index), _view_bits(views), length_divisor, INT_MIN, 0, height_threshold)
+    rec = out.cpu().numpy()
+    if rec[0, 13] == 0:
+        return None
+    if np.any(rec[:, 14] != 0):
+        raise ValueError(EMPTY_THIRD)
+    ranges = ranges.cpu()
+    res = {'records': rec}
+    for j, name in enumerate(VIEWS):
+        if name in tensors:
+            res[name] = _map_view(tensors[name], 0)
+            res[name]['range'] = (int(ranges[j, 0, 0]), int(ranges[j, 0, 1]))
+    return res
+
+
+def height_loss_dataset(fakes, labels, label_indices, length_divisor=5, height_threshold=0.64, views=('sagittal', 'coronal'), chunk=256):
+    """height_loss_map over N resident volume pairs of equal shape, dtype and strides (the batched form beside rhlv_dataset): one launch sequence
+    per `chunk` pairs (hv_rhlv_maps_batch).  -> {view: height_loss_map's tensors stacked to [N, ...] on the device ('range': int32 [N, 2]),
+    'records': float64 numpy [N, len(views), 16], 'present': bool numpy [N]}.  present is False where the original lacks the vertebra (that
+    pair's rows are NaN / 0); nothing raises per vertebra: check records[:, -1, 14] for the coronal view.  The maps take 25 bytes per column
+    of every slice, view and pair."""
+    L = _lib.get()
+    bits = _view_bits(views)
+    n = len(fakes)
+    if n == 0 or len(labels) != n or len(label_indices) != n:
+        raise ValueError('height_loss_dataset: equally many (at least one) generated volumes, original volumes and label indices expected')
+    dev = fakes[0].device
+    geo = (fakes[0].shape, fakes[0].stride(), fakes[0].dtype)
+    for t in list(fakes) + list(labels):
+        _lib.require_gpu(t)
+        if t.dim() != 3 or (t.shape, t.stride(), t.dtype) != geo or t.dtype not in (torch.float32, torch.uint8) or t.device != dev:
+            raise ValueError('height_loss_dataset: [H, W, Z] float32 or uint8 device volumes of one shape, dtype and stride pattern expected')
+    H, W, Z = geo[0]
+    nv = bin(bits).count('1')
+    table = torch.tensor([p for f, l in zip(fakes, labels) for p in (f.data_ptr(), l.data_ptr())], dtype=torch.int64).to(dev)
+    ids = torch.tensor([float(i) for i in label_indices], dtype=torch.float32).to(dev)
+    out = torch.zeros(n, nv, 16, dtype=torch.float64, device=dev)
+    chunk = max(1, min(int(chunk), n))
+    ws, _ = ops._ws(L.size('hv_rhlv_maps_workspace_bytes', W, Z, bits, chunk), dev, slot=3)
+    sag, cor = _view_args(L, bits, length_divisor, INT_MIN, 0, height_threshold)
+    tensors, _ = _map_buffers(bits, n, W, Z, dev)
+    for i in range(0, n, chunk):
+        m = min(chunk, n - i)
+        so, co = _map_args(L, tensors, i)
+        L.call('hv_rhlv_maps_batch', _lib.ptr(table[2 * i:]), _lib.ptr(ids[i:]), m, *_geometry(fakes[0]), bits, sag, cor, so, co,
+               _lib.ptr(out[i:]), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream())
+    rec = out.cpu().numpy()
+    res = {'records': rec, 'present': rec[:, 0, 13] != 0}
+    for name in tensors:
+        res[name] = _map_view(tensors[name])
+        res[name]['range'] = tensors[name]['range']
+    return res

@@ -537,6 +537,43 @@ int hv_rhlv_views_batch(const void* pairs, const float* label_indices, int n_pai
                         long long stride_z, int H, int W, int Z, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
                         double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-column height-loss maps and profiles of RHLV (the distribution of height loss over the vertebra's cross-section and the curve of
+ * height loss along it, reference README "Clinical value"; the same lines of the two scripts as hv_rhlv_views) ----
+ * Arguments, records (`out`, [n_pairs][views][16], bit for bit hv_rhlv_views' / hv_rhlv_views_batch's) and the pass over the volumes as for
+ * hv_rhlv_views / hv_rhlv_views_batch; in addition, per requested view (S slices of C columns: sagittal S = Z, C = W; coronal S = W, C = Z), what the
+ * script computes per column of a slice before it folds it into means.  For a slice s the script visits (inside [lo, hi) after numpy slice
+ * normalisation, both volumes non-empty there) and a column c:
+ *   height_fake[s][c]  = cnt_fake[s][c] * all_scale_ratio[s]  (all_height_fake * all_scale_ratio, :93; the view's own ratio arithmetic)
+ *   height_label[s][c] = cnt_label[s][c]                      (:70)
+ *   flags[s][c]: bits 0-1 = 0 pre (c < one_third_y), 1 mid (c < two_third_y), 2 post (:60-61); bit 2 = height_fake > center_height_fake *
+ *                all_scale_ratio * height_threshold (:99); bit 3 = height_label > center_height_label * height_threshold (:100); bit 4 = visited
+ *   loss[s][c]         = (height_fake - height_label) / (height_fake + 1e-6) where bit 2 is set, NaN elsewhere (the formula of :139 per column)
+ * and a slice that is not visited is a row of NaN losses, zero heights and zero flags.
+ *   column_profile [3][C]: profile_fake[c] = sum over s of the bit-2 height_fake / their number, profile_label[c] the same of the bit-3 height_label,
+ *                  curve[c] = (profile_fake - profile_label) / (profile_fake + 1e-6); NaN where no slice selects the column
+ *   slice_profile [3][S]: the same three per slice s over its columns
+ *   range [2]: lo, hi after normalisation (0, 0 where the original lacks the vertebra)
+ * Sums run in ascending index order, one lane each: the results do not change from run to run or between the single and the batched entry.
+ * Every hv_rhlv_map_out pointer is a DEVICE pointer or NULL = not wanted; the structs themselves (h_*) are host memory, NULL = nothing wanted of
+ * that view.  hv_rhlv_maps_batch: every array gains a leading [n_pairs] axis.  workspace: hv_rhlv_maps_workspace_bytes bytes, 8-byte aligned. */
+typedef struct {
+    double* loss;           /* [S][C] */
+    double* height_fake;    /* [S][C] */
+    double* height_label;   /* [S][C] */
+    uint8_t* flags;         /* [S][C] */
+    double* column_profile; /* [3][C] */
+    double* slice_profile;  /* [3][S] */
+    int* range;             /* [2] */
+} hv_rhlv_map_out;
+size_t hv_rhlv_maps_workspace_bytes(int W, int Z, int views, int n_pairs);
+int hv_rhlv_maps(const void* fake, const void* label, int dtype, long long stride_h, long long stride_w, long long stride_z, int H, int W, int Z,
+                 float label_index, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal, const hv_rhlv_map_out* h_sagittal_out,
+                 const hv_rhlv_map_out* h_coronal_out, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int hv_rhlv_maps_batch(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                       long long stride_z, int H, int W, int Z, int views, const hv_rhlv_view* h_sagittal, const hv_rhlv_view* h_coronal,
+                       const hv_rhlv_map_out* h_sagittal_out, const hv_rhlv_map_out* h_coronal_out, double* out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- batch assembly on the device (reference data/aligned_dataset.py:204-280, AlignedDataset.__getitem__) ----
  * One item = one sagittal slice of a vertebra volume whose four uint8 planes [H][W] are resident on the device: ct = ct_data.astype(uint8)
  * (:245), vert = component-filtered vertebra mask * 255 (:247-248), normal = the patient's normal vertebrae as 0/255 (:190-196), cam =

@@ -3,6 +3,8 @@
   * one pair, both views (the 2.5D grade's six features): rhlv_volume_25d (one pass over the volumes, one readback) vs two rhlv_volume
     calls, the second on the permuted view -- the only way to both views before hv_rhlv_views (its coronal numbers follow the sagittal
     script's arithmetic, so it is a timing yardstick only);
+  * one pair, both views, the per-column height-loss maps and profiles: height_loss_map (rhlv_volume_25d's launches plus two, the maps left in
+    HBM) vs the host alternative -- download both volumes and run the numpy restatement (tests/height_map_ref.py) on them;
   * a dataset of 64 pairs: rhlv_dataset (one launch sequence, one readback) vs 64 rhlv_volume_25d calls.
 Device-only times are hipEvent brackets around back-to-back launches; the end-to-end times (`wall`) include the readbacks and are
 medians of repeated wall-clock measurements."""
@@ -72,6 +74,25 @@ one_wall = wall_us(lambda: evaluation.rhlv_volume_25d(f, l, 20))
 two_wall = wall_us(two_calls)
 print('2.5D, one 256x256x64 pair: rhlv_volume_25d %.1f us device / %.1f us wall; two rhlv_volume calls (second on the permuted view) '
       '%.1f us device / %.1f us wall' % (one_dev, one_wall, two_dev, two_wall))
+
+# (a') the per-column maps and profiles of the same pair
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+import height_map_ref
+
+
+def host_maps():
+    hf, hl = f.cpu().numpy(), l.cpu().numpy()
+    return [height_map_ref.view_maps(hf, hl, 20, 5, 0.64, view) for view in ('sagittal', 'coronal')]
+
+
+bufs = evaluation._run_maps(f, l, 20.0, both, 5, evaluation.INT_MIN, 0, 0.64)      # allocated once: the bracket holds launches only
+map_dev = device_us(lambda: evaluation._run_maps(f, l, 20.0, both, 5, evaluation.INT_MIN, 0, 0.64, buffers=bufs))
+map_wall = wall_us(lambda: evaluation.height_loss_map(f, l, 20))
+host_wall = wall_us(host_maps, n=5, warm=1)
+maps, ref = evaluation.height_loss_map(f, l, 20), host_maps()
+worst = max(float(np.nanmax(np.abs(maps[view]['loss'].cpu().numpy() - r['loss']))) for view, r in zip(('sagittal', 'coronal'), ref))
+print('height-loss maps, one 256x256x64 pair, both views: height_loss_map %.1f us device / %.1f us wall (rhlv_volume_25d: %.1f / %.1f); '
+      'download + numpy restatement %.1f ms wall; max |d loss| %.2e' % (map_dev, map_wall, one_dev, one_wall, host_wall / 1e3, worst))
 
 # (b) a dataset of 64 resident pairs
 N = 64
