@@ -68,7 +68,7 @@ def flow_to_image(flow):
         f = fk - k0
         img = np.zeros(u.shape + (3,))
         for c in range(3):
-            col = (1 - f) * wheel[k0 - 1, c] / 255 + f * wheel[k1 - 1, c] / 255
+            col = (1 - f) * (wheel[k0 - 1, c] / 255) + f * (wheel[k1 - 1, c] / 255)      # each entry / 255 first, as the reference and hv_ca_flow do
             inside = rad <= 1
             col = np.where(inside, 1 - rad * (1 - col), col * 0.75)
             img[:, :, c] = np.uint8(np.floor(255 * col))

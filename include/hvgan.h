@@ -320,7 +320,7 @@ int hv_ca_mask(const float* mask, int Himg, int Wimg, int h, int w, float* mm, v
  * loop runs the generator at batch 1, eval_3d_sagittal_twostage.py:101), not for one training batch (which shares sample 0's mask) */
 int hv_ca_mask_batched(const float* mask, int B, long long mask_bstride, int Himg, int Wimg, int h, int w, float* mm, void* stream);
 /* score fusion (two diagonal 3-tap sums with the (h,w)<->(w,h) transposes, :352-361); adjoint=1 applies the
- * transposed operator (backward).  h == w required. */
+ * transposed operator (backward).  h and w need not be equal. */
 int hv_ca_fuse(const float* S, float* out, int B, int h, int w, int adjoint, void* stream);
 /* A[b][p][l] = softmax_l(S*mm*scale)*mm (:364-366); optional argmax over l -> argmax[b*L+p] (:368). */
 int hv_ca_softmax(const float* S, const float* mm, float* A, int B, int L, float scale, int* argmax, void* stream);
@@ -330,6 +330,9 @@ int hv_ca_softmax_batched(const float* S, const float* mm, long long mm_bstride,
  * coloured with the Middlebury wheel (double precision, running maximum radius over samples 0..b like the reference's batch loop), as
  * uint8/255 and nearest-upsampled x`up` (rate*4): flow[B][3][h*up][w*up] (NCHW like the reference's tensor). */
 int hv_ca_flow(const int* argmax, int B, int h, int w, int up, float* flow, void* stream);
+/* dS[b][p][l] = scale*mm[l]*A[b][p][l]*(dA[b][p][l] - sum_l' dA[b][p][l']*A[b][p][l']).  hv_ca_softmax_backward(_f16) take ONE mask mm[L] and apply it
+ * to every sample: they are valid only after a shared-mask forward (hv_ca_softmax, or mm_bstride = 0); after a per-sample-mask forward they would read
+ * sample 0's mask for all samples (the engine refuses that backward). */
 int hv_ca_softmax_backward(const float* dA, const float* A, const float* mm, float* dS, int B, int L, float scale, void* stream);
 int hv_transpose_batched(const float* src, float* dst, int B, int R, int C, void* stream); /* dst[b][c][r] = src[b][r][c] */
 /* Batched "NT" matrix product on fp16 MFMA (fp32 accumulation and result; A / B are fp32 -- converted when staged -- or, with a_f16 / b_f16, fp16

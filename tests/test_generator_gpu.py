@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from hvtest import _flow_close
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -13,16 +14,6 @@ TOL = 1e-3
 
 def _err(a, b):
     return (a.detach().cpu().double() - b.double()).abs().max().item()
-
-
-def _flow_close(got, ref, name):
-    """offset_flow: uint8 colour codes / 255.  The arg-max of near-tied scores may pick a different patch on the device than the CPU
-    reference did (a different colour for that pixel's 8x8 block), and floor(255*col) can fall either side of an integer: allow a
-    handful of pixels; everything else must agree to half a colour step."""
-    d = (got.detach().cpu() - ref).abs()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    frac = (d > 0.5 / 255).float().mean().item()
-    assert frac <= 5e-3, (name, frac, d.max().item())
 
 
 def _gen(g, ngf=4):
