@@ -281,7 +281,9 @@ int hv_nchw_to_nhwc(const float* src, void* dst, int dst_f16, int B, int C, int 
 int hv_nhwc_to_nchw(const void* src, int src_f16, float* dst, int B, int C, int H, int W, int src_ld, int src_coff, int accumulate, void* stream);
 /* Copies C channels into a channel slice of dst; H,W are the dst size.  mode 0: same size; 1: src is half size
  * (nearest x2 upsample); 2: src is double size (nearest x1/2 downsample, even indices); 3: dst(half) (+)= sum of the
- * 2x2 block of src(full) [adjoint of 1]; 4: dst(full) (+)= src(half) at even indices, 0 elsewhere [adjoint of 2]. */
+ * 2x2 block of src(full) [adjoint of 1]; 4: dst(full) (+)= src(half) at even indices, 0 elsewhere [adjoint of 2].
+ * Modes 1 and 4 need even H and W (HV_ERR_UNSUPPORTED otherwise); modes 0, 2, 3 take any size.  16 B per lane when C, both strides and both offsets
+ * are multiples of 4 and both base pointers 16-byte aligned, element by element otherwise: same result. */
 int hv_copy_channels(const void* src, int src_f16, void* dst, int dst_f16, int B, int H, int W, int C, int src_ld, int src_coff, int dst_ld,
                      int dst_coff, int mode, int accumulate, void* stream);   /* *_f16: storage of src / dst (may differ: the copy converts) */
 /* dst = a + b over C channels of same-size [npix] tensors, each with its own storage / channel stride / offset: a gradient with two contributions
@@ -291,15 +293,18 @@ int hv_add_channels(const void* a, int a_f16, int a_ld, int a_coff, const void* 
 
 /* ---------------------------------------------------------------- generator heads and inputs
  * cat[x, ratio-plane, mask] / cat[x, coarse_seg, mask, ratio-plane] (models/inpaint_networks.py:71-77,173-179)
- * written as a CP-channel NHWC buffer (pad channels zero).  order: 0 = coarse, 1 = fine. */
+ * written as a CP-channel NHWC buffer (pad channels zero).  order: 0 = coarse, 1 = fine.  CP a multiple of 4, >= 4; seg may be NULL for order 0
+ * only; the ratio plane is slice_ratio rounded to fp32. */
 int hv_gen_input(const float* x, const float* seg, const float* mask, const double* slice_ratio, void* dst, int dst_f16,
                  int B, int H, int W, int CP, int order, void* stream);
-/* AdaptiveAvgPool2d(1) -> Linear(C,1) -> sigmoid (models/inpaint_networks.py:90-93,211-214). */
+/* AdaptiveAvgPool2d(1) -> Linear(C,1) -> sigmoid (models/inpaint_networks.py:90-93,211-214).  C a power of two <= 256 (HV_ERR_UNSUPPORTED otherwise),
+ * x_ld >= C; workspace: hv_gap_fc_workspace_bytes(B, C) bytes (HV_ERR_WORKSPACE when shorter). */
 size_t hv_gap_fc_workspace_bytes(int B, int C);
 int hv_gap_fc_sigmoid(const void* x, int x_f16, int B, int HW, int C, int x_ld, const float* fc_w, const float* fc_b,
                       float* pooled /*[B][C]*/, float* pred /*[B]*/, float* workspace, size_t workspace_bytes, void* stream);
 /* backward: dx[n,p,c] += dpred[n]*pred(1-pred)*w[c]/HW [* act'(mul_src[n,p,c]) when mul_src: dx then holds the gradient wrt the PRE-activation of the
- * pooled tensor, like hv_conv_desc.mul_src]; dw[c] (+)= sum_n dl_n*pooled[n,c]; db (+)= sum_n dl_n */
+ * pooled tensor, like hv_conv_desc.mul_src]; dw[c] (+)= sum_n dl_n*pooled[n,c]; db (+)= sum_n dl_n.  `accumulate` is about dw / db only: dx is
+ * always added to (in its storage type).  C <= 1024, mul_ld >= C. */
 int hv_gap_fc_sigmoid_backward(const float* dpred, const float* pred, const float* pooled, const float* fc_w,
                                void* dx, int dx_f16, int B, int HW, int C, int dx_ld, float* dw, float* db, int accumulate,
                                const void* mul_src, int mul_f16, int mul_ld, int mul_act, void* stream);
@@ -440,7 +445,10 @@ int hv_gan_loss_head_pair(const float* z0, long long n0, int real0, float* loss0
 
 /* Generator losses and their gradient seeds (models/pix2pix_model.py:331-353): writes
  * losses[0..5] = {G_maskL1, G_Dice, coarse_Dice, edge, h, sum of those five} and the seeds
- * d_fake_B (L1 part), d_fake_B_coarse, d_fine_seg, d_coarse_seg, d_pred1 (raw sigmoid output), d_pred2. */
+ * d_fake_B (L1 part), d_fake_B_coarse, d_fine_seg, d_coarse_seg, d_pred1 (raw sigmoid output), d_pred2.
+ * The four image seeds are written when all four pointers are given and none of them otherwise (losses only); d_pred1 / d_pred2 are optional one by
+ * one.  Any B: up to 64 samples are finalized in one pass, more through a spill into the workspace (same results).  The mask must have a non-zero
+ * element.  workspace: hv_generator_losses_workspace_bytes(B) bytes, 8-byte aligned. */
 typedef struct {
     const float* fake_B; const float* fake_B_coarse; const float* real_B; const float* mask;
     const float* fine_seg; const float* coarse_seg; const float* real_B_mask; const float* normal_vert;
@@ -462,7 +470,8 @@ typedef struct {
 size_t hv_generator_losses_workspace_bytes(int B);
 int hv_generator_losses(const hv_gloss_desc* d, void* stream);
 /* Gradient of the compositing + local crop: d_gen[row] = (d_fake[row] + d_local[row]*mask*band) for xu<=row<xb else 0.
- * which: 0 -> rows[b][0..1] (stage 2), 1 -> rows[b][2..3] (stage 1). */
+ * which: 0 -> rows[b][0..1] (stage 2), 1 -> rows[b][2..3] (stage 1).  band: columns W/2 - half_band <= col < W/2 + half_band.  d_fake and d_local may
+ * each be NULL (that term is absent; mask is read only with d_local); accumulate: d_gen += instead of =. */
 int hv_shrm_backward(const float* d_fake, const float* d_local, const float* mask, const int* rows, int which,
                      float* d_gen, int B, int H, int W, int half_band, int accumulate, void* stream);
 

@@ -38,9 +38,14 @@ def _env():
     import hvtest as _T
     ops, T, lib = _ops, _T, _lib
     yield
+    print_ratios()
+
+
+def print_ratios(prefix=''):
     print('\nworst error / bound per family')
     for k in sorted(RATIOS):
-        print('  %-22s %.3e' % (k, RATIOS[k]))
+        if k.startswith(prefix):
+            print('  %-22s %.3e' % (k, RATIOS[k]))
 
 
 class Check:
