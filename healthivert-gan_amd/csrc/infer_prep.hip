@@ -223,21 +223,29 @@ extern "C" int hv_select_slices(const int* flag, const float* src, float* dst, i
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------
-// Volume intake / output of the inference driver on the device (reference eval_3d_sagittal_twostage.py:186-197,:208,:217,:236-239): the float64
-// [H][W][Z] volumes (z fastest) are uploaded as they lie -- ONE pinned copy per volume on the host, no scan and no float32 conversion there --
-//   volume_scan_kernel     counts[j][z] = number of voxels of slice z equal to ids[j] (the vertebra's z-extent and the two neighbours' > 200-pixel
+// Volume intake / output of the inference driver on the device (reference eval_3d_sagittal_twostage.py:186-197,:208,:217,:236-239 and the `[:, z, :]`
+// slicing of evaluation/RHLV_quantification_coronal.py:51-54): the [A0][A1][A2] volumes (A2 fastest; float64 as nibabel hands them over, or the
+// float32 / uint8 volumes a resident producer leaves) are read as they lie -- no scan and no float32 conversion on the host.
+// Slice axis 2 (sagittal, planes [A0][A1], p = a0 * A1 + a1): neighbouring voxels belong to different slices
+//   volume_scan_kernel     counts[j][z] = number of voxels of slice z equal to ids[j] (the vertebra's extent and the two neighbours' > 200-pixel
 //                          gates in one pass over the label volume; integer sums: exact in any order)
-//   volume_slices_kernel   out[s][p] = (float)vol[p][z0 + s]: cut the z-range, convert (C cast, numpy's astype) and transpose to slices
-//   volume_merge_kernel    out[p][z] = (z in range and flag[z - z0]) ? (double)src[z - z0][p] : 0: the output volume as the reference builds it
-//                          (np.zeros + per-slice assignment), z fastest, float64
-__global__ __launch_bounds__(256) void volume_scan_kernel(const double* __restrict__ label, long long n, int Z, double id0, double id1, double id2,
+//   volume_slices_kernel   out[s][p] = (float)vol[p][z0 + s]: cut the range, convert (C cast, numpy's astype) and transpose to slices
+//   volume_merge_kernel    out[p][z] = (z in range and flag[z - z0]) ? src[z - z0][p] : 0: the output volume as the reference builds it
+//                          (np.zeros + per-slice assignment), z fastest
+// Slice axis 1 (coronal, planes [A0][A2]): a plane row is A2 contiguous elements in the volume and in the slice alike, so nothing is transposed
+//   rows_scan_kernel       one wave per row (a0, a1): it counts its matches and adds once per row and id
+//   rows_slices_kernel     out[s][a0][:] = (float)vol[a0][k0 + s][:]
+//   rows_merge_kernel      out[a0][k][:] = (k in range and flag[k - k0]) ? src[k - k0][a0][:] : 0
+//   each with a 4-elements-per-lane form (WIDE: A2 % 4 == 0 and row starts aligned to the vector) and a scalar form for odd A2 / unaligned rows
+template <typename T>
+__global__ __launch_bounds__(256) void volume_scan_kernel(const T* __restrict__ label, long long n, int Z, double id0, double id1, double id2,
                                                           int* __restrict__ counts) {
     extern __shared__ int hist[];      // [3][Z]
     for (int i = threadIdx.x; i < 3 * Z; i += 256) hist[i] = 0;
     __syncthreads();
     const long long stride = (long long)gridDim.x * 256;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const double v = label[i];
+        const double v = (double)label[i];
         if (v == 0.0) continue;          // background: no id is 0 (checked on the host side)
         const int z = (int)(i % Z);
         if (v == id0) atomicAdd(hist + z, 1);
@@ -248,20 +256,10 @@ __global__ __launch_bounds__(256) void volume_scan_kernel(const double* __restri
     for (int i = threadIdx.x; i < 3 * Z; i += 256)
         if (hist[i]) atomicAdd(counts + i, hist[i]);
 }
-extern "C" int hv_volume_scan(const double* label, long long HW, int Z, double id0, double id1, double id2, int* counts, void* stream) {
-    if (!label || !counts || HW <= 0 || Z <= 0 || Z > 2048) return HV_ERR_ARG;
-    if (id0 == 0.0 || id1 == 0.0 || id2 == 0.0) return HV_ERR_ARG;      // unused ids are passed as a negative number
-    hipError_t e = hipMemsetAsync(counts, 0, (size_t)3 * Z * sizeof(int), (hipStream_t)stream);
-    if (e != hipSuccess) return -1000 - (int)e;
-    const long long n = HW * Z;
-    const int grid = (int)(n / (256 * 16) < 1 ? 1 : (n / (256 * 16) > 2048 ? 2048 : n / (256 * 16)));
-    hipLaunchKernelGGL(volume_scan_kernel, dim3(grid), dim3(256), (size_t)3 * Z * sizeof(int), (hipStream_t)stream, label, n, Z, id0, id1, id2, counts);
-    HV_LAUNCH_CHECK();
-    return HV_OK;
-}
 
 // 64 pixels x 32 slices per workgroup through LDS: 256-byte runs of doubles in, 256-byte runs of floats out
-__global__ __launch_bounds__(256) void volume_slices_kernel(const double* __restrict__ vol, long long HW, int Z, int z0, int S, float* __restrict__ out) {
+template <typename T>
+__global__ __launch_bounds__(256) void volume_slices_kernel(const T* __restrict__ vol, long long HW, int Z, int z0, int S, float* __restrict__ out) {
     __shared__ float t[64][33];
     const long long p0 = (long long)blockIdx.x * 64;
     const int s0 = blockIdx.y * 32, zz = threadIdx.x & 31, pr = threadIdx.x >> 5;
@@ -278,15 +276,10 @@ __global__ __launch_bounds__(256) void volume_slices_kernel(const double* __rest
         if (s < S && p0 + pl < HW) out[(long long)s * HW + p0 + pl] = t[pl][sr + 4 * k];
     }
 }
-extern "C" int hv_volume_slices(const double* vol, long long HW, int Z, int z0, int S, float* out, void* stream) {
-    if (!vol || !out || HW <= 0 || Z <= 0 || z0 < 0 || S <= 0 || z0 + S > Z || HW > (1ll << 31) || S > 32 * 65535) return HV_ERR_ARG;
-    hipLaunchKernelGGL(volume_slices_kernel, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(S, 32)), dim3(256), 0, (hipStream_t)stream, vol, HW, Z, z0, S, out);
-    HV_LAUNCH_CHECK();
-    return HV_OK;
-}
 
+template <typename TO>
 __global__ __launch_bounds__(256) void volume_merge_kernel(const float* __restrict__ src, const int* __restrict__ flag, long long HW, int Z, int z0, int S,
-                                                           double* __restrict__ out) {
+                                                           TO* __restrict__ out) {
     __shared__ float t[64][33];
     const long long p0 = (long long)blockIdx.x * 64;
     const int zb = blockIdx.y * 32;                 // 32 output slices zb .. zb + 31 of the FULL z range
@@ -302,12 +295,205 @@ __global__ __launch_bounds__(256) void volume_merge_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const long long p = p0 + pr + 8 * k;
-        if (p < HW && zb + zz < Z) out[p * Z + zb + zz] = (double)t[pr + 8 * k][zz];
+        if (p < HW && zb + zz < Z) out[p * Z + zb + zz] = (TO)t[pr + 8 * k][zz];
     }
+}
+
+template <typename T> using vec4_t = T __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void rows_count_add(int* dst, int c, int lane) {
+    if (__ballot(c != 0) == 0) return;      // the same in every lane: all 64 lanes reach the shuffles
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) atomicAdd(dst, c);
+}
+
+// one wave per row of A2 contiguous voxels (all of one slice a1): per-lane match counts, one shuffle sum and one atomic per row and id that occurs
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(256) void rows_scan_kernel(const T* __restrict__ label, long long rows, int A1, int A2, double id0, double id1, double id2,
+                                                        int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const long long nw = (long long)gridDim.x * 4;
+    for (long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += nw) {
+        const T* row = label + r * A2;
+        int c0 = 0, c1 = 0, c2 = 0;
+        if (WIDE) {
+            for (int c = lane * 4; c < A2; c += 256) {
+                const vec4_t<T> q = *reinterpret_cast<const vec4_t<T>*>(row + c);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double v = (double)q[j];
+                    c0 += v == id0; c1 += v == id1; c2 += v == id2;
+                }
+            }
+        } else {
+            for (int c = lane; c < A2; c += 64) {
+                const double v = (double)row[c];
+                c0 += v == id0; c1 += v == id1; c2 += v == id2;
+            }
+        }
+        const int k = (int)(r % A1);
+        rows_count_add(counts + k, c0, lane);
+        rows_count_add(counts + A1 + k, c1, lane);
+        rows_count_add(counts + 2 * A1 + k, c2, lane);
+    }
+}
+
+// grid (items of one slice / 256, S): item = 4 elements (WIDE) or 1 of row a0; rows are contiguous on both sides
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(256) void rows_slices_kernel(const T* __restrict__ vol, int A0, int A1, int A2, int k0, float* __restrict__ out) {
+    const unsigned per = WIDE ? (unsigned)A2 >> 2 : (unsigned)A2;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)A0 * per) return;
+    const unsigned a0 = i / per, c = (i - a0 * per) * (WIDE ? 4u : 1u);
+    const int s = blockIdx.y;
+    const T* src = vol + ((long long)a0 * A1 + k0 + s) * A2 + c;
+    float* dst = out + ((long long)s * A0 + a0) * A2 + c;
+    if (WIDE) {
+        const vec4_t<T> q = *reinterpret_cast<const vec4_t<T>*>(src);
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (float)q[j];
+        *reinterpret_cast<f32x4*>(dst) = o;
+    } else {
+        *dst = (float)*src;
+    }
+}
+
+// grid (items of one slice / 256, A1): every element of out is written; the flag test is the same for the whole workgroup
+template <typename TO, bool WIDE>
+__global__ __launch_bounds__(256) void rows_merge_kernel(const float* __restrict__ src, const int* __restrict__ flag, int A0, int A1, int A2, int k0, int S,
+                                                         TO* __restrict__ out) {
+    const unsigned per = WIDE ? (unsigned)A2 >> 2 : (unsigned)A2;
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)A0 * per) return;
+    const unsigned a0 = i / per, c = (i - a0 * per) * (WIDE ? 4u : 1u);
+    const int k = blockIdx.y, s = k - k0;
+    const bool in = s >= 0 && s < S && flag[s] != 0;
+    TO* dst = out + ((long long)a0 * A1 + k) * A2 + c;
+    const float* from = src + ((long long)(in ? s : 0) * A0 + a0) * A2 + c;
+    if (WIDE) {
+        f32x4 q = {0.f, 0.f, 0.f, 0.f};
+        if (in) q = *reinterpret_cast<const f32x4*>(from);
+        vec4_t<TO> o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (TO)q[j];
+        *reinterpret_cast<vec4_t<TO>*>(dst) = o;
+    } else {
+        *dst = in ? (TO)*from : (TO)0;
+    }
+}
+
+static int scan_grid(long long n) { return (int)(n / (256 * 16) < 1 ? 1 : (n / (256 * 16) > 2048 ? 2048 : n / (256 * 16))); }
+static size_t dt_bytes(int dtype) { return dtype == HV_DT_F64 ? 8 : dtype == HV_DT_F32 ? 4 : dtype == HV_DT_U8 ? 1 : 0; }
+static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// shared argument rules of the three view entries: HV_OK, or the status to return before any launch
+static int view_args(const void* a, const void* b, int A0, int A1, int A2, int axis) {
+    if (!a || !b || A0 <= 0 || A1 <= 0 || A2 <= 0 || (axis != 1 && axis != 2)) return HV_ERR_ARG;
+    // 32-bit item indices inside a plane (axis 1) / the p index of the tiles (axis 2)
+    if ((long long)A0 * A1 > (1ll << 31) || (long long)A0 * A2 > (1ll << 31)) return HV_ERR_UNSUPPORTED;
+    return HV_OK;
+}
+
+template <typename T>
+static void scan_launch(const void* label, int A0, int A1, int A2, int axis, double id0, double id1, double id2, int* counts, hipStream_t s) {
+    const T* lab = (const T*)label;
+    if (axis == 2) {
+        const long long n = (long long)A0 * A1 * A2;
+        hipLaunchKernelGGL(volume_scan_kernel<T>, dim3(scan_grid(n)), dim3(256), (size_t)3 * A2 * sizeof(int), s, lab, n, A2, id0, id1, id2, counts);
+        return;
+    }
+    const long long rows = (long long)A0 * A1;
+    const int grid = (int)(rows / 4 < 1 ? 1 : (rows / 4 > 2048 ? 2048 : rows / 4));
+    if (A2 % 4 == 0 && aligned_to(label, 4 * sizeof(T)))
+        hipLaunchKernelGGL((rows_scan_kernel<T, true>), dim3(grid), dim3(256), 0, s, lab, rows, A1, A2, id0, id1, id2, counts);
+    else
+        hipLaunchKernelGGL((rows_scan_kernel<T, false>), dim3(grid), dim3(256), 0, s, lab, rows, A1, A2, id0, id1, id2, counts);
+}
+extern "C" int hv_volume_scan_view(const void* label, int dtype, int A0, int A1, int A2, int axis, double id0, double id1, double id2, int* counts,
+                                   void* stream) {
+    const int rc = view_args(label, counts, A0, A1, A2, axis);
+    if (rc != HV_OK) return rc;
+    if (!dt_bytes(dtype)) return HV_ERR_ARG;
+    if (id0 == 0.0 || id1 == 0.0 || id2 == 0.0) return HV_ERR_ARG;      // unused ids are passed as a negative number
+    if (axis == 2 && A2 > 2048) return HV_ERR_UNSUPPORTED;              // the per-workgroup histogram in LDS
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)3 * (axis == 2 ? A2 : A1) * sizeof(int), (hipStream_t)stream);
+    if (e != hipSuccess) return -1000 - (int)e;
+    if (dtype == HV_DT_F64) scan_launch<double>(label, A0, A1, A2, axis, id0, id1, id2, counts, (hipStream_t)stream);
+    else if (dtype == HV_DT_F32) scan_launch<float>(label, A0, A1, A2, axis, id0, id1, id2, counts, (hipStream_t)stream);
+    else scan_launch<unsigned char>(label, A0, A1, A2, axis, id0, id1, id2, counts, (hipStream_t)stream);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+extern "C" int hv_volume_scan(const double* label, long long HW, int Z, double id0, double id1, double id2, int* counts, void* stream) {
+    if (!label || !counts || HW <= 0 || Z <= 0 || Z > 2048) return HV_ERR_ARG;
+    if (id0 == 0.0 || id1 == 0.0 || id2 == 0.0) return HV_ERR_ARG;      // unused ids are passed as a negative number
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)3 * Z * sizeof(int), (hipStream_t)stream);
+    if (e != hipSuccess) return -1000 - (int)e;
+    const long long n = HW * Z;
+    hipLaunchKernelGGL(volume_scan_kernel<double>, dim3(scan_grid(n)), dim3(256), (size_t)3 * Z * sizeof(int), (hipStream_t)stream, label, n, Z, id0, id1, id2, counts);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+template <typename T>
+static void slices_launch(const void* vol, int A0, int A1, int A2, int axis, int k0, int S, float* out, hipStream_t s) {
+    const T* v = (const T*)vol;
+    if (axis == 2) {
+        const long long HW = (long long)A0 * A1;
+        hipLaunchKernelGGL(volume_slices_kernel<T>, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(S, 32)), dim3(256), 0, s, v, HW, A2, k0, S, out);
+        return;
+    }
+    if (A2 % 4 == 0 && aligned_to(vol, 4 * sizeof(T)) && aligned_to(out, 16))
+        hipLaunchKernelGGL((rows_slices_kernel<T, true>), dim3((unsigned)hv_cdiv((long long)A0 * (A2 / 4), 256), S), dim3(256), 0, s, v, A0, A1, A2, k0, out);
+    else
+        hipLaunchKernelGGL((rows_slices_kernel<T, false>), dim3((unsigned)hv_cdiv((long long)A0 * A2, 256), S), dim3(256), 0, s, v, A0, A1, A2, k0, out);
+}
+extern "C" int hv_volume_slices_view(const void* vol, int dtype, int A0, int A1, int A2, int axis, int k0, int S, float* out, void* stream) {
+    const int rc = view_args(vol, out, A0, A1, A2, axis);
+    if (rc != HV_OK) return rc;
+    if (!dt_bytes(dtype) || k0 < 0 || S <= 0 || (long long)k0 + S > (axis == 2 ? A2 : A1)) return HV_ERR_ARG;
+    if (S > (axis == 2 ? 32 * 65535 : 65535)) return HV_ERR_UNSUPPORTED;     // grid.y
+    if (dtype == HV_DT_F64) slices_launch<double>(vol, A0, A1, A2, axis, k0, S, out, (hipStream_t)stream);
+    else if (dtype == HV_DT_F32) slices_launch<float>(vol, A0, A1, A2, axis, k0, S, out, (hipStream_t)stream);
+    else slices_launch<unsigned char>(vol, A0, A1, A2, axis, k0, S, out, (hipStream_t)stream);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+extern "C" int hv_volume_slices(const double* vol, long long HW, int Z, int z0, int S, float* out, void* stream) {
+    if (!vol || !out || HW <= 0 || Z <= 0 || z0 < 0 || S <= 0 || z0 + S > Z || HW > (1ll << 31) || S > 32 * 65535) return HV_ERR_ARG;
+    hipLaunchKernelGGL(volume_slices_kernel<double>, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(S, 32)), dim3(256), 0, (hipStream_t)stream, vol, HW, Z, z0, S, out);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+template <typename TO>
+static void merge_launch(const float* src, const int* flag, int A0, int A1, int A2, int axis, int k0, int S, void* out, hipStream_t s) {
+    TO* o = (TO*)out;
+    if (axis == 2) {
+        const long long HW = (long long)A0 * A1;
+        hipLaunchKernelGGL(volume_merge_kernel<TO>, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(A2, 32)), dim3(256), 0, s, src, flag, HW, A2, k0, S, o);
+        return;
+    }
+    if (A2 % 4 == 0 && aligned_to(src, 16) && aligned_to(out, 4 * sizeof(TO)))
+        hipLaunchKernelGGL((rows_merge_kernel<TO, true>), dim3((unsigned)hv_cdiv((long long)A0 * (A2 / 4), 256), A1), dim3(256), 0, s, src, flag, A0, A1, A2, k0, S, o);
+    else
+        hipLaunchKernelGGL((rows_merge_kernel<TO, false>), dim3((unsigned)hv_cdiv((long long)A0 * A2, 256), A1), dim3(256), 0, s, src, flag, A0, A1, A2, k0, S, o);
+}
+extern "C" int hv_volume_merge_view(const float* src, const int* flag, int A0, int A1, int A2, int axis, int k0, int S, int out_dtype, void* out,
+                                    void* stream) {
+    const int rc = view_args(src, out, A0, A1, A2, axis);
+    if (rc != HV_OK) return rc;
+    if (!flag || (out_dtype != HV_DT_F64 && out_dtype != HV_DT_F32) || k0 < 0 || S <= 0 || (long long)k0 + S > (axis == 2 ? A2 : A1)) return HV_ERR_ARG;
+    if ((axis == 2 ? A2 : A1) > (axis == 2 ? 32 * 65535 : 65535)) return HV_ERR_UNSUPPORTED;     // grid.y
+    if (out_dtype == HV_DT_F64) merge_launch<double>(src, flag, A0, A1, A2, axis, k0, S, out, (hipStream_t)stream);
+    else merge_launch<float>(src, flag, A0, A1, A2, axis, k0, S, out, (hipStream_t)stream);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
 }
 extern "C" int hv_volume_merge(const float* src, const int* flag, long long HW, int Z, int z0, int S, double* out, void* stream) {
     if (!src || !flag || !out || HW <= 0 || Z <= 0 || z0 < 0 || S <= 0 || z0 + S > Z || HW > (1ll << 31)) return HV_ERR_ARG;
-    hipLaunchKernelGGL(volume_merge_kernel, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(Z, 32)), dim3(256), 0, (hipStream_t)stream, src, flag, HW, Z, z0, S, out);
+    hipLaunchKernelGGL(volume_merge_kernel<double>, dim3((unsigned)hv_cdiv(HW, 64), hv_cdiv(Z, 32)), dim3(256), 0, (hipStream_t)stream, src, flag, HW, Z, z0, S, out);
     HV_LAUNCH_CHECK();
     return HV_OK;
 }

@@ -161,70 +161,142 @@ def _stage_device(model, st, vert_id, selected, maxheight):
     return valid
 
 
+VIEWS = {'sagittal': 2, 'coronal': 1}                                # view -> slice axis of a C-contiguous [A0][A1][A2] volume
+_DT = {torch.uint8: 0, torch.float32: 4, torch.float64: 5}           # HV_DT_* of include/hvgan.h
+
+
+def view_geometry(shape, view):
+    """(slice axis, number of slices, plane shape) of a volume [A0, A1, A2] under a view: 'sagittal' slices `[:, :, k]` (planes [A0, A1], the reference's
+    eval_3d_sagittal_twostage.py), 'coronal' slices `[:, k, :]` (planes [A0, A2], evaluation/RHLV_quantification_coronal.py:51-54).  Pure host code.
+    ValueError for an unknown view, a shape that is not three positive sizes, or a coronal view of a volume with A0 != A2 (the generator takes
+    square planes only)."""
+    if view not in VIEWS:
+        raise ValueError("unknown view %r: expected 'sagittal' or 'coronal'" % (view,))
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) <= 0:
+        raise ValueError('a volume [A0, A1, A2] is expected, got shape %s' % (shape,))
+    axis = VIEWS[view]
+    if axis == 1 and shape[0] != shape[2]:
+        raise ValueError("view='coronal' slices %s along axis 1 into planes [%d, %d]: the generator takes square planes only (A0 == A2)"
+                         % (shape, shape[0], shape[2]))
+    return axis, shape[axis], (shape[0], shape[3 - axis])
+
+
+def check_volume_inputs(ct_data, label_data, cam_data, view, device):
+    """The argument rules of one volume of `VolumePipeline.run`, checked on the host before any GPU work: three arrays of one shape that `view_geometry`
+    accepts, each a numpy array or a contiguous float64 / float32 / uint8 tensor on `device`.  Returns view_geometry(label_data.shape, view)."""
+    geo = view_geometry(label_data.shape, view)
+    dev = torch.device(device)
+    for name, v in (('ct_data', ct_data), ('label_data', label_data), ('cam_data', cam_data)):
+        if tuple(v.shape) != tuple(label_data.shape):
+            raise ValueError('%s has shape %s, label_data %s' % (name, tuple(v.shape), tuple(label_data.shape)))
+        if not isinstance(v, torch.Tensor):
+            continue
+        if v.device.type != dev.type or (dev.index is not None and v.device.index is not None and v.device.index != dev.index):
+            raise ValueError('%s %s is a tensor on %s, the pipeline runs on %s (pass a numpy array or a tensor on that device)'
+                             % (name, tuple(v.shape), v.device, dev))
+        if not v.is_contiguous():
+            raise ValueError('%s %s with strides %s is not contiguous' % (name, tuple(v.shape), tuple(v.stride())))
+        if v.dtype not in _DT:
+            raise ValueError('%s %s has dtype %s: float64, float32 or uint8 expected' % (name, tuple(v.shape), v.dtype))
+    return geo
+
+
 class VolumePipeline:
-    """process_nii_files' per-volume loop (reference eval_3d_sagittal_twostage.py:186-241) for a STREAM of volumes.
+    """process_nii_files' per-volume loop (reference eval_3d_sagittal_twostage.py:186-241) for a STREAM of volumes, sliced along axis 2 (view='sagittal',
+    the reference's `[:, :, z]`) or along axis 1 (view='coronal', `[:, z, :]`: the volumes a coronal model synthesizes for RHLV_quantification_coronal.py).
 
-    Per volume the host does ONE thing with the data: it copies the three float64 [H, W, Z] arrays into a pinned buffer (three threads; numpy
-    releases the GIL).  Everything else runs on the device: the upload (copy stream), the z-extent scan and the neighbours' pixel counts
-    (hv_volume_scan, one pass over the label volume), the z-range cut + float32 conversion + transpose to slices (hv_volume_slices), the three
-    chained synthesis stages batched over all slices (`_stage_device`), the float64 output volumes (hv_volume_merge) and their download.  Buffers
+    Per host volume the host does ONE thing with the data: it copies the three float64 [A0, A1, A2] arrays into a pinned buffer (three threads; numpy
+    releases the GIL).  Everything else runs on the device: the upload (copy stream), the slice-extent scan and the neighbours' pixel counts
+    (hv_volume_scan_view, one pass over the label volume), the range cut + float32 conversion + layout as slices (hv_volume_slices_view), the three
+    chained synthesis stages batched over all slices (`_stage_device`), the output volumes (hv_volume_merge_view) and their download.  Buffers
     are double: while the compute stream runs volume n's stages, volume n + 1 is copied to pinned memory (worker thread), uploaded and scanned
-    (copy stream) and volume n - 1's outputs come down (output stream) -- one host wait per volume (its 3 x Z scan counts decide S, the z-range and
-    which neighbour stages run)."""
+    (copy stream) and volume n - 1's outputs come down (output stream) -- one host wait per volume (its 3 x N scan counts decide S, the slice range and
+    which neighbour stages run).  An input that is a device tensor skips the pinned copy and the upload and is scanned and sliced where it lies;
+    output='device' leaves the two output volumes on the device (no download)."""
 
-    def __init__(self, model, device, maxheight=40):
+    def __init__(self, model, device, maxheight=40, view='sagittal'):
         from concurrent.futures import ThreadPoolExecutor
         from . import engine
-        self.model, self.dev, self.maxheight = model, torch.device(device), maxheight
+        if view not in VIEWS:
+            raise ValueError("unknown view %r: expected 'sagittal' or 'coronal'" % (view,))
+        self.model, self.dev, self.maxheight, self.view = model, torch.device(device), maxheight, view
         self.copy_stream = engine.named_stream('volume-upload', self.dev)
         self.out_stream = engine.named_stream('volume-download', self.dev)
         self.slots = [None, None]
         self.stager = ThreadPoolExecutor(max_workers=1)
 
-    def _slot(self, i, H, W, Z):
+    def _slot(self, i, shape):
         sl = self.slots[i]
-        if sl is None or sl['shape'] != (H, W, Z):
-            n = H * W * Z
+        if sl is None or sl['shape'] != shape:
+            N = shape[VIEWS[self.view]]
             sl = self.slots[i] = {
-                'shape': (H, W, Z),
-                'pin_in': torch.empty(3 * n, dtype=torch.float64).pin_memory(), 'dev_in': torch.empty(3 * n, dtype=torch.float64, device=self.dev),
-                'counts': torch.empty(3 * Z, dtype=torch.int32, device=self.dev), 'pin_counts': torch.empty(3 * Z, dtype=torch.int32).pin_memory(),
-                'dev_out': torch.empty(2 * n, dtype=torch.float64, device=self.dev), 'pin_out': torch.empty(2 * n, dtype=torch.float64).pin_memory(),
+                'shape': shape,
+                'counts': torch.empty(3 * N, dtype=torch.int32, device=self.dev), 'pin_counts': torch.empty(3 * N, dtype=torch.int32).pin_memory(),
                 'ev_in': torch.cuda.Event(), 'ev_done': torch.cuda.Event(), 'ev_out': torch.cuda.Event(), 'ev_free': None}
         return sl
 
-    def _stage_in(self, i, ct_data, label_data, cam_data, vert_id):
-        """Worker thread: the volume's three arrays -> pinned slot i -> device; scan; counts -> pinned.  Returns the slot (its ev_in says when)."""
+    def _buffer(self, sl, name):
+        """The slot's staging buffers, made when a volume first needs them (a resident stream needs none): pin_in / dev_in hold three float64 volumes,
+        dev_out / pin_out two."""
+        if name not in sl:
+            A0, A1, A2 = sl['shape']
+            n = (3 if name.endswith('_in') else 2) * A0 * A1 * A2
+            sl[name] = torch.empty(n, dtype=torch.float64).pin_memory() if name.startswith('pin') else torch.empty(n, dtype=torch.float64, device=self.dev)
+        return sl[name]
+
+    def _stage_in(self, i, ct_data, label_data, cam_data, vert_id, ready):
+        """Worker thread: the volume's host arrays -> pinned slot i -> device; scan; counts -> pinned.  Returns the slot (its ev_in says when).
+        `ready`: event of the caller's stream, recorded when the volume was handed over (what produced a device input has been queued before it)."""
         import numpy as np
-        H, W, Z = label_data.shape
-        sl = self._slot(i, H, W, Z)
+        shape = tuple(label_data.shape)
+        A0, A1, A2 = shape
+        sl = self._slot(i, shape)
         if sl['ev_free'] is not None:
             sl['ev_free'].synchronize()          # the compute stream has read this slot's previous volume out of dev_in
-        n = H * W * Z
-        pin = sl['pin_in'].numpy().reshape(3, H, W, Z)
-        _parallel([(lambda k=k, vol=vol: np.copyto(pin[k], vol, casting='unsafe')) for k, vol in enumerate((label_data, ct_data, cam_data))])
+        n = A0 * A1 * A2
+        vols = (label_data, ct_data, cam_data)
+        host = [k for k, vol in enumerate(vols) if not isinstance(vol, torch.Tensor)]
+        srcs = list(vols)
+        if host:
+            pin = self._buffer(sl, 'pin_in').numpy().reshape(3, A0, A1, A2)
+            dev_in = self._buffer(sl, 'dev_in')
+            _parallel([(lambda k=k: np.copyto(pin[k], vols[k], casting='unsafe')) for k in host])
         L = _lib.get()
         nbs = [float(nb) if cond else -1.0 for nb, cond in ((vert_id - 1, vert_id > 8), (vert_id + 1, vert_id < 24))]
         with torch.cuda.stream(self.copy_stream):
-            sl['dev_in'].copy_(sl['pin_in'], non_blocking=True)
-            L.call('hv_volume_scan', ptr(sl['dev_in']), ctypes.c_longlong(H * W), Z, ctypes.c_double(float(vert_id)), ctypes.c_double(nbs[0]),
-                   ctypes.c_double(nbs[1]), ptr(sl['counts']), stream())
+            if len(host) == 3:
+                dev_in.copy_(sl['pin_in'], non_blocking=True)
+            for k in host:
+                if len(host) < 3:
+                    dev_in[k * n:(k + 1) * n].copy_(sl['pin_in'][k * n:(k + 1) * n], non_blocking=True)
+                srcs[k] = dev_in[k * n:(k + 1) * n]
+            if len(host) < 3:
+                self.copy_stream.wait_event(ready)
+                if 0 not in host:
+                    srcs[0].record_stream(self.copy_stream)
+            L.call('hv_volume_scan_view', ptr(srcs[0]), _DT[srcs[0].dtype], A0, A1, A2, VIEWS[self.view], ctypes.c_double(float(vert_id)),
+                   ctypes.c_double(nbs[0]), ctypes.c_double(nbs[1]), ptr(sl['counts']), stream())
             sl['pin_counts'].copy_(sl['counts'], non_blocking=True)
             sl['ev_in'].record(self.copy_stream)
-        sl['vert_id'] = vert_id
+        sl['vert_id'], sl['srcs'], sl['resident'], sl['ready'] = vert_id, srcs, [k for k in range(3) if k not in host], ready if len(host) < 3 else None
         return sl
 
-    def _compute(self, sl):
-        """Main thread: wait for the slot's scan counts, plan the z-range, queue the stages, the output volumes and their download."""
+    def _compute(self, sl, output):
+        """Main thread: wait for the slot's scan counts, plan the slice range, queue the stages, the output volumes and (output='host') their download."""
         L = _lib.get()
-        H, W, Z = sl['shape']
+        A0, A1, A2 = shape = sl['shape']
+        axis, N, (H, W) = view_geometry(shape, self.view)
         vert_id, dev = sl['vert_id'], self.dev
         sl['ev_in'].synchronize()                # the only host wait of the volume (the upload + scan ran while the previous volume computed)
-        counts = sl['pin_counts'].numpy().reshape(3, Z)
+        counts = sl['pin_counts'].numpy().reshape(3, N)
         zhas = counts[0].nonzero()[0]
         main = torch.cuda.current_stream(dev)
-        n = H * W * Z
-        out = sl['dev_out'].view(2, n)
+        n = A0 * A1 * A2
+        if output == 'device':
+            out = sl['result'] = [torch.empty(shape, dtype=torch.float64, device=dev) for _ in range(2)]      # fresh: the caller owns them
+        else:
+            out = self._buffer(sl, 'dev_out').view(2, n)
         sl['empty'] = zhas.size == 0
         S = 0
         if not sl['empty']:
@@ -237,18 +309,23 @@ class VolumePipeline:
             S = nz1 - nz0 + 1
         if S <= 0:
             sl['empty'] = True
-            sl['dev_out'].zero_()
+            for o in (out if output == 'device' else [sl['dev_out']]):
+                o.zero_()
         else:
             main.wait_event(sl['ev_in'])
+            if sl['ready'] is not None:
+                main.wait_event(sl['ready'])
             vols = torch.empty(3, S, H, W, dtype=torch.float32, device=dev)
-            for k in range(3):
-                L.call('hv_volume_slices', ptr(sl['dev_in'][k * n:(k + 1) * n]), ctypes.c_longlong(H * W), Z, nz0, S, ptr(vols[k]), stream())
+            for k, src in enumerate(sl['srcs']):
+                if k in sl['resident']:
+                    src.record_stream(main)      # a caller's tensor: its memory is not reused before the cut below has run
+                L.call('hv_volume_slices_view', ptr(src), _DT[src.dtype], A0, A1, A2, axis, nz0, S, ptr(vols[k]), stream())
             sl['ev_free'] = torch.cuda.Event()
             sl['ev_free'].record(main)           # dev_in may take the next volume
             st = {'lab': vols[0], 'ct': vols[1], 'cam': vols[2],
                   'ratio': torch.tensor([abs(z - centre) / rng_len * 2 for z in range(nz0, nz1 + 1)], dtype=torch.float64, device=dev)}
             # the neighbour stages run on the slices where the neighbour has > 200 pixels on the ORIGINAL labels (reference :208,:217): the scan counted
-            # them per z, so the host already knows which stages run and on which slices
+            # them per slice, so the host already knows which stages run and on which slices
             for j, (nb, cond) in enumerate(((vert_id - 1, vert_id > 8), (vert_id + 1, vert_id < 24))):
                 if cond:
                     sel = counts[1 + j, nz0:nz1 + 1] > 200
@@ -256,64 +333,92 @@ class VolumePipeline:
                         _stage_device(self.model, st, nb, torch.from_numpy(sel.astype('int32')).to(dev, non_blocking=True), self.maxheight)
             valid = _stage_device(self.model, st, vert_id, None, self.maxheight)
             for k, name in enumerate(('ct', 'lab')):
-                L.call('hv_volume_merge', ptr(st[name]), ptr(valid), ctypes.c_longlong(H * W), Z, nz0, S, ptr(out[k]), stream())
+                L.call('hv_volume_merge_view', ptr(st[name]), ptr(valid), A0, A1, A2, axis, nz0, S, _DT[torch.float64], ptr(out[k]), stream())
+        sl['srcs'] = None                        # the slices are cut (queued on streams the inputs are recorded on): the caller's tensors may go
+        if output == 'device':
+            return
         sl['ev_done'].record(main)
         with torch.cuda.stream(self.out_stream):
             self.out_stream.wait_event(sl['ev_done'])
-            sl['pin_out'].copy_(sl['dev_out'], non_blocking=True)
+            self._buffer(sl, 'pin_out').copy_(sl['dev_out'], non_blocking=True)
             sl['ev_out'].record(self.out_stream)
 
-    def _finish(self, sl, copy):
+    def _finish(self, sl, copy, output):
         import numpy as np
-        H, W, Z = sl['shape']
+        if output == 'device':
+            res, sl['result'] = sl['result'], None
+            return res[0], res[1]
+        shape = sl['shape']
         sl['ev_out'].synchronize()
-        res = sl['pin_out'].numpy().reshape(2, H, W, Z)
+        res = sl['pin_out'].numpy().reshape((2,) + shape)
         if not copy:
             return res[0], res[1]
-        outs = [np.empty((H, W, Z), dtype=np.float64), np.empty((H, W, Z), dtype=np.float64)]
+        outs = [np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)]
         _parallel([lambda: np.copyto(outs[0], res[0]), lambda: np.copyto(outs[1], res[1])])
         return outs[0], outs[1]
 
-    def run(self, volumes, copy=True):
-        """volumes: iterable of (ct_data, label_data, cam_data, vert_id) -- float64 [H, W, Z] arrays, ct in 0..255, cam already scaled by 255
-        (reference :181).  Yields (output_ct, output_seg) [H, W, Z] float64 per volume, in order.  copy=False hands out views of the pinned download
-        buffers instead of fresh arrays: a view is valid only until the generator is advanced again -- the NEXT `next()` call queues the download of the
-        volume after next into the same pinned slot (two slots), before the following result is yielded.  Consume (or copy) each result before asking
-        for the next one."""
+    def _submit(self, i, vol):
+        """Check one volume's arguments (ValueError before any of its GPU work) and hand it to the worker thread."""
+        ct_data, label_data, cam_data, vert_id = vol
+        check_volume_inputs(ct_data, label_data, cam_data, self.view, self.dev)
+        ready = None
+        if any(isinstance(v, torch.Tensor) for v in vol[:3]):
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(self.dev))
+        return self.stager.submit(self._stage_in, i, ct_data, label_data, cam_data, vert_id, ready)
+
+    def run(self, volumes, copy=True, output='host'):
+        """volumes: iterable of (ct_data, label_data, cam_data, vert_id) -- [A0, A1, A2] volumes, ct in 0..255, cam already scaled by 255 (reference
+        :181), each a numpy array (converted to float64 on the way into pinned memory) or a contiguous float64 / float32 / uint8 tensor on the pipeline's
+        device (read where it lies, never written; it may be freed or overwritten -- on the stream that was current when the iterable handed it over --
+        as soon as the next result has been yielded).  Yields (output_ct, output_seg) [A0, A1, A2] float64 per volume, in order.
+        output='host': numpy arrays.  copy=False hands out views of the pinned download buffers instead of fresh arrays: a view is valid only until the
+        generator is advanced again -- the NEXT `next()` call queues the download of the volume after next into the same pinned slot (two slots), before
+        the following result is yielded.  Consume (or copy) each result before asking for the next one.
+        output='device': fresh device tensors the caller owns, queued on the current stream; no download and no host wait beyond the scan counts."""
+        if output not in ('host', 'device'):
+            raise ValueError("unknown output %r: expected 'host' or 'device'" % (output,))
         it = iter(volumes)
         nxt = next(it, None)
         if nxt is None:
             return
-        fut = self.stager.submit(self._stage_in, 0, *nxt)
+        fut = self._submit(0, nxt)
         i, prev = 0, None
         while fut is not None:
             sl = fut.result()
             nxt = next(it, None)
-            fut = self.stager.submit(self._stage_in, (i + 1) & 1, *nxt) if nxt is not None else None
-            self._compute(sl)
+            fut = self._submit((i + 1) & 1, nxt) if nxt is not None else None
+            self._compute(sl, output)
             if prev is not None:
-                yield self._finish(prev, copy)
+                yield self._finish(prev, copy, output)
             prev, i = sl, i + 1
-        yield self._finish(prev, copy)
+        yield self._finish(prev, copy, output)
 
 
 _PIPELINES = {}
 
 
-def process_volumes(model, volumes, device, maxheight=40, copy=True):
-    """Generator over (output_ct, output_seg) for an iterable of (ct_data, label_data, cam_data, vert_id): `VolumePipeline.run`."""
-    key = (id(model), str(device), maxheight)
+def process_volumes(model, volumes, device, maxheight=40, copy=True, view='sagittal', output='host'):
+    """Generator over (output_ct, output_seg) for an iterable of (ct_data, label_data, cam_data, vert_id): `VolumePipeline.run` of the cached pipeline
+    of (model, device, maxheight, view)."""
+    if view not in VIEWS:
+        raise ValueError("unknown view %r: expected 'sagittal' or 'coronal'" % (view,))
+    if output not in ('host', 'device'):
+        raise ValueError("unknown output %r: expected 'host' or 'device'" % (output,))
+    key = (id(model), str(device), maxheight, view)
     pipe = _PIPELINES.get(key)
     if pipe is None:
-        pipe = _PIPELINES[key] = VolumePipeline(model, device, maxheight)
-    return pipe.run(volumes, copy=copy)
+        pipe = _PIPELINES[key] = VolumePipeline(model, device, maxheight, view)
+    return pipe.run(volumes, copy=copy, output=output)
 
 
-def process_volume(model, ct_data, label_data, cam_data, vert_id, device, maxheight=40):
+def process_volume(model, ct_data, label_data, cam_data, vert_id, device, maxheight=40, view='sagittal', output='host'):
     """process_nii_files' per-volume body (reference :186-234) with the three chained syntheses (upper neighbour, lower neighbour, target) each
-    batched over ALL z-slices: 3 generator launches per volume instead of ~130 bs=1 calls, the slices staying on the device between the stages --
+    batched over ALL slices: 3 generator launches per volume instead of ~130 bs=1 calls, the slices staying on the device between the stages --
     component filter, bounding rows, band re-stacking and quantisation (run_model :46-98) included.  ct_data in 0..255, label_data = vertebra
-    ids, cam_data already scaled by 255 (reference :181).  Returns (output_ct [H,W,Z], output_seg [H,W,Z]) as float64 numpy arrays (zeros outside
-    the processed z range).  One volume through `VolumePipeline`; a loop over volumes should use `process_volumes`, which overlaps their transfers.
+    ids, cam_data already scaled by 255 (reference :181); view='sagittal' slices `[:, :, z]` as the reference does, view='coronal' `[:, z, :]`.
+    Returns (output_ct, output_seg) [A0, A1, A2] as float64 numpy arrays, or device tensors with output='device' (zeros outside the processed
+    slice range).  One volume through `VolumePipeline`; a loop over volumes should use `process_volumes`, which overlaps their transfers.
     (Where the reference would raise -- a neighbour stage returning None, :212,:221 -- the slice passes through unchanged.)"""
-    return next(process_volumes(model, [(ct_data, label_data, cam_data, vert_id)], device, maxheight))
+    check_volume_inputs(ct_data, label_data, cam_data, view, device)
+    return next(process_volumes(model, [(ct_data, label_data, cam_data, vert_id)], device, maxheight, view=view, output=output))

@@ -642,6 +642,20 @@ int hv_slice_count(const float* label, int S, long long per_slice, float value, 
 int hv_volume_scan(const double* label, long long HW, int Z, double id0, double id1, double id2, int* counts, void* stream);
 int hv_volume_slices(const double* vol, long long HW, int Z, int z0, int S, float* out, void* stream);
 int hv_volume_merge(const float* src, const int* flag, long long HW, int Z, int z0, int S, double* out, void* stream);
+/* The same three for either in-plane slice axis of a C-contiguous volume [A0][A1][A2] (element (a0, a1, a2) at (a0 * A1 + a1) * A2 + a2) of dtype HV_DT_F64,
+ * HV_DT_F32 or HV_DT_U8 (codes below; uint8 is what hv_straighten_crop leaves for labels): axis = 2 slices `[:, :, k]` (sagittal, planes [A0][A1]: the
+ * entries above, bit for bit on float64), axis = 1 slices `[:, k, :]` (coronal, planes [A0][A2]: evaluation/RHLV_quantification_coronal.py:51-54).  N = the
+ * size of the slice axis, C = the other in-plane axis (A1 for axis 2, A2 for axis 1).
+ * hv_volume_scan_view: counts[j * N + k] = number of voxels of slice k equal to id_j (id rules as hv_volume_scan).  counts: 3 * N ints, zeroed by the
+ *   call.  axis 2: A2 <= 2048.
+ * hv_volume_slices_view: out[s][a0][c] = (float)vol[...] for slices k0 .. k0 + S - 1: the range cut out, converted (C cast) and laid out as [S][A0][C] float32.
+ * hv_volume_merge_view: every element of out ([A0][A1][A2], out_dtype HV_DT_F64 -- the reference's volume -- or HV_DT_F32 -- what a resident consumer
+ *   such as hv_rhlv reads without a conversion) is written: src[k - k0][a0][c] where k0 <= k < k0 + S and flag[k - k0], 0 elsewhere.
+ * HV_ERR_ARG: null pointer, non-positive size, axis other than 1 / 2, unknown dtype, an id of 0, k0 < 0, S <= 0, k0 + S > N.  HV_ERR_UNSUPPORTED: A0 * A1 or
+ *   A0 * A2 > 2^31, A2 > 2048 (scan, axis 2), S (slices) or N (merge) > 65535 on axis 1 / > 32 * 65535 on axis 2. */
+int hv_volume_scan_view(const void* label, int dtype, int A0, int A1, int A2, int axis, double id0, double id1, double id2, int* counts, void* stream);
+int hv_volume_slices_view(const void* vol, int dtype, int A0, int A1, int A2, int axis, int k0, int S, float* out, void* stream);
+int hv_volume_merge_view(const float* src, const int* flag, int A0, int A1, int A2, int axis, int k0, int S, int out_dtype, void* out, void* stream);
 
 /* ---- spine straightening and per-vertebra volume extraction (reference straighten/location_json_local.py:14-16,33-45,
  * straighten/straighten_mask_3d.py:123-146,172-184,222-247,463-563, straighten/curve.py:54-102) ----
