@@ -10,7 +10,10 @@ back of that record, the curve math on the host (a few hundred points, numpy), t
 requested vertebra (csrc/straighten.hip).
 
   vertebra_centroids(label) -> [{"label", "X", "Y", "Z"}, ...]             the JSON list location_json_local.py writes
-  straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64)) -> {vert_id: (ct_vol, label_vol)}
+  straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), depedicle=False) -> {vert_id: (ct_vol, label_vol)}
+  depedicle(label_vol, out=None) -> uint8 volume            process_3d_array (straighten_mask_3d.py:189-219) on a crop or a batch of crops
+  component_counts(label_vol) -> int32 [Z, 256]             4-connected components of every label value per slice
+  single_component_range(label_vol, label, offset=10)       find_single_component_layers (:249-280) -> (z0, z1)
 
 Volumes are [X, Y, Z] device tensors as nibabel hands them over (any strides; a Fortran-ordered array passes as it lies).  The CT may be
 int16, float32 or float64 and is windowed in double for every dtype.  Deviation: the reference reads CT files over 500 MB as float32
@@ -264,10 +267,106 @@ def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE):
     return knots, basis, local, boxes
 
 
-def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False):
+def _depedicle_launch(vol4, out4, counts):
+    """One hv_depedicle launch for a [V, A0, A1, Z] batch (csrc/depedicle.hip) and the read back of its status words."""
+    L = _lib.get()
+    V, A0, A1, Z = vol4.shape
+    status = torch.empty(V, dtype=torch.int32, device=vol4.device)
+    sv, s0, s1, s2 = _strides(vol4)
+    if out4 is None:
+        optr, (ov, o0, o1, o2) = None, [ctypes.c_longlong(0)] * 4
+    else:
+        optr, (ov, o0, o1, o2) = _lib.ptr(out4), _strides(out4)
+    L.call('hv_depedicle', _lib.ptr(vol4), _DT[vol4.dtype], s0, s1, s2, sv, A0, A1, Z, V, optr, o0, o1, o2, ov, _lib.ptr(counts),
+           _lib.ptr(status), _lib.stream())
+    st = status.cpu().numpy()
+    if (st & 1).any():
+        raise ValueError('depedicle: the label volume holds values that are not integers in [0, 255]')
+    if (st & 2).any():
+        where = '' if counts is None else ': (volume, slice) %s' % [tuple(int(i) for i in r) for r in (counts[:, :, 0] < 0).nonzero().cpu().numpy()]
+        raise RuntimeError('depedicle: the labelling of a slice did not converge' + where)
+
+
+def _as_batch(label_vol, what):
+    _lib.require_gpu(label_vol)
+    if label_vol.dim() not in (3, 4):
+        raise ValueError('%s: expected a [A0, A1, Z] volume or a [V, A0, A1, Z] batch, got %s' % (what, tuple(label_vol.shape)))
+    _dtype_code(label_vol, tuple(_DT), 'label')
+    if label_vol.numel() == 0:
+        raise ValueError('%s: empty volume %s' % (what, tuple(label_vol.shape)))
+    return label_vol if label_vol.dim() == 4 else label_vol.unsqueeze(0)
+
+
+def depedicle(label_vol, out=None):
+    """process_3d_array (straighten_mask_3d.py:215-219) on the device: in every slice [:, :, z] and for every label value, only the 4-connected
+    component that reaches the smallest index on axis 1 stays (ties: the component scipy numbers first), which cuts the vertebral arches off.
+    label_vol: a [A0, A1, Z] volume or a [V, A0, A1, Z] batch (one launch), integer values 0..255 in any dtype of _DT, any strides; a slice
+    holds at most 65536 pixels.  out: None or a uint8 device tensor of the same shape (any strides; may be label_vol itself).  -> out."""
+    vol4 = _as_batch(label_vol, 'depedicle')
+    if out is None:
+        out = torch.empty(tuple(label_vol.shape), dtype=torch.uint8, device=label_vol.device)
+    else:
+        _lib.require_gpu(out)
+        if out.dtype != torch.uint8 or tuple(out.shape) != tuple(label_vol.shape) or out.device != label_vol.device:
+            raise ValueError('depedicle: out must be a uint8 tensor of shape %s on the device of the labels' % (tuple(label_vol.shape),))
+    V, _, _, Z = vol4.shape
+    counts = torch.empty(V, Z, 256, dtype=torch.int32, device=vol4.device)
+    _depedicle_launch(vol4, out if out.dim() == 4 else out.unsqueeze(0), counts)
+    return out
+
+
+def component_counts(label_vol):
+    """-> int32 device tensor [Z, 256] ([V, Z, 256] for a batch): the number of 4-connected components of every label value in every slice
+    [:, :, z] (scipy.ndimage.label(layer == value)[1]; 0 for an absent value and for value 0)."""
+    vol4 = _as_batch(label_vol, 'component_counts')
+    V, _, _, Z = vol4.shape
+    counts = torch.empty(V, Z, 256, dtype=torch.int32, device=vol4.device)
+    _depedicle_launch(vol4, None, counts)
+    return counts if label_vol.dim() == 4 else counts[0]
+
+
+def single_component_walk(ncomp, offset=10):
+    """The walk of find_single_component_layers (straighten_mask_3d.py:255-280) over the per-slice component counts of one label: from
+    mid - offset downwards and from mid + offset upwards (both start indices clamped to the volume) to the first slice with exactly one
+    component; z0 = 1 and z1 = 128 where none is found."""
+    Z = len(ncomp)
+    mid = Z // 2
+    start_left, start_right = max(0, mid - offset), min(Z - 1, mid + offset)
+    z0, z1 = 1, 128
+    for i in range(start_left, -1, -1):
+        if ncomp[i] == 1:
+            z0 = i
+            break
+    for i in range(start_right, Z):
+        if ncomp[i] == 1:
+            z1 = i
+            break
+    return z0, z1
+
+
+def single_component_range(label_vol, label, offset=10):
+    """find_single_component_layers(data, label) (straighten_mask_3d.py:249-280) for one [A0, A1, Z] device volume: the slice range over
+    which vertebra `label` is one piece, from one read back of that label's count column."""
+    _lib.require_gpu(label_vol)
+    if label_vol.dim() != 3:
+        raise ValueError('single_component_range: expected one [A0, A1, Z] volume, got %s' % (tuple(label_vol.shape),))
+    counts = component_counts(label_vol)
+    if float(label) == int(label) and 1 <= int(label) <= 255:
+        col = counts[:, int(label)].cpu().numpy()
+    else:                                   # no voxel can hold it: no slice qualifies
+        col = np.zeros(counts.shape[0], dtype=np.int32)
+    return single_component_walk(col, offset)
+
+
+_depedicle = depedicle
+
+
+def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False, depedicle=False):
     """process_mask3d(ct, label, json, vertebrae_ids, out, out_size) on device tensors (straighten_mask_3d.py:463-563, mask_2d and file I/O
     excepted).  ct: [X, Y, Z] int16 / float32 / float64; label: [X, Y, Z] integer values 0..255 in any integer or float dtype.  centroids:
     the list location_json_local.py writes, or None = computed on the device from the same stats pass.
+    depedicle: the label crops of all requested vertebrae go through one de-pedicling launch, in place, before they are returned (the
+    process_3d_array call the reference keeps commented out in process_mask3d).
     -> {vert_id: (ct_vol float64, label_vol uint8)}, each [out_size] on the device, the orientation the reference saves."""
     ctc, lc = _check(ct, label)
     L = _lib.get()
@@ -303,6 +402,8 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
         else:   # one centroid: the windowed raw CT and the raw label are cropped at the raw position (:499-502)
             L.call('hv_straighten_crop', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), Y, win, wmin, wmax,
                    _lib.ptr(rec[_PRES:]), _lib.ptr(d_boxes), V, O0, O1, O2, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
+        if depedicle:
+            _depedicle(lab_out, out=lab_out)
     out = {vid: (ct_out[i], lab_out[i]) for i, vid in enumerate(vertebrae_ids)}
     if return_plan:
         return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win)}

@@ -690,6 +690,25 @@ int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs
                        long long ls0, long long ls1, long long ls2, int D1, int window, double win_min, double win_max, const uint64_t* presence,
                        const int* boxes, int V, int O0, int O1, int O2, double* ct_out, uint8_t* label_out, void* stream);
 
+/* ---- de-pedicling of label crops (reference straighten/straighten_mask_3d.py:189-219 process_layer / process_3d_array and :249-280
+ * find_single_component_layers).  V volumes [A0][A1][Z]: element (i0, i1, z) of volume v at
+ * label[v*lsv + i0*ls0 + i1*ls1 + z*ls2] (strides in elements, any order; label_dtype one of the HV_DT_* codes above), values integers in
+ * [0, 255].  Per slice [:, :, z], with the raster index p = i0*A1 + i1: pixels are joined iff they are 4-neighbours (never diagonal) holding
+ * the same non-zero value (the union over the values of scipy.ndimage.label(layer == value) with the default structure); a component's
+ * identity is its smallest raster index; per value the component with the smallest (min i1 over the component, identity) is kept and every
+ * other pixel of that value becomes 0.
+ * out: uint8, element at out[v*osv + i0*os0 + i1*os1 + z*os2]; may be the label buffer itself when that is uint8 with the same strides (a
+ *   slice is read completely before it is written).  NULL with counts != NULL: the counts only.
+ * counts: NULL or [V][Z][256] int32: the number of components of every value 1..255 in the slice (0 for an absent value); entry 0 is 0, or -1
+ *   for a slice whose labelling hit its iteration bound.
+ * status: [V] int32, zeroed by the call; bit 0: the volume holds a value that is not an integer in [0, 255] (nothing else is promised for
+ *   that slice), bit 1: a slice did not converge (see counts).
+ * The labelling state lives in LDS (one 16-bit parent per pixel), no workspace.  HV_ERR_ARG: label or status NULL, out and counts both NULL,
+ * a non-positive size, an unknown dtype code.  HV_ERR_UNSUPPORTED: A0 * A1 > 65536 (128 KiB of parents is what fits the 160 KiB of LDS; the
+ * reference's crops are 256 x 256 x 64) or V > 65535.  In both cases nothing is launched and nothing is written. */
+int hv_depedicle(const void* label, int label_dtype, long long ls0, long long ls1, long long ls2, long long lsv, int A0, int A1, int Z, int V,
+                 uint8_t* out, long long os0, long long os1, long long os2, long long osv, int* counts, int* status, void* stream);
+
 /* ---- generation-quality evaluation of a synthesized volume (reference evaluation/generation_eval_sagittal.py:11-37 calculate_iou /
  * calculate_dice / relative_volume_difference, :39-103 process_images; generation_eval_coronal.py the same with the slice axis 1; SURVEY.md
  * row 17).  Four [H][W][Z] volumes: element (h, w, z) of the CTs at base[h*cs0 + w*cs1 + z*cs2], of the labels
