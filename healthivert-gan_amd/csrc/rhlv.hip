@@ -126,33 +126,41 @@ __global__ __launch_bounds__(256) void rhlv_tot_kernel(char* __restrict__ ws, Rh
     if (threadIdx.x == 0) tot[v * V.S + s] = red[0];
 }
 
+// The slices [lo, hi) a script walks on an axis of Z slices, from the original vertebra's voxels per slice (tot_label[Z]): lo_in == INT_MIN: centre
+// = int(mean slice index), half-length = extent // divisor like process_datasets_to_excel, else the explicit [lo_in, hi_in); numpy's slice
+// normalisation either way.  One lane walks the axis: rhlv_range_kernel per view, rhlv_sweep_final_kernel per divisor.
+struct RhlvRange { int lo, hi, cz, len, valid; };
+__device__ __forceinline__ RhlvRange rhlv_slice_range(const int* __restrict__ tot_label, int Z, int divisor, int lo_in, int hi_in) {
+    int lo, hi, cz = 0, len = 0, valid = 1;
+    if (lo_in == INT_MIN) {
+        long long n = 0, sz = 0;
+        int mn = Z, mx = -1;
+        for (int z = 0; z < Z; ++z) {
+            const int t = tot_label[z];
+            if (t > 0) { n += t; sz += (long long)t * z; mn = min(mn, z); mx = max(mx, z); }
+        }
+        if (n == 0) { valid = 0; lo = hi = 0; }
+        else {
+            cz = (int)((double)sz / (double)n);          // int(np.mean(loc))
+            len = (mx - mn) / divisor;                  // (max_z - min_z) // length_divisor
+            lo = cz - len; hi = cz + len;
+        }
+    } else { lo = lo_in; hi = hi_in; cz = (lo_in + hi_in) / 2; len = (hi_in - lo_in) / 2; }
+    // numpy slice normalisation of [lo:hi] on an axis of length Z
+    if (lo < 0) lo = max(lo + Z, 0);
+    if (hi < 0) hi = max(hi + Z, 0);
+    lo = min(lo, Z); hi = min(hi, Z);
+    return {lo, hi, cz, len, valid};
+}
+
 // params: [0] lo, [1] hi, [2] centre slice, [3] length, [4] valid (label has voxels)
 __global__ void rhlv_range_kernel(char* __restrict__ ws, RhlvPlan P) {
     if (threadIdx.x != 0) return;
     const RhlvView& V = P.view[blockIdx.y];
     const int* tot = (const int*)(rhlv_slab(ws, P) + V.tot);
     int* params = (int*)(rhlv_slab(ws, P) + V.params);
-    const int Z = V.S;
-    int lo, hi, cz = 0, len = 0, valid = 1;
-    if (V.lo == INT_MIN) {
-        long long n = 0, sz = 0;
-        int mn = Z, mx = -1;
-        for (int z = 0; z < Z; ++z) {
-            const int t = tot[Z + z];
-            if (t > 0) { n += t; sz += (long long)t * z; mn = min(mn, z); mx = max(mx, z); }
-        }
-        if (n == 0) { valid = 0; lo = hi = 0; }
-        else {
-            cz = (int)((double)sz / (double)n);          // int(np.mean(loc))
-            len = (mx - mn) / V.divisor;                // (max_z - min_z) // length_divisor
-            lo = cz - len; hi = cz + len;
-        }
-    } else { lo = V.lo; hi = V.hi; cz = (V.lo + V.hi) / 2; len = (V.hi - V.lo) / 2; }
-    // numpy slice normalisation of [lo:hi] on an axis of length Z
-    if (lo < 0) lo = max(lo + Z, 0);
-    if (hi < 0) hi = max(hi + Z, 0);
-    lo = min(lo, Z); hi = min(hi, Z);
-    params[0] = lo; params[1] = hi; params[2] = cz; params[3] = len; params[4] = valid;
+    const RhlvRange R = rhlv_slice_range(tot + V.S, V.S, V.divisor, V.lo, V.hi);
+    params[0] = R.lo; params[1] = R.hi; params[2] = R.cz; params[3] = R.len; params[4] = R.valid;
 }
 
 __device__ __forceinline__ long long rhlv_block_sum(long long v, long long* sh) {
@@ -250,6 +258,15 @@ __global__ __launch_bounds__(256) void rhlv_slice_kernel(char* __restrict__ ws, 
 // out[0..4] = all, pre, mid, post RHLV, relative height of the original; out[5..12] = the eight mean heights
 // (all_f, all_l, pre_f, pre_l, mid_f, mid_l, post_f, post_l); out[13] = 1 if the original vertebra exists, else 0;
 // 16-double records: out[14] = 1 if the reference would have raised (coronal view), out[15] = 0
+__device__ __forceinline__ void rhlv_write_record(double* __restrict__ out, const double (&m)[8], int valid, long long raises, int out_len) {
+    for (int c = 0; c < 4; ++c) out[c] = (m[2 * c] - m[2 * c + 1]) / (m[2 * c] + 1e-6);
+    const double mn = fmin(m[3], fmin(m[5], m[7])), mx = fmax(m[3], fmax(m[5], m[7]));
+    out[4] = mn / (mx + 1e-6);
+    for (int i = 0; i < 8; ++i) out[5 + i] = m[i];
+    out[13] = (double)valid;
+    if (out_len > 14) { out[14] = (double)raises; out[15] = 0.0; }
+}
+
 __global__ void rhlv_final_kernel(char* __restrict__ ws, RhlvPlan P, double* __restrict__ out, int out_len) {
     if (threadIdx.x != 0) return;
     const RhlvView& V = P.view[blockIdx.y];
@@ -272,12 +289,153 @@ __global__ void rhlv_final_kernel(char* __restrict__ ws, RhlvPlan P, double* __r
         m[2 * c] = nf > 0 ? sf / (double)nf : 0.0;
         m[2 * c + 1] = nl > 0 ? sl / (double)nl : 0.0;
     }
-    for (int c = 0; c < 4; ++c) out[c] = (m[2 * c] - m[2 * c + 1]) / (m[2 * c] + 1e-6);
-    const double mn = fmin(m[3], fmin(m[5], m[7])), mx = fmax(m[3], fmax(m[5], m[7]));
-    out[4] = mn / (mx + 1e-6);
-    for (int i = 0; i < 8; ++i) out[5 + i] = m[i];
-    out[13] = (double)params[4];
-    if (out_len > 14) { out[14] = (double)raises; out[15] = 0.0; }
+    rhlv_write_record(out, m, params[4], raises, out_len);
+}
+
+// ---- the parameter sweep (hv_rhlv_sweep): every (length_divisor, height_threshold) of a grid from one pass over the volumes.  Neither parameter
+// touches the table or a slice's thirds, maxima, ratios and centre heights; the threshold selects columns, the divisor selects slices.
+//   rhlv_sweep_slice_kernel   grid (S, views, N): EVERY slice where both vertebrae have voxels (the range differs per divisor): the
+//                             threshold-independent state once (RhlvSweepSlice), then per threshold the integer sums of rhlv_slice_kernel
+//   rhlv_sweep_final_kernel   grid (ceil(D*T/64), views, N): one lane per grid point: that divisor's range, the ordered fold of rhlv_final_kernel
+// A pair's slab is the other entries' (rhlv_plan) followed by, per view, RhlvSweepSlice[S] and RhlvSweepRec[S][T].
+struct RhlvSweepSlice { double ratio[4]; int on, raises; };
+struct RhlvSweepRec { int Sf[4], nf[4], Sl[4], nl[4]; };    // a slice's sums are at most H * C: hv_rhlv_sweep refuses shapes where that passes INT_MAX
+struct RhlvSweepPlan { long long state[2], recs[2]; };       // per view: byte offsets in a pair's slab
+
+__device__ __forceinline__ int rhlv_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int rhlv_wave_count(bool p) { return __popcll(__ballot(p)); }
+
+__global__ __launch_bounds__(256) void rhlv_sweep_slice_kernel(char* __restrict__ ws, RhlvPlan P, RhlvSweepPlan Q, hv_rhlv_grid G) {
+    __shared__ long long sh[256];
+    __shared__ int part[HV_RHLV_MAX_THRESHOLDS][4][14];   // per threshold and wave: Sf all, pre, mid, post | nf the same | Sl pre, mid, post | nl the same
+    const RhlvView& V = P.view[blockIdx.y];
+    const int z = blockIdx.x, Z = V.S, W = V.C, tid = threadIdx.x, T = G.n_thresholds;
+    if (z >= Z) return;                                  // the grid is as wide as the longer view
+    const long long sc = V.sc;
+    const int* tot = (const int*)(rhlv_slab(ws, P) + V.tot);
+    RhlvSweepSlice* st = (RhlvSweepSlice*)(rhlv_slab(ws, P) + Q.state[blockIdx.y]) + z;
+    RhlvSweepRec* recs = (RhlvSweepRec*)(rhlv_slab(ws, P) + Q.recs[blockIdx.y]) + (long long)z * T;
+    const int* cf = (const int*)(rhlv_slab(ws, P) + P.cnt) + (long long)z * V.ss;     // column w of this slice: cf[w * sc]
+    const int* cl = cf + (long long)P.Z * P.W;
+    if (!(tot[z] > 0 && tot[Z + z] > 0)) {               // no script visits it, whatever the range: the fold skips its records
+        if (tid < 4) st->ratio[tid] = 1.0;
+        if (tid == 0) { st->on = 0; st->raises = 0; }
+        return;
+    }
+    // the threshold-independent state, in rhlv_slice_kernel's expressions
+    int ymin = W, ymax = -1;
+    long long swf = 0, swl = 0;
+    for (int w = tid; w < W; w += 256) {
+        if (cf[w * sc] > 0) { ymin = min(ymin, w); ymax = max(ymax, w); }
+        swf += (long long)cf[w * sc] * w;
+        swl += (long long)cl[w * sc] * w;
+    }
+    ymax = rhlv_block_max(ymax, sh);
+    ymin = -rhlv_block_max(-ymin, sh);
+    swf = rhlv_block_sum(swf, sh);
+    swl = rhlv_block_sum(swl, sh);
+    const int y_range = ymax - ymin;
+    const int t1 = (int)((double)ymin + (double)y_range / 3.0);            // int(y_min + y_range/3)
+    const int t2 = (int)((double)ymin + (double)(2 * y_range) / 3.0);      // int(y_min + 2*y_range/3)
+    const int ccf = (int)((double)swf / (double)tot[z]);                   // int(np.mean(loc))
+    const int ccl = (int)((double)swl / (double)tot[Z + z]);
+    const int center_f_i = cf[ccf * sc], center_l = cl[ccl * sc];
+    const int r0[4] = {0, 0, t1, t2}, r1[4] = {W, t1, t2, W};
+    double ratio[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        int mf = -1, ml = -1;
+        for (int w = r0[c] + tid; w < r1[c]; w += 256) { mf = max(mf, cf[w * sc]); ml = max(ml, cl[w * sc]); }
+        mf = rhlv_block_max(mf, sh);
+        ml = rhlv_block_max(ml, sh);
+        const double den = V.coronal ? (double)mf : (double)mf + 1e-6;    // see rhlv_slice_kernel
+        ratio[c] = (r1[c] > r0[c] && ml > mf) ? (double)ml / den : 1.0;
+    }
+    const double center_f = (double)center_f_i * ratio[0];
+    if (tid == 0) {
+        for (int c = 0; c < 4; ++c) st->ratio[c] = ratio[c];
+        st->on = 1;
+        st->raises = V.coronal && (t1 <= 0 || t2 <= t1);
+    }
+    // per threshold: a column counts for the whole slice (ratio[0]) and for its own third (that third's ratio); the original's test is the same in
+    // both, so its whole-slice sums are the thirds' added up.  Integer sums: a wave folds its 64 columns by shuffles, the counts by ballots,
+    // lane 0 keeps the wave's running sums in LDS; one barrier, then one lane per threshold adds the four waves.
+    const int wave = tid >> 6, lane = tid & 63;
+    for (int k = 0; k < W; k += 256) {                   // block-uniform: every lane takes part in the shuffles
+        const int w = k + tid;
+        const bool live = w < W;
+        const int f = live ? cf[w * sc] : 0, l = live ? cl[w * sc] : 0;
+        const int reg = w < t1 ? 1 : w < t2 ? 2 : 3;
+        const double hf_all = (double)f * ratio[0], hf_reg = (double)f * (reg == 1 ? ratio[1] : reg == 2 ? ratio[2] : ratio[3]), hl = (double)l;
+        for (int t = 0; t < T; ++t) {
+            const double thr_f = center_f * G.threshold[t], thr_l = (double)center_l * G.threshold[t];
+            const bool sa = live && hf_all > thr_f, sr = live && hf_reg > thr_f, sl = live && hl > thr_l;
+            int v[14];
+            v[0] = rhlv_wave_sum(sa ? f : 0);
+            v[4] = rhlv_wave_count(sa);
+#pragma unroll
+            for (int c = 1; c < 4; ++c) {
+                v[c] = rhlv_wave_sum(sr && reg == c ? f : 0);
+                v[4 + c] = rhlv_wave_count(sr && reg == c);
+                v[7 + c] = rhlv_wave_sum(sl && reg == c ? l : 0);
+                v[10 + c] = rhlv_wave_count(sl && reg == c);
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 14; ++i) part[t][wave][i] = k == 0 ? v[i] : part[t][wave][i] + v[i];
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < T; t += 256) {
+        int v[14];
+#pragma unroll
+        for (int i = 0; i < 14; ++i) v[i] = part[t][0][i] + part[t][1][i] + part[t][2][i] + part[t][3][i];
+        RhlvSweepRec r;
+        r.Sl[0] = r.nl[0] = 0;
+#pragma unroll
+        for (int c = 1; c < 4; ++c) { r.Sl[c] = v[7 + c]; r.nl[c] = v[10 + c]; r.Sl[0] += v[7 + c]; r.nl[0] += v[10 + c]; }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { r.Sf[c] = v[c]; r.nf[c] = v[4 + c]; }
+        recs[t] = r;
+    }
+}
+
+// out [N][D][T][views][16]: hv_rhlv_views' records
+__global__ __launch_bounds__(64) void rhlv_sweep_final_kernel(const char* __restrict__ ws, RhlvPlan P, RhlvSweepPlan Q, hv_rhlv_grid G,
+                                                              double* __restrict__ out) {
+    const int D = G.n_divisors, T = G.n_thresholds;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= D * T) return;
+    const int d = i / T, t = i - d * T;
+    const RhlvView& V = P.view[blockIdx.y];
+    const char* slab = ws + (long long)blockIdx.z * P.pair_bytes;
+    const RhlvSweepSlice* st = (const RhlvSweepSlice*)(slab + Q.state[blockIdx.y]);
+    const RhlvSweepRec* recs = (const RhlvSweepRec*)(slab + Q.recs[blockIdx.y]);
+    const RhlvRange R = rhlv_slice_range((const int*)(slab + V.tot) + V.S, V.S, G.divisor[d], INT_MIN, 0);
+    double m[8];
+    long long raises = 0;
+    for (int c = 0; c < 4; ++c) {
+        double sf = 0.0, sl = 0.0;
+        long long nf = 0, nl = 0;
+        for (int z = R.lo; z < R.hi; ++z) {              // rhlv_final_kernel's fold: the slices outside add nothing there
+            if (!st[z].on) continue;
+            const RhlvSweepRec& r = recs[(long long)z * T + t];
+            if (r.nf[c] > 0) sf += (double)r.Sf[c] * st[z].ratio[c];
+            sl += (double)r.Sl[c];
+            nf += r.nf[c];
+            nl += r.nl[c];
+            raises |= st[z].raises;
+        }
+        m[2 * c] = nf > 0 ? sf / (double)nf : 0.0;
+        m[2 * c + 1] = nl > 0 ? sl / (double)nl : 0.0;
+    }
+    out += ((((long long)blockIdx.z * D + d) * T + t) * P.nviews + blockIdx.y) * 16;
+    rhlv_write_record(out, m, R.valid, raises, 16);
 }
 
 // Output pointers of one view for n_pairs pairs, each NULL = not wanted: loss / hf / hl / flags [N][S][C], colp [N][3][C], slicep [N][3][S],
@@ -386,11 +544,11 @@ static RhlvPlan rhlv_plan(int W, int Z, int views, const hv_rhlv_view* sagittal,
     return P;
 }
 
-// the launch sequence of every entry: one pair passed by value (pairs == NULL, n_pairs 1) or a device table of n_pairs pointer pairs
-static int rhlv_run(const void* fake, const void* label, const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h,
-                    long long stride_w, long long stride_z, int H, float label_index, const RhlvPlan& P, double* out, int out_len, void* workspace,
-                    hipStream_t s, const RhlvMapOuts* maps = nullptr) {
-    char* ws = (char*)workspace;
+// the pass over the volumes and the per-slice totals, the start of every entry: one pair passed by value (pairs == NULL, n_pairs 1) or a device
+// table of n_pairs pointer pairs
+static int rhlv_launch_table(const void* fake, const void* label, const void* pairs, const float* label_indices, int n_pairs, int dtype,
+                             long long stride_h, long long stride_w, long long stride_z, int H, float label_index, const RhlvPlan& P, char* ws,
+                             hipStream_t s) {
     const void* const* pp = (const void* const*)pairs;
     const bool zfast = stride_z == 1 && stride_w != 1;   // z fastest in memory: lanes along z
     const dim3 grid = zfast ? dim3(hv_cdiv((long long)P.W * P.Z, 256), 2, n_pairs) : dim3(P.Z, 2, n_pairs);
@@ -407,13 +565,24 @@ static int rhlv_run(const void* fake, const void* label, const void* pairs, cons
         hipLaunchKernelGGL((rhlv_counts_kernel<unsigned char>), grid, dim3(256), 0, s, (const unsigned char*)fake, (const unsigned char*)label, pp,
                            label_indices, stride_h, stride_w, stride_z, H, label_index, ws, P);
     HV_LAUNCH_CHECK();
-    int smax = 0;
     for (int i = 0; i < P.nviews; ++i) {
-        smax = P.view[i].S > smax ? P.view[i].S : smax;
         if (!P.view[i].coronal && !zfast) continue;      // the lanes-along-w counts kernel left the sagittal totals
         hipLaunchKernelGGL(rhlv_tot_kernel, dim3(P.view[i].S, 2, n_pairs), dim3(256), 0, s, ws, P, i);
         HV_LAUNCH_CHECK();
     }
+    return HV_OK;
+}
+
+static int rhlv_longer_view(const RhlvPlan& P) { return P.nviews > 1 && P.view[1].S > P.view[0].S ? P.view[1].S : P.view[0].S; }
+
+// the launch sequence of the one-setting entries
+static int rhlv_run(const void* fake, const void* label, const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h,
+                    long long stride_w, long long stride_z, int H, float label_index, const RhlvPlan& P, double* out, int out_len, void* workspace,
+                    hipStream_t s, const RhlvMapOuts* maps = nullptr) {
+    char* ws = (char*)workspace;
+    const int rc = rhlv_launch_table(fake, label, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, label_index, P, ws, s);
+    if (rc != HV_OK) return rc;
+    const int smax = rhlv_longer_view(P);
     hipLaunchKernelGGL(rhlv_range_kernel, dim3(1, P.nviews, n_pairs), dim3(64), 0, s, ws, P);
     HV_LAUNCH_CHECK();
     if (maps) hipLaunchKernelGGL(rhlv_slice_kernel<true>, dim3(smax, P.nviews, n_pairs), dim3(256), 0, s, ws, P);
@@ -527,4 +696,50 @@ extern "C" int hv_rhlv_maps_batch(const void* pairs, const float* label_indices,
     const RhlvMapOuts O = rhlv_map_outs(views, h_sagittal_out, h_coronal_out);
     return rhlv_run(nullptr, nullptr, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, 0.f,
                     rhlv_plan(W, Z, views, h_sagittal, h_coronal, true), out, 16, workspace, (hipStream_t)stream, &O);
+}
+
+// the sweep's plan: the one-setting entries' slab, then per view RhlvSweepSlice[S] and RhlvSweepRec[S][T]
+static RhlvPlan rhlv_sweep_plan(int W, int Z, int views, int T, RhlvSweepPlan* Q) {
+    RhlvPlan P = rhlv_plan(W, Z, views, nullptr, nullptr);
+    long long off = P.pair_bytes;
+    for (int i = 0; i < P.nviews; ++i) { Q->state[i] = off; off += (long long)P.view[i].S * sizeof(RhlvSweepSlice); }
+    for (int i = 0; i < P.nviews; ++i) { Q->recs[i] = off; off += (long long)P.view[i].S * T * sizeof(RhlvSweepRec); }
+    P.pair_bytes = off;
+    return P;
+}
+
+static bool rhlv_grid_counts_ok(int n_divisors, int n_thresholds) {
+    return n_divisors >= 1 && n_divisors <= HV_RHLV_MAX_DIVISORS && n_thresholds >= 1 && n_thresholds <= HV_RHLV_MAX_THRESHOLDS;
+}
+
+extern "C" size_t hv_rhlv_sweep_workspace_bytes(int W, int Z, int views, int n_pairs, int n_divisors, int n_thresholds) {
+    if (W <= 0 || Z <= 0 || n_pairs <= 0 || views < 1 || views > (HV_RHLV_SAGITTAL | HV_RHLV_CORONAL) || !rhlv_grid_counts_ok(n_divisors, n_thresholds))
+        return 0;
+    RhlvSweepPlan Q = {};
+    return (size_t)rhlv_sweep_plan(W, Z, views, n_thresholds, &Q).pair_bytes * n_pairs;
+}
+
+extern "C" int hv_rhlv_sweep(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                             long long stride_z, int H, int W, int Z, int views, const hv_rhlv_grid* h_grid, double* out, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (!pairs || !label_indices || !out || !h_grid || n_pairs <= 0 || H <= 0 || W <= 0 || Z <= 0 || (dtype != 0 && dtype != 1) || views < 1 ||
+        views > (HV_RHLV_SAGITTAL | HV_RHLV_CORONAL))
+        return HV_ERR_ARG;
+    if (!rhlv_grid_counts_ok(h_grid->n_divisors, h_grid->n_thresholds)) return HV_ERR_UNSUPPORTED;
+    for (int d = 0; d < h_grid->n_divisors; ++d)
+        if (h_grid->divisor[d] <= 0) return HV_ERR_UNSUPPORTED;
+    if (Z > 65535 || W > 65535 || n_pairs > 65535 || (long long)H * (W > Z ? W : Z) > INT_MAX) return HV_ERR_UNSUPPORTED;
+    const int D = h_grid->n_divisors, T = h_grid->n_thresholds;
+    if (!workspace || workspace_bytes < hv_rhlv_sweep_workspace_bytes(W, Z, views, n_pairs, D, T) || ((uintptr_t)workspace & 7)) return HV_ERR_WORKSPACE;
+    RhlvSweepPlan Q = {};
+    const RhlvPlan P = rhlv_sweep_plan(W, Z, views, T, &Q);
+    char* ws = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = rhlv_launch_table(nullptr, nullptr, pairs, label_indices, n_pairs, dtype, stride_h, stride_w, stride_z, H, 0.f, P, ws, s);
+    if (rc != HV_OK) return rc;
+    hipLaunchKernelGGL(rhlv_sweep_slice_kernel, dim3(rhlv_longer_view(P), P.nviews, n_pairs), dim3(256), 0, s, ws, P, Q, *h_grid);
+    HV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rhlv_sweep_final_kernel, dim3(hv_cdiv((long long)D * T, 64), P.nviews, n_pairs), dim3(64), 0, s, (const char*)ws, P, Q, *h_grid, out);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
 }

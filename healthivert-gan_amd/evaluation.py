@@ -10,6 +10,9 @@ ratios without the sagittal script's + 1e-6, ValueError where it takes max() of 
   rhlv_volume_25d(vol_fake, vol_label, label_index, ...)   both views from one pass over the volumes, one readback
   rhlv_dataset(fakes, labels, label_indices, ...)          N pairs of equal shape: one launch sequence per chunk, one readback in all
   svm_features(records, file1='sagittal')                  the six feature columns in SVM_grading_2.5d.py's order
+  rhlv_sweep(fakes, labels, label_indices, length_divisors, height_thresholds, ...)   rhlv_dataset at every point of a parameter grid
+                                                           (the reference's ParameterGrid tuning) from one pass over each pair
+  svm_feature_grid(sweep)                                  the six feature columns at every grid point
 and what the reference's README draws from those scripts' per-column heights (the distribution of height loss over the vertebra's
 cross-section and the curve of height loss along it), left on the device:
   height_loss_map(vol_fake, vol_label, label_index, ...)       per view: loss / height maps [S, C], flags, column and slice profiles
@@ -168,6 +171,76 @@ def svm_features(records, file1='sagittal'):
     other view's (its `_2` columns)."""
     first = 0 if VIEWS[file1] == SAGITTAL else 1
     return np.concatenate([records[:, first, 1:4], records[:, 1 - first, 1:4]], axis=1)
+
+
+# ---------------------------------------------------------------- parameter sweep (hv_rhlv_sweep)
+MAX_DIVISORS, MAX_THRESHOLDS = 16, 32       # HV_RHLV_MAX_DIVISORS, HV_RHLV_MAX_THRESHOLDS: longer grids are split over several calls
+SWEEP_WORKSPACE = 1 << 30                   # pairs per launch sequence are limited to this many workspace bytes
+
+
+def rhlv_sweep(fakes, labels, label_indices, length_divisors=(5,), height_thresholds=(0.64,), views=('sagittal', 'coronal'), chunk=256):
+    """rhlv_dataset at every (length_divisor, height_threshold) of a grid from ONE pass over each volume pair (hv_rhlv_sweep): the tuning the
+    reference imports sklearn's ParameterGrid for.  fakes / labels: N [H, W, Z] volumes of one shape, dtype and stride pattern (device tensors;
+    arrays and host tensors are uploaded), one vertebra id per pair; one launch sequence and one readback per `chunk` pairs.
+    -> {'records': float64 numpy [N, D, T, V, 16] (hv_rhlv_views' record per grid point and view, bit for bit rhlv_dataset's at that setting),
+        'length_divisors': [D], 'height_thresholds': [T], 'views': the V view names in the records' order (sagittal first),
+        'raised': bool numpy [N, D] -- the coronal script would have raised on a slice of that divisor's range (all False without the coronal view)}
+    Nothing raises per vertebra or per setting: a sweep reports the settings that are unusable.  records[..., 13] == 0 where the original lacks
+    the vertebra."""
+    L = _lib.get()
+    bits = _view_bits(views)
+    names = tuple(v for v in VIEWS if bits & VIEWS[v])
+    divs, thrs = [int(d) for d in length_divisors], [float(t) for t in height_thresholds]
+    n = len(fakes)
+    if n == 0 or len(labels) != n or len(label_indices) != n:
+        raise ValueError('rhlv_sweep: equally many (at least one) generated volumes, original volumes and label indices expected')
+    if not divs or not thrs or any(d <= 0 for d in divs):
+        raise ValueError('rhlv_sweep: at least one length divisor (each > 0) and one height threshold expected')
+    first = fakes[0]
+    dev = first.device if isinstance(first, torch.Tensor) and first.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    fakes, labels = [_prep(t, dev) for t in fakes], [_prep(t, dev) for t in labels]
+    geo = (fakes[0].shape, fakes[0].stride(), fakes[0].dtype)
+    for t in fakes + labels:
+        _lib.require_gpu(t)
+        if t.dim() != 3 or (t.shape, t.stride(), t.dtype) != geo or t.device != dev:
+            raise ValueError('rhlv_sweep: [H, W, Z] float32 or uint8 volumes of one shape, dtype and stride pattern expected')
+    H, W, Z = geo[0]
+    D, T, V = len(divs), len(thrs), len(names)
+    table = torch.tensor([p for f, l in zip(fakes, labels) for p in (f.data_ptr(), l.data_ptr())], dtype=torch.int64).to(dev)
+    ids = torch.tensor([float(i) for i in label_indices], dtype=torch.float32).to(dev)
+    chunk = max(1, min(int(chunk), n))
+    per_pair = L.size('hv_rhlv_sweep_workspace_bytes', W, Z, bits, 1, min(D, MAX_DIVISORS), min(T, MAX_THRESHOLDS))
+    chunk = max(1, min(chunk, SWEEP_WORKSPACE // max(1, per_pair)))
+    ws, _ = ops._ws(per_pair * chunk, dev, slot=3)
+    records = np.empty((n, D, T, V, 16), dtype=np.float64)
+    for i in range(0, n, chunk):
+        m = min(chunk, n - i)
+        whole = torch.empty(m, D, T, V, 16, dtype=torch.float64, device=dev)
+        for d0 in range(0, D, MAX_DIVISORS):
+            for t0 in range(0, T, MAX_THRESHOLDS):
+                dd, tt = divs[d0:d0 + MAX_DIVISORS], thrs[t0:t0 + MAX_THRESHOLDS]
+                grid = L.hv_rhlv_grid(len(dd), (ctypes.c_int * MAX_DIVISORS)(*dd), len(tt), (ctypes.c_double * MAX_THRESHOLDS)(*tt))
+                part = whole if (len(dd), len(tt)) == (D, T) else torch.empty(m, len(dd), len(tt), V, 16, dtype=torch.float64, device=dev)
+                L.call('hv_rhlv_sweep', _lib.ptr(table[2 * i:]), _lib.ptr(ids[i:]), m, *_geometry(fakes[0]), bits, ctypes.byref(grid),
+                       _lib.ptr(part), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream())
+                if part is not whole:
+                    whole[:, d0:d0 + len(dd), t0:t0 + len(tt)] = part
+        records[i:i + m] = whole.cpu().numpy()
+    raised = records[:, :, 0, names.index('coronal'), 14] != 0 if 'coronal' in names else np.zeros((n, D), dtype=bool)
+    return {'records': records, 'length_divisors': np.array(divs), 'height_thresholds': np.array(thrs), 'views': names, 'raised': raised}
+
+
+def svm_feature_grid(sweep):
+    """rhlv_sweep's result (both views) -> float64 [N, D, T, 6]: svm_features' columns (Pre / Mid / Post RHLV of the sagittal view, then of the
+    coronal view) at every grid point; NaN where the coronal script would have raised at that divisor or the original lacks the vertebra."""
+    rec, names = np.asarray(sweep['records']), tuple(sweep['views'])
+    if set(names) != set(VIEWS):
+        raise ValueError('svm_feature_grid: a sweep of both views expected')
+    sag, cor = names.index('sagittal'), names.index('coronal')
+    feats = np.concatenate([rec[:, :, :, sag, 1:4], rec[:, :, :, cor, 1:4]], axis=-1)
+    unusable = np.asarray(sweep['raised'], dtype=bool)[:, :, None] | (rec[:, :, :, sag, 13] == 0)
+    feats[unusable] = np.nan
+    return feats
 
 
 # ---------------------------------------------------------------- per-column height-loss maps and profiles (hv_rhlv_maps)

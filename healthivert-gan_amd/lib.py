@@ -49,6 +49,9 @@ def _strip_comments(src):
 def parse_header(path=HEADER):
     """-> (structs: name -> ctypes.Structure subclass, protos: name -> (restype, [argtypes]))."""
     src = _strip_comments(open(path).read())
+    consts = {}                          # enumerators with an explicit value: the extents of array fields
+    for body in re.findall(r'enum\s*\w*\s*\{(.*?)\}', src, flags=re.S):
+        consts.update((n, int(v, 0)) for n, v in re.findall(r'(\w+)\s*=\s*(-?\w+)\s*(?:,|$)', body.strip()) if re.fullmatch(r'-?(0x)?[0-9a-fA-F]+', v))
     structs = {}
     for body, name in re.findall(r'typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;', src, flags=re.S):
         fields = []
@@ -62,7 +65,12 @@ def parse_header(path=HEADER):
                 nm = nm.strip()
                 extra = nm.count('*')
                 nm = nm.replace('*', '').strip()
-                fields.append((nm, _ctype(tname + '*' * extra, structs)))
+                ct = _ctype(tname + '*' * extra, structs)
+                arr = re.fullmatch(r'(\w+)\s*\[\s*(\w+)\s*\]', nm)      # name[extent], the extent a number or an enumerator
+                if arr:
+                    nm, ext = arr.group(1), arr.group(2)
+                    ct = ct * (int(ext) if ext.isdigit() else consts[ext])
+                fields.append((nm, ct))
         structs[name] = type(name, (ctypes.Structure,), {'_fields_': fields})
     protos = {}
     body = re.sub(r'typedef\s+struct\s*\{.*?\}\s*\w+\s*;', ' ', src, flags=re.S)
@@ -87,7 +95,9 @@ def ctypes_source(struct_name, path=HEADER, width=118):
     """Python source of the ctypes mirror of one struct of include/hvgan.h, generated from the header: the snippet INTEGRATION.md shows
     a maintainer of the reference (tools/gen_integration_stub.py writes it there; tests/test_host_cpu.py checks the two agree)."""
     structs, _ = parse_header(path)
-    fields = ['("%s", %s)' % (n, _CTYPES_NAME[t]) for n, t in structs[struct_name]._fields_]
+    def tname(t):
+        return '%s * %d' % (_CTYPES_NAME[t._type_], t._length_) if issubclass(t, ctypes.Array) else _CTYPES_NAME[t]
+    fields = ['("%s", %s)' % (n, tname(t)) for n, t in structs[struct_name]._fields_]
     lines, cur = [], '    _fields_ = ['
     for i, f in enumerate(fields):
         piece = f + (', ' if i + 1 < len(fields) else ']')

@@ -586,6 +586,31 @@ int hv_rhlv_maps_batch(const void* pairs, const float* label_indices, int n_pair
                        const hv_rhlv_map_out* h_sagittal_out, const hv_rhlv_map_out* h_coronal_out, double* out, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- RHLV parameter sweep: every (length_divisor, height_threshold) of a grid from one pass over the volumes (the tuning the reference's
+ * evaluation/RHLV_quantification.py imports sklearn's ParameterGrid for; its defaults are 5 / 0.64, its main() passes 0.7) ----
+ * pairs, label_indices, dtype, strides and `views` as for hv_rhlv_views_batch.  Neither parameter touches the column-count table or a slice's
+ * thirds, maxima, rescale ratios and centre heights: the volumes are read once per pair, the threshold then only selects columns of the
+ * L2-resident table and the divisor only selects which slices are folded.  h_grid (HOST, copied into the kernel arguments: 328 bytes) lists
+ * 1 ... HV_RHLV_MAX_DIVISORS divisors (each > 0) and 1 ... HV_RHLV_MAX_THRESHOLDS thresholds; a count outside that, a divisor <= 0 or a shape
+ * with H * max(W, Z) > INT_MAX returns HV_ERR_UNSUPPORTED with nothing launched.  The slice range always derives from the original vertebra's
+ * extent (hv_rhlv_view's explicit [lo, hi) form is not part of the sweep).
+ * out (device): [n_pairs][n_divisors][n_thresholds][views][16] doubles, each record laid out like hv_rhlv_views' ([13] the original exists,
+ * [14] the coronal script would have raised -- a property of the divisor's slices, not of the threshold) and bit for bit the record
+ * hv_rhlv_views_batch gives at that single setting, whatever the rest of the grid and of the batch.  No atomics, no cross-lane floating-point
+ * sums.  workspace: hv_rhlv_sweep_workspace_bytes(W, Z, views, n_pairs, n_divisors, n_thresholds) bytes (0 for arguments the entry refuses),
+ * 8-byte aligned: the one-setting entries' slab plus 64 bytes per (slice, threshold) of every view and pair. */
+enum { HV_RHLV_MAX_DIVISORS = 16, HV_RHLV_MAX_THRESHOLDS = 32 };
+typedef struct {
+    int n_divisors;
+    int divisor[HV_RHLV_MAX_DIVISORS];
+    int n_thresholds;
+    double threshold[HV_RHLV_MAX_THRESHOLDS];
+} hv_rhlv_grid;
+size_t hv_rhlv_sweep_workspace_bytes(int W, int Z, int views, int n_pairs, int n_divisors, int n_thresholds);
+int hv_rhlv_sweep(const void* pairs, const float* label_indices, int n_pairs, int dtype, long long stride_h, long long stride_w,
+                  long long stride_z, int H, int W, int Z, int views, const hv_rhlv_grid* h_grid, double* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- batch assembly on the device (reference data/aligned_dataset.py:204-280, AlignedDataset.__getitem__) ----
  * One item = one sagittal slice of a vertebra volume whose four uint8 planes [H][W] are resident on the device: ct = ct_data.astype(uint8)
  * (:245), vert = component-filtered vertebra mask * 255 (:247-248), normal = the patient's normal vertebrae as 0/255 (:190-196), cam =
