@@ -25,6 +25,10 @@ def precision_note(precision):
 
 
 # ================================================================================================ parameters
+# weight_prep_kernel (csrc/prep.hip) stages a spectral-norm layer's v and u in LDS arrays of PREP_MAXK = 4608 and PREP_MAXCO = 1024 floats
+SN_MAX_K, SN_MAX_COUT = 4608, 1024
+
+
 class ConvParams:
     """One convolution's parameters and their kernel-layout copies.
 
@@ -41,6 +45,11 @@ class ConvParams:
         self.u, self.v = u, v
         self.sn = u is not None
         self.transposed_src = transposed_src
+        if self.sn and transposed_src:
+            # the sigma kernel reads the source as [cout][cin*taps]; a conv-transpose source is [cin][cout][taps] (no model builds the combination)
+            raise ValueError('%s: spectral norm on a transposed_src (conv-transpose) weight is not supported' % name)
+        if self.sn and (cin * self.taps > SN_MAX_K or cout > SN_MAX_COUT):
+            raise ValueError('%s: spectral norm takes cin * k * k <= %d and cout <= %d (got %d, %d)' % (name, SN_MAX_K, SN_MAX_COUT, cin * self.taps, cout))
         self.w_fwd = self.w_bwd = self.sigma = self.dw = None
         self.w_fwd_t = self.w_bwd_t = None      # fp16 tables in MFMA-fragment order (None: the shape has no tiled form)
         # which prepared tables the layer's forward / data-gradient convolutions have read so far (hv_last_weight_tables bits: 1 fp32, 2 fp16 rows, 4 fp16

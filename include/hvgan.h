@@ -486,7 +486,12 @@ int hv_adam_step(const hv_adam_tensor* d_tensors, int n_tensors, long long max_n
  * flat_grad[n_grad] -- the network's flat gradient buffer, after any all-reduce -- is checked first and multiplied by grad_mul on the way (1 / the loss
  * scale, a power of two; 1 = left alone); if it holds a non-finite value the whole step is skipped (weights, moments and step count unchanged) and
  * d_state[2] counts it.  d_state: 8 floats {step count, scratch, skipped steps, scratch, ticket, -, -, -}, zero-initialised by the caller.  Two launches
- * (check + update); device-side only (no host read): safe inside a captured graph. */
+ * (check + update); device-side only (no host read): safe inside a captured graph.
+ * "Non-finite" is the test !(|g| <= 3.0e38) on the values before the multiplication: inf and nan, and also the finite fp32 values above 3.0e38 (up to
+ * FLT_MAX = 3.4e38) count as an overflow; 3.0e38 itself passes.  The multiplication by grad_mul happens on good and skipped steps alike: after the call
+ * flat_grad holds the unscaled gradient either way (a non-finite element stays non-finite).  After every call d_state[1] and the ticket d_state[4] are back
+ * at zero and d_state[3] says whether THIS step was skipped (1) or taken (0).  Returns HV_ERR_ARG -- before any launch -- for a NULL pointer,
+ * n_tensors / max_numel / n_grad <= 0, a flat_grad that is not 16-byte aligned or a grad_mul that is not > 0 (nan included). */
 int hv_adam_step_guarded(const hv_adam_tensor* d_tensors, int n_tensors, long long max_numel, const float* d_lr, float beta1,
                          float beta2, float eps, float* d_state, float* flat_grad, long long n_grad, float grad_mul, void* stream);
 

@@ -366,3 +366,69 @@ def test_attention_scores_are_a_box_filter_on_the_pixel_gram_matrix():
     T = T.view(L, L)
     assert (S - T / torch.clamp(norm, min=1e-4).view(L, 1)).abs().max().item() <= 1e-4
     assert (T.diagonal().sqrt() - norm).abs().max().item() <= 1e-4
+
+
+def test_conv_params_refuses_spectral_norm_on_a_conv_transpose_source():
+    """weight_prep_kernel reads a spectral-norm layer's weight as [cout][cin * taps]; a transposed_src weight is [cin][cout][taps].  No model builds the
+    combination, and ConvParams refuses it where it used to yield a wrong sigma silently."""
+    import hvgan  # noqa: F401
+    from hvgan import engine
+    w = torch.zeros(8, 4, 3, 3)
+    engine.ConvParams('plain_t', w, None, 8, 4, 3, transposed_src=True)
+    engine.ConvParams('sn', torch.zeros(4, 8, 3, 3), None, 8, 4, 3, u=torch.zeros(4), v=torch.zeros(72))
+    with pytest.raises(ValueError, match='transposed_src'):
+        engine.ConvParams('sn_t', w, None, 8, 4, 3, u=torch.zeros(4), v=torch.zeros(72), transposed_src=True)
+
+
+def test_conv_params_refuses_a_spectral_norm_layer_beyond_the_sigma_kernels_lds_arrays():
+    """cin * k * k <= 4608 and cout <= 1024 (PREP_MAXK / PREP_MAXCO of csrc/prep.hip): the limits themselves pass, one more is a ValueError; layers without
+    spectral norm have no such limit."""
+    import re
+    import hvgan  # noqa: F401
+    from hvgan import engine
+    src = open(os.path.join(ROOT, 'healthivert-gan_amd', 'csrc', 'prep.hip')).read()
+    assert int(re.search(r'#define PREP_MAXK (\d+)', src).group(1)) == engine.SN_MAX_K == 4608
+    assert int(re.search(r'#define PREP_MAXCO (\d+)', src).group(1)) == engine.SN_MAX_COUT == 1024
+    sn = lambda cin, cout, k: engine.ConvParams('c', None, None, cin, cout, k, u=torch.zeros(cout), v=torch.zeros(cin * k * k))
+    sn(512, 8, 3)
+    sn(4, 1024, 2)
+    for cin, cout, k in ((513, 8, 3), (4609, 1, 1), (4, 1025, 2), (289, 8, 4)):
+        with pytest.raises(ValueError, match='4608'):
+            sn(cin, cout, k)
+    engine.ConvParams('plain', None, None, 1024, 2048, 3)
+
+
+def test_weight_path_entries_refuse_bad_arguments_before_any_launch():
+    """hv_adam_step(_guarded), hv_weight_prep(2) and hv_weight_prep_backward return HV_ERR_ARG / HV_ERR_UNSUPPORTED for these arguments before they touch
+    the device: callable without a GPU, on pointers that are never followed."""
+    import ctypes
+    import hvgan  # noqa: F401
+    from hvgan import lib
+    L = lib.get()
+    P = ctypes.c_void_p(0x10000)
+    tab = lambda s, v=0x10000: ctypes.cast(ctypes.c_void_p(v), ctypes.POINTER(getattr(L, s)))
+    ll, fl = ctypes.c_longlong, ctypes.c_float
+
+    def guarded(t=tab('hv_adam_tensor'), nt=1, mx=8, lr=P, st=P, g=P, n=8, mul=1.0):
+        L.call('hv_adam_step_guarded', t, nt, ll(mx), lr, fl(0.5), fl(0.999), fl(1e-8), st, g, ll(n), fl(mul), None)
+
+    bad = [dict(g=ctypes.c_void_p(0x10004)), dict(g=ctypes.c_void_p(0x10008)), dict(mul=0.0), dict(mul=-1.0), dict(mul=float('nan')), dict(n=0), dict(n=-4),
+           dict(nt=0), dict(mx=0), dict(t=tab('hv_adam_tensor', None)), dict(lr=None), dict(st=None), dict(g=None)]
+    for kw in bad:
+        with pytest.raises(RuntimeError, match='HV_ERR_ARG'):
+            guarded(**kw)
+    for t, nt, mx, lr, st in ((tab('hv_adam_tensor', None), 1, 8, P, P), (tab('hv_adam_tensor'), 0, 8, P, P), (tab('hv_adam_tensor'), 1, 0, P, P),
+                              (tab('hv_adam_tensor'), 1, 8, None, P), (tab('hv_adam_tensor'), 1, 8, P, None)):
+        with pytest.raises(RuntimeError, match='HV_ERR_ARG'):
+            L.call('hv_adam_step', t, nt, ll(mx), lr, fl(0.5), fl(0.999), fl(1e-8), st, None)
+    for t, n, mx in ((tab('hv_wprep_layer', None), 1, 8), (tab('hv_wprep_layer'), 0, 8), (tab('hv_wprep_layer'), 1, 0)):
+        with pytest.raises(RuntimeError, match='HV_ERR_ARG'):
+            L.call('hv_weight_prep', t, n, ll(mx), None)
+        with pytest.raises(RuntimeError, match='HV_ERR_ARG'):
+            L.call('hv_weight_prep2', t, n, ll(mx), 1, 1, None)
+    for t, n, mx in ((tab('hv_wprep_bwd_layer', None), 1, 8), (tab('hv_wprep_bwd_layer'), 0, 8), (tab('hv_wprep_bwd_layer'), 1, 0), (tab('hv_wprep_bwd_layer'), -1, 8)):
+        with pytest.raises(RuntimeError, match='HV_ERR_ARG'):
+            L.call('hv_weight_prep_backward', t, n, ll(mx), 1, None)
+    for mx in (1 << 31, (1 << 31) + 5, 1 << 40):
+        with pytest.raises(RuntimeError, match='HV_ERR_UNSUPPORTED'):
+            L.call('hv_weight_prep_backward', tab('hv_wprep_bwd_layer'), 1, ll(mx), 1, None)
