@@ -13,12 +13,16 @@ ratios without the sagittal script's + 1e-6, ValueError where it takes max() of 
   rhlv_sweep(fakes, labels, label_indices, length_divisors, height_thresholds, ...)   rhlv_dataset at every point of a parameter grid
                                                            (the reference's ParameterGrid tuning) from one pass over each pair
   svm_feature_grid(sweep)                                  the six feature columns at every grid point
+  svm_grade_grid(features, labels, dataset, ...)           the reference's grading (SVM_grading.py / SVM_grading_2.5d.py: scaler, 5-fold linear SVM,
+                                                           val-set scores) of every grid point in one launch sequence (hv_svm_grade_grid)
+  stratified_folds(y)                                      the unshuffled StratifiedKFold assignment the grading uses (host, labels only)
+  best_setting(sweep, grades, score='f1')                  the (length_divisor, height_threshold) with the best mean score
 and what the reference's README draws from those scripts' per-column heights (the distribution of height loss over the vertebra's
 cross-section and the curve of height loss along it), left on the device:
   height_loss_map(vol_fake, vol_label, label_index, ...)       per view: loss / height maps [S, C], flags, column and slice profiles
   height_loss_dataset(fakes, labels, label_indices, ...)       the same stacked over N pairs of equal shape
 Volumes are [H, W, Z] tensors (any strides; float32 or uint8) already resident in HBM, e.g. the label volume infer.process_volume
-just produced.  The file I/O / Excel part of the reference and the SVM stay on the host.
+just produced.  The file I/O / Excel part of the reference stays on the host.
 """
 import ctypes
 
@@ -241,6 +245,137 @@ def svm_feature_grid(sweep):
     unusable = np.asarray(sweep['raised'], dtype=bool)[:, :, None] | (rec[:, :, :, sag, 13] == 0)
     feats[unusable] = np.nan
     return feats
+
+
+# ---------------------------------------------------------------- SVM grading of every grid point (hv_svm_grade_grid)
+N_SPLITS, MAX_CLASSES, MAX_PAIR_ROWS, MAX_GRID = 5, 4, 1792, 65535    # HV_SVM_FOLDS, HV_SVM_MAX_CLASSES, HV_SVM_MAX_ROWS, the launch grid's z extent
+CONVERGED, HIT_MAX_ITER, PAIR_ABSENT, UNUSABLE, BAD_PLAN = 0, 1, 2, 3, 4   # HV_SVM_*: a problem's status
+SCORES = ('f1', 'precision', 'recall', 'accuracy')
+
+
+def stratified_folds(y, n_splits=N_SPLITS):
+    """The test fold of every row under scikit-learn 1.7.2's unshuffled StratifiedKFold(n_splits): the classes are numbered in order of first
+    appearance, the sorted labels dealt to the folds round robin give the number of rows of every class per fold, and a class's rows take
+    their folds in contiguous blocks of those sizes.  Depends on the labels only.  -> int32 [len(y)]"""
+    y = np.asarray(y)
+    if y.ndim != 1 or len(y) == 0:
+        raise ValueError('stratified_folds: a non-empty vector of labels expected')
+    _, first, inverse = np.unique(y, return_index=True, return_inverse=True)
+    encoded = np.argsort(np.argsort(first))[inverse]
+    counts = np.bincount(encoded)
+    if np.all(n_splits > counts):
+        raise ValueError('stratified_folds: n_splits=%d cannot be greater than the number of members in each class' % n_splits)
+    order = np.sort(encoded)
+    allocation = np.array([np.bincount(order[i::n_splits], minlength=len(first)) for i in range(n_splits)])
+    folds = np.empty(len(y), dtype=np.int32)
+    for k in range(len(first)):
+        folds[encoded == k] = np.arange(n_splits).repeat(allocation[:, k])
+    return folds
+
+
+def svm_grade_grid(features, labels, dataset, folds=None, tol=1e-3, max_iter=100000, decisions=False):
+    """The reference's grading (evaluation/SVM_grading.py with three feature columns, SVM_grading_2.5d.py with six) of EVERY grid point of a
+    sweep on the device: StandardScaler fitted on the train + test rows, SVC(kernel='linear', class_weight='balanced') with tolerance `tol`
+    (libsvm's 1e-3), StratifiedKFold(5), each fold's model applied to the val rows, confusion matrix and macro F1 / precision / recall /
+    accuracy per fold, their mean and np.var over the folds.
+    features [N, G..., F] (svm_feature_grid's [N, D, T, 6]; its first three columns alone reproduce SVM_grading.py), labels [N] small
+    non-negative integer grades (at most 4 different ones), dataset [N] of 'train' / 'test' / 'val', folds: the test fold (0..4) of every
+    train + test row in row order (default: stratified_folds of their labels).  Rows that are NaN at every grid point (vertebra absent) are
+    dropped.  One upload, one launch sequence, one readback.  ->
+      {'confusion' [G..., 5, K, K] (true x predicted), 'scores' [G..., 5, 4] (SCORES order), 'mean', 'var' [G..., 4] over the folds,
+       'pred' [G..., 5, Mv] (grades; -1 at an unusable grid point), 'w' [G..., 5, P, F], 'b', 'gap' [G..., 5, P] (decision = w . x_scaled - b, the pairs
+       (0,1), (0,2), ... of `classes`, positive = the lower class), 'iterations', 'status', 'support' [G..., 5, P], 'unusable' [G...] (a feature
+       of that grid point is not finite: nothing solved, NaN scores), 'classes' [K], 'folds' [M], 'rows_tt' / 'rows_val' (the rows of `features`
+       used), and with decisions=True 'decision' [G..., 5, Mv, P]}
+    Nothing raises per grid point: check 'unusable' and 'status' (CONVERGED, HIT_MAX_ITER, PAIR_ABSENT: a class of the pair does not occur
+    in that fold's training rows).  ValueError before any launch: F not 3 or 6, more than 4 grades, a class pair with more than 1792 training
+    rows in a fold (the solver keeps them in LDS), bad fold ids."""
+    feats = np.asarray(features, dtype=np.float64)
+    labels, dataset = np.asarray(labels), np.asarray(dataset)
+    if feats.ndim < 2 or labels.shape != feats.shape[:1] or dataset.shape != feats.shape[:1]:
+        raise ValueError('svm_grade_grid: features [N, G..., F] with one label and one dataset name per row expected')
+    grid, F = feats.shape[1:-1], feats.shape[-1]
+    if F not in (3, 6):
+        raise ValueError('svm_grade_grid: 3 or 6 feature columns expected, got %d' % F)
+    if not np.all(np.isin(dataset, ('train', 'test', 'val'))):
+        raise ValueError("svm_grade_grid: dataset entries must be 'train', 'test' or 'val'")
+    if not np.all(labels == np.floor(labels)) or np.any(labels < 0):
+        raise ValueError('svm_grade_grid: labels must be non-negative integers')
+    if not (tol > 0) or int(max_iter) < 1:
+        raise ValueError('svm_grade_grid: tol > 0 and max_iter >= 1 expected')
+    flat = feats.reshape(feats.shape[0], -1, F)
+    G = flat.shape[1]
+    if G == 0 or G > MAX_GRID:
+        raise ValueError('svm_grade_grid: between 1 and %d grid points expected' % MAX_GRID)
+    keep = ~np.isnan(flat).any(axis=2).all(axis=1)
+    rows_tt, rows_val = np.flatnonzero(keep & (dataset != 'val')), np.flatnonzero(keep & (dataset == 'val'))
+    M, Mv = len(rows_tt), len(rows_val)
+    if M == 0 or Mv == 0:
+        raise ValueError('svm_grade_grid: train / test rows and val rows expected')
+    y_tt, y_val = labels[rows_tt].astype(np.int32), labels[rows_val].astype(np.int32)
+    classes = np.unique(np.concatenate([y_tt, y_val])).astype(np.int32)
+    K = len(classes)
+    if K < 2 or K > MAX_CLASSES:
+        raise ValueError('svm_grade_grid: between 2 and %d different grades expected, got %d' % (MAX_CLASSES, K))
+    folds = stratified_folds(y_tt) if folds is None else np.ascontiguousarray(folds, dtype=np.int32)
+    if folds.shape != (M,):
+        raise ValueError('svm_grade_grid: one fold id per train / test row expected')
+    L = _lib.get()
+    y_tt, y_val, folds = np.ascontiguousarray(y_tt), np.ascontiguousarray(y_val), np.ascontiguousarray(folds, dtype=np.int32)
+    plan = np.zeros(L.size('hv_svm_grade_plan_bytes', M, Mv), dtype=np.uint8)
+    max_rows = ctypes.c_int(0)
+    rc = L.cdll.hv_svm_grade_plan(y_tt.ctypes.data, folds.ctypes.data, M, y_val.ctypes.data, Mv, classes.ctypes.data, K, plan.ctypes.data,
+                                  ctypes.c_size_t(plan.nbytes), ctypes.byref(max_rows))
+    if rc != 0:
+        raise ValueError('svm_grade_grid: %s' % ('a class pair has %d training rows in one fold, more than the %d the solver keeps in LDS'
+                                                 % (max_rows.value, MAX_PAIR_ROWS) if max_rows.value > MAX_PAIR_ROWS else
+                                                 'fold ids must be 0..%d (hv_svm_grade_plan: %s)' % (N_SPLITS - 1, _lib.ERRORS.get(rc, rc))))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    x_tt, x_val = np.ascontiguousarray(flat[rows_tt].transpose(1, 0, 2)), np.ascontiguousarray(flat[rows_val].transpose(1, 0, 2))
+    blob = torch.from_numpy(np.concatenate([x_tt.reshape(-1).view(np.uint8), x_val.reshape(-1).view(np.uint8), plan])).to(dev)
+    _lib.require_gpu(blob)
+    P = K * (K - 1) // 2
+    # one output buffer, the float64 arrays first: name -> (dtype, shape)
+    outs = [('w', np.float64, (G, N_SPLITS, P, F)), ('b', np.float64, (G, N_SPLITS, P)), ('gap', np.float64, (G, N_SPLITS, P)),
+            ('scores', np.float64, (G, N_SPLITS, 4)), ('mean', np.float64, (G, 4)), ('var', np.float64, (G, 4))]
+    if decisions:
+        outs.append(('decision', np.float64, (G, N_SPLITS, Mv, P)))
+    outs += [('info', np.int32, (G, N_SPLITS, P, 4)), ('pred', np.int32, (G, N_SPLITS, Mv)), ('confusion', np.int32, (G, N_SPLITS, K, K)),
+             ('unusable', np.int32, (G,))]
+    offs, total = {}, 0
+    for name, dt, shape in outs:
+        offs[name] = total
+        total += int(np.prod(shape)) * np.dtype(dt).itemsize
+    buf = torch.zeros(total + 8, dtype=torch.uint8, device=dev)
+    at = lambda name: ctypes.c_void_p(buf.data_ptr() + offs[name]) if name in offs else None
+    base = blob.data_ptr()
+    L.call('hv_svm_grade_grid', ctypes.c_void_p(base), ctypes.c_void_p(base + x_tt.nbytes), ctypes.c_void_p(base + x_tt.nbytes + x_val.nbytes), G, M,
+           Mv, F, K, max_rows.value, ctypes.c_double(tol), int(max_iter), at('w'), at('b'), at('gap'), at('info'), at('pred'), at('confusion'),
+           at('scores'), at('mean'), at('var'), at('unusable'), at('decision'), _lib.stream())
+    host = buf.cpu().numpy()
+    res = {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(grid + shape[1:]).copy()
+           for name, dt, shape in outs}
+    info = res.pop('info')
+    res['iterations'], res['status'], res['support'] = info[..., 0].copy(), info[..., 1].copy(), info[..., 2].copy()
+    res['unusable'] = res['unusable'] != 0
+    res['pred'] = np.where(res['pred'] >= 0, classes[np.clip(res['pred'], 0, K - 1)], -1)
+    res.update(classes=classes, folds=folds, rows_tt=rows_tt, rows_val=rows_val)
+    return res
+
+
+def best_setting(sweep, grades, score='f1'):
+    """The (length_divisor, height_threshold) of rhlv_sweep's grid whose grading (svm_grade_grid of svm_feature_grid(sweep)) has the highest mean
+    `score` over the folds, among the usable grid points whose every problem converged; ties go to the first in grid order."""
+    k = SCORES.index(score)
+    mean, status = np.asarray(grades['mean'])[..., k], np.asarray(grades['status'])
+    divs, thrs = np.asarray(sweep['length_divisors']), np.asarray(sweep['height_thresholds'])
+    if mean.shape != (len(divs), len(thrs)):
+        raise ValueError('best_setting: grades of the sweep\'s [D, T] grid expected')
+    ok = ~np.asarray(grades['unusable'], dtype=bool) & np.all((status == CONVERGED) | (status == PAIR_ABSENT), axis=(-2, -1)) & ~np.isnan(mean)
+    if not ok.any():
+        raise ValueError('best_setting: no usable grid point whose problems all converged')
+    d, t = np.unravel_index(int(np.argmax(np.where(ok, mean, -np.inf))), mean.shape)
+    return int(divs[d]), float(thrs[t])
 
 
 # ---------------------------------------------------------------- per-column height-loss maps and profiles (hv_rhlv_maps)

@@ -759,6 +759,44 @@ int hv_gen_eval(const void* ori_ct, const void* fake_ct, int ct_dtype, long long
                 const void* fake_seg, int label_dtype, long long ls0, long long ls1, long long ls2, int H, int W, int Z, int view, double label,
                 double* out, double* slices, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- SVM grading of the RHLV features at every point of a parameter grid (reference evaluation/SVM_grading.py:21-52,63-71 and
+ * evaluation/SVM_grading_2.5d.py:33-59: StandardScaler fitted on the train + test rows, SVC(kernel='linear', class_weight='balanced'),
+ * StratifiedKFold(5), each fold's model applied to the val rows, confusion matrix / macro F1 / precision / recall / accuracy per fold, their
+ * mean and np.var over the folds).  Float64 throughout, every reduction in a fixed order: a grid point's results
+ * are the same bits whether it is graded alone or inside a larger grid.  No workspace (the scaler is fused into the kernels' staging).
+ * hv_svm_grade_plan: HOST arithmetic only, nothing is launched.  y_tt [M] / y_val [Mv]: the grades of the train + test / val rows, classes [K]:
+ *   the sorted (strictly increasing, non-negative) list of all grades, fold [M]: the test fold (0..4) of every train + test row (the unshuffled
+ *   StratifiedKFold assignment; it depends on the labels only).  Writes into `plan` (host memory, hv_svm_grade_plan_bytes(M, Mv) bytes) what
+ *   the kernels read: per fold and class the bound on alpha n_train / (n_classes_in_train * count(class)) (class_weight='balanced', C = 1) and
+ *   whether the class occurs in the fold's training rows, the class index of every row, the fold ids; *max_rows = the largest number of
+ *   training rows of one class pair in one fold.  The caller uploads the plan as it is.  HV_ERR_ARG: null pointer, non-positive size, a
+ *   fold id outside 0..4, classes not sorted, a grade that is not in classes; HV_ERR_UNSUPPORTED: K < 2, K > HV_SVM_MAX_CLASSES, *max_rows >
+ *   HV_SVM_MAX_ROWS (the solver keeps a pair's rows in LDS: (F + 4) * 8 bytes per row, 1792 rows x 80 B = 140 KiB of the 160 KiB);
+ *   HV_ERR_WORKSPACE: plan_bytes too small.
+ * hv_svm_grade_grid: X_tt [G][M][F], X_val [G][Mv][F] (device, F = 3 or 6), plan (device copy of the plan), max_rows as the plan call gave it.
+ *   One wave per (class pair, fold, grid point) solves libsvm's C-SVC dual of that pair's training rows (the +1 side is the lower class) by
+ *   SMO -- maximal violating pair with the second-order choice of the second row, ties to the lowest row -- until the KKT gap m(alpha) -
+ *   M(alpha) <= tol or max_iter iterations; one wave per (fold, grid point) then votes in libsvm's way (a decision w.x - b > 0 votes for the
+ *   pair's lower class, ties among the vote counts go to the lowest class, classes absent from the fold's training rows are never predicted)
+ *   and scores by scikit-learn's rule (macro averages over the classes that occur in y_val or in the predictions; an empty denominator
+ *   contributes 0).  With P = K (K - 1) / 2 pairs in the order (0,1), (0,2), ..., (K-2,K-1) of class indices:
+ *   w [G][5][P][F], b [G][5][P] (libsvm's rho: decision = w.x - b), gap [G][5][P] (the final KKT gap), info [G][5][P][4] = { iterations, status,
+ *   support vectors, rows }, pred [G][5][Mv] (class index; -1 for an unusable grid point), confusion [G][5][K][K] (true class x predicted class),
+ *   scores [G][5][4] = { F1, precision, recall, accuracy }, mean / var [G][4] over the folds (ddof 0), unusable [G] (1: a feature of that grid
+ *   point is not finite -- nothing is solved, scores / mean / var are NaN, the other grid points are not affected), decision (NULL or
+ *   [G][5][Mv][P]; NaN for a pair that was not solved).  A problem that hit max_iter is voted with what it has; its status says so.
+ *   HV_ERR_ARG: null pointer (decision excepted), non-positive size, max_iter < 1, tol <= 0; HV_ERR_UNSUPPORTED: F not 3 or 6, K < 2 or >
+ *   HV_SVM_MAX_CLASSES, max_rows > HV_SVM_MAX_ROWS, G > 65535.  In both cases nothing is launched and nothing is written. */
+enum { HV_SVM_FOLDS = 5, HV_SVM_MAX_CLASSES = 4, HV_SVM_MAX_ROWS = 1792 };
+enum { HV_SVM_CONVERGED = 0, HV_SVM_MAX_ITER = 1, HV_SVM_ABSENT = 2 /* a class of the pair is missing from the fold's training rows */,
+       HV_SVM_UNUSABLE = 3 /* non-finite feature at that grid point */, HV_SVM_BAD_PLAN = 4 /* the plan does not belong to these sizes */ };
+size_t hv_svm_grade_plan_bytes(int M, int Mv);
+int hv_svm_grade_plan(const int* y_tt, const int* fold, int M, const int* y_val, int Mv, const int* classes, int K, void* plan,
+                      size_t plan_bytes, int* max_rows);
+int hv_svm_grade_grid(const double* X_tt, const double* X_val, const void* plan, int G, int M, int Mv, int F, int K, int max_rows, double tol,
+                      int max_iter, double* w, double* b, double* gap, int* info, int* pred, int* confusion, double* scores, double* mean,
+                      double* var, int* unusable, double* decision, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
