@@ -14,6 +14,10 @@ requested vertebra (csrc/straighten.hip).
   depedicle(label_vol, out=None) -> uint8 volume            process_3d_array (straighten_mask_3d.py:189-219) on a crop or a batch of crops
   component_counts(label_vol) -> int32 [Z, 256]             4-connected components of every label value per slice
   single_component_range(label_vol, label, offset=10)       find_single_component_layers (:249-280) -> (z0, z1)
+  restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebra') -> (ct_out, label_out[, covered][, local])
+                                                            the way back: Interpolator.global_to_local (curve.py:104-150,223-239) for every
+                                                            voxel of a vertebra's patient-space box (restore_box) and a resample of the
+                                                            (synthesized) crop there (csrc/restore.hip)
 
 Volumes are [X, Y, Z] device tensors as nibabel hands them over (any strides; a Fortran-ordered array passes as it lies).  The CT may be
 int16, float32 or float64 and is windowed in double for every dtype.  Deviation: the reference reads CT files over 500 MB as float32
@@ -408,3 +412,171 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
     if return_plan:
         return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win)}
     return out
+
+
+# ------------------------------------------------------------------------------------------------ back to patient space
+RESTORE = {'crop': 0, 'vertebra': 1}          # HV_RESTORE_CROP / HV_RESTORE_VERTEBRA (include/hvgan.h)
+
+
+def restore_box(knots, basis, box, shape, plane=PLANE, pad=2):
+    """Patient-space integer box that holds every voxel a crop's filled part can reach: -> [x0, y0, z0, nx, ny, nz] (all zero when nothing
+    is filled).  box: the crop_box row of the vertebra.  With a curve, the filled part is the knots whose cumulative length lies in the
+    row's axis-0 range (one knot more at each end: global_to_local interpolates between neighbouring planes) times the in-plane rectangle
+    [lo1, lo1 + n1 - 1] x [lo2, lo2 + n2 - 1]; the box is the min / max over those knots of the rectangle's four corners
+    knots[n] + basis[n][:, 1] (b - plane[0] / 2) + basis[n][:, 2] (a - plane[1] / 2), widened by `pad` and clipped to the volume.  Without
+    one (knots None: the crop was cut from the raw volume) it is the row's source range itself."""
+    lo, n = [int(v) for v in box[0:3]], [int(v) for v in box[3:6]]
+    shape = [int(s) for s in shape]
+    if min(n) <= 0:
+        return [0] * 6
+    if knots is None:
+        a = [max(0, lo[i]) for i in range(3)]
+        b = [min(shape[i], lo[i] + n[i]) for i in range(3)]
+        return [0] * 6 if min(b[i] - a[i] for i in range(3)) <= 0 else a + [b[i] - a[i] for i in range(3)]
+    cum = cumulative_length(knots)
+    sel, = np.nonzero((cum >= lo[0] - 1) & (cum <= lo[0] + n[0]))
+    if len(sel) == 0:
+        return [0] * 6
+    k0, k1 = max(int(sel[0]) - 1, 0), min(int(sel[-1]) + 1, len(knots) - 1)
+    K, B = np.asarray(knots)[k0:k1 + 1], np.asarray(basis)[k0:k1 + 1]
+    a = np.array([lo[1], lo[1] + n[1] - 1], dtype=np.float64) - plane[1] / 2      # axis 1 of the straight volume runs along frame vector 2
+    b = np.array([lo[2], lo[2] + n[2] - 1], dtype=np.float64) - plane[0] / 2
+    corners = K[:, None, None, :] + B[:, None, None, :, 1] * b[None, None, :, None] + B[:, None, None, :, 2] * a[None, :, None, None]
+    corners = corners.reshape(-1, 3)
+    mn = np.floor(corners.min(0)).astype(np.int64) - pad
+    mx = np.ceil(corners.max(0)).astype(np.int64) + pad
+    mn = np.maximum(mn, 0)
+    mx = np.minimum(mx, np.array(shape) - 1)
+    if (mx < mn).any():
+        return [0] * 6
+    return [int(v) for v in mn] + [int(v) for v in mx - mn + 1]
+
+
+def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebra', return_covered=False, return_local=False, out=None,
+                    regions=None):
+    """The way back from the straightened crops to the patient's scan: Interpolator.global_to_local (curve.py:104-150,223-239) for every
+    voxel of each vertebra's patient-space box and a resample of the crop there, on the device (csrc/restore.hip), where the reference
+    offers the transform one point at a time in Python.
+    plan: what straighten_patient(..., return_plan=True) returned.  crops: {vert_id: (ct_vol, label_vol)} device tensors of the size the
+    crops were cut at -- float64 / float32 CT in the crops' windowed 0..255 units, uint8 label, any strides; applied in the dict's order.
+    ct / label: the patient volumes (the dtypes straighten_patient accepts): the CT output starts as the patient CT under the plan's window
+    rule, the label output as the patient label in uint8; without them both start as zeros of `shape`.  out: (ct_out float64, label_out uint8)
+    device tensors of the patient's shape (any strides) to start from and write into instead.  regions: {vert_id: [x0, y0, z0, nx, ny, nz]}
+    patient-space boxes to visit instead of restore_box's (a region of interest; voxels outside are not touched).
+    where = 'crop': every voxel the crop covers is written (trilinear CT sample, nearest label sample); 'vertebra' (needs `label`): only
+    where the label sample or the patient's own label is vert_id.  The crop's zero padding never reaches the patient.
+    -> (ct_out float64, label_out uint8[, covered uint8: 1 where written][, {vert_id: (box, local)}: the patient-space box
+    [x0, y0, z0, nx, ny, nz] and the local coordinate of each of its voxels, float64 [nx, ny, nz, 3], NaN where there is none])."""
+    if where not in RESTORE:
+        raise ValueError("restore: where must be 'crop' or 'vertebra', got %r" % (where,))
+    if where == 'vertebra' and label is None:
+        raise ValueError("restore: where='vertebra' needs the patient's label volume")
+    crops = dict(crops)
+    if not crops:
+        raise ValueError('restore: no crop')
+    for t in (ct, label) + tuple(out or ()):
+        if t is not None:
+            if t.dim() != 3:
+                raise ValueError('restore: patient volumes are [X, Y, Z], got %s' % (tuple(t.shape),))
+            if shape is not None and tuple(t.shape) != tuple(int(s) for s in shape):
+                raise ValueError('restore: volume of shape %s where shape=%s was given' % (tuple(t.shape), tuple(shape)))
+            shape = tuple(t.shape)
+    if shape is None or len(shape) != 3 or min(shape) <= 0:
+        raise ValueError('restore: the patient shape is needed (shape=, ct=, label= or out=)')
+    shape = tuple(int(s) for s in shape)
+    knots, basis = plan['knots'], plan['basis']
+    src_shape = shape if knots is None else (len(knots), PLANE[1], PLANE[0])
+    # plan['boxes'] has one row per requested id in request order, plan['local'] one entry per distinct id in first-request order: a
+    # repeated id repeats its row, so the distinct rows in order are the vertebrae's own
+    rows = []
+    for b in plan['boxes']:
+        b = [int(v) for v in b]
+        if len(plan['boxes']) == len(plan['local']) or b not in rows:
+            rows.append(b)
+    if len(rows) != len(plan['local']):
+        raise ValueError('restore: the plan holds %d box rows for %d vertebrae' % (len(rows), len(plan['local'])))
+    own_box = dict(zip(plan['local'], rows))
+    jobs = []      # every ValueError comes before the first launch (and before the device is asked for)
+    for vid, pair in crops.items():
+        if vid not in plan['local']:
+            raise ValueError('restore: vertebra %r is not in the plan' % (vid,))
+        if float(vid) != int(vid) or not 0 <= int(vid) <= 255:
+            raise ValueError('restore: vertebra id %r is not an integer in [0, 255]' % (vid,))
+        cvol, lvol = pair
+        if cvol.dim() != 3 or tuple(cvol.shape) != tuple(lvol.shape) or min(cvol.shape) <= 0:
+            raise ValueError('restore: vertebra %r: CT and label crop must be two volumes of one size, got %s and %s'
+                             % (vid, tuple(cvol.shape), tuple(lvol.shape)))
+        _dtype_code(cvol, (torch.float32, torch.float64), 'crop CT')
+        _dtype_code(lvol, (torch.uint8,), 'crop label')
+        try:
+            box = crop_box(plan['local'][vid], src_shape, tuple(cvol.shape))
+        except ValueError:
+            box = None
+        if box != own_box[vid]:        # the row the vertebra's crop was cut with: another size gives another row
+            raise ValueError('restore: vertebra %r: a crop of size %s is not what the plan cut' % (vid, tuple(cvol.shape)))
+        region = restore_box(knots, basis, box, shape)
+        if regions is not None and vid in regions:
+            region = [int(v) for v in regions[vid]]
+            if len(region) != 6 or any(region[i] < 0 or region[3 + i] < 0 or region[i] + region[3 + i] > shape[i] for i in range(3)):
+                raise ValueError('restore: vertebra %r: region %s leaves the volume %s' % (vid, region, shape))
+        jobs.append((int(vid), cvol, lvol, box, region))
+    dev = jobs[0][1].device
+    for _, cvol, lvol, _, _ in jobs:
+        _lib.require_gpu(cvol, lvol)
+        if cvol.device != dev or lvol.device != dev:
+            raise ValueError('restore: crops on different devices')
+    _lib.require_gpu(ct, label, *(out or ()))
+    if label is not None:
+        _dtype_code(label, tuple(_DT), 'label')
+        if label.device != dev:
+            raise ValueError('restore: label on another device than the crops')
+    if ct is not None:
+        _dtype_code(ct, _CT_DT, 'CT')
+        if ct.device != dev:
+            raise ValueError('restore: CT on another device than the crops')
+    if out is not None:
+        ct_out, lab_out = out
+        if ct_out.dtype != torch.float64 or lab_out.dtype != torch.uint8 or ct_out.device != dev or lab_out.device != dev:
+            raise ValueError('restore: out must be (float64, uint8) tensors on the device of the crops')
+    else:
+        if ct is None:
+            ct_out = torch.zeros(shape, dtype=torch.float64, device=dev)
+        else:       # window(ct_data, -300, 800) (straighten_mask_3d.py:172-184), as the crops were: not hot, plain torch in double
+            ct_out = ct.to(torch.float64).contiguous()
+            if ct_out.data_ptr() == ct.data_ptr():
+                ct_out = ct_out.clone()
+            if plan['window']:
+                ct_out = (255.0 * (ct_out - WINDOW[0]) / (WINDOW[1] - WINDOW[0])).clamp_(0.0, 255.0)
+        lab_out = torch.zeros(shape, dtype=torch.uint8, device=dev) if label is None else label.to(torch.uint8).contiguous()
+        if label is not None and lab_out.data_ptr() == label.data_ptr():
+            lab_out = lab_out.clone()
+    covered = torch.zeros(shape, dtype=torch.uint8, device=dev) if return_covered else None
+    L = _lib.get()
+    zero3 = [ctypes.c_longlong(0)] * 3
+    N = 0
+    d_knots = d_basis = d_cum = None
+    if knots is not None:
+        N = len(knots)
+        d_knots = torch.from_numpy(np.ascontiguousarray(knots, dtype=np.float64)).to(dev)
+        d_basis = torch.from_numpy(np.ascontiguousarray(basis, dtype=np.float64)).to(dev)
+        d_cum = torch.from_numpy(np.ascontiguousarray(cumulative_length(knots), dtype=np.float64)).to(dev)
+    local = {}
+    for vid, cvol, lvol, box, region in jobs:
+        loc = None
+        if return_local:
+            loc = torch.empty(region[3], region[4], region[5], 3, dtype=torch.float64, device=dev)
+            local[vid] = (region, loc)
+        if min(region[3:]) <= 0:
+            continue
+        L.call('hv_restore_volume', _lib.ptr(cvol), _DT[cvol.dtype], *_strides(cvol), _lib.ptr(lvol), *_strides(lvol), *cvol.shape,
+               (ctypes.c_int * 9)(*box), _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), N, ctypes.c_double(PLANE[0] / 2),
+               ctypes.c_double(PLANE[1] / 2), _lib.ptr(label), 0 if label is None else _DT[label.dtype],
+               *(zero3 if label is None else _strides(label)), *shape, (ctypes.c_int * 6)(*region), RESTORE[where], vid, _lib.ptr(ct_out),
+               *_strides(ct_out), _lib.ptr(lab_out), *_strides(lab_out), _lib.ptr(covered), *(zero3 if covered is None else _strides(covered)),
+               _lib.ptr(loc), _lib.stream())
+    res = (ct_out, lab_out)
+    if return_covered:
+        res += (covered,)
+    if return_local:
+        res += (local,)
+    return res

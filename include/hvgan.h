@@ -739,6 +739,38 @@ int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs
 int hv_depedicle(const void* label, int label_dtype, long long ls0, long long ls1, long long ls2, long long lsv, int A0, int A1, int Z, int V,
                  uint8_t* out, long long os0, long long os1, long long os2, long long osv, int* counts, int* status, void* stream);
 
+/* ---- restore of a straightened (synthesized) vertebra crop to patient CT space (reference straighten/straighten/curve.py:104-150,223-239
+ * Interpolator.global_to_local / _to_local / _transform / interpolate_coords, which the reference runs one point at a time; DESIGN.md section
+ * 8 row f8).  One lane per voxel p = (x, y, z) of the patient-space box region = {x0, y0, z0, nx, ny, nz} (HOST pointer, inside [D0][D1][D2]):
+ *   local = global_to_local(p): per knot n d = p - knots[n], to_origin = |d|, q = basis[n]^T d, to_plane = q[0], coords = q + (cumlen[n],
+ *   centre1, centre2); idx = the first minimum of to_origin, replaced by the n with sign(to_plane[n+1]) != sign(to_plane[n]) (sign(0) = 0)
+ *   nearest to it (the lowest on ties) if there is one; coords interpolated linearly to to_plane = 0 over the planes [max(0, idx - 2),
+ *   min(N, idx + 2)) (stable sort by to_plane, searchsorted left, segment clipped to [1, len - 1], slope * (0 - x_lo) + y_lo).
+ *   knots [N][3], basis [N][3][3] row-major, cumlen [N] = cumulative_length(knots) (device, fp64), N >= 2; they are staged in LDS up to 630
+ *   knots and read from global memory beyond.
+ *   Crop coordinate: the straight volume is indexed (n, a, b) = (local[0], local[2], local[1]) (interpolate_along's meshgrid puts frame vector
+ *   2 on axis 1); c = that - lo + start with box = {lo0, lo1, lo2, len0, len1, len2, start0, start1, start2} (HOST pointer, the row
+ *   hv_straighten_crop took for the vertebra).  p is covered iff start_i <= c_i <= start_i + len_i - 1 on all three axes and local is
+ *   finite: the crop's zero padding is never read.  CT sample: trilinear (map_coordinates order 1) on crop_ct ([O0][O1][O2], HV_DT_F32 or
+ *   HV_DT_F64, strides in elements); label sample: crop_label (uint8) at floor(c + 0.5) (order 0).
+ *   knots == NULL (the single-centroid branch: the crop was cut from the raw volume): c = p - lo + start in integers, covered iff
+ *   0 <= p - lo < len.
+ * where = HV_RESTORE_CROP: every covered voxel is written; HV_RESTORE_VERTEBRA: a covered voxel is written only if the label sample equals
+ *   vert_id or patient_label (any HV_DT_* code, strides in elements; may be NULL for HV_RESTORE_CROP) holds vert_id at p.
+ * A written voxel gets the CT sample into ct_out (fp64), the label sample into label_out (uint8) and 1 into covered (uint8, may be NULL), all
+ *   [D0][D1][D2] with their own strides; every other voxel is left as it is.  local_out: NULL or [nx][ny][nz][3] fp64, the local coordinate of
+ *   every box voxel (NaN where it is not finite; p itself with knots == NULL).  One call per vertebra; calls on one stream apply in order.
+ * HV_ERR_ARG: null pointer, non-positive size, crop dtype not F32 / F64, unknown `where`, vert_id outside 0..255, N < 2, a box that leaves the
+ *   crop, a region that leaves the patient volume: nothing is launched and nothing is written.  An empty region or box is HV_OK. */
+enum { HV_RESTORE_CROP = 0, HV_RESTORE_VERTEBRA = 1 };
+int hv_restore_volume(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
+                      long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+                      const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
+                      int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region, int where,
+                      int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out, long long qs0,
+                      long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2, double* local_out,
+                      void* stream);
+
 /* ---- generation-quality evaluation of a synthesized volume (reference evaluation/generation_eval_sagittal.py:11-37 calculate_iou /
  * calculate_dice / relative_volume_difference, :39-103 process_images; generation_eval_coronal.py the same with the slice axis 1; SURVEY.md
  * row 17).  Four [H][W][Z] volumes: element (h, w, z) of the CTs at base[h*cs0 + w*cs1 + z*cs2], of the labels
