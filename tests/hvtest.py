@@ -97,3 +97,28 @@ class Guarded:
 
     def cpu(self):
         return self.t.cpu()
+
+
+class ExactWs:
+    """ops._ws replaced (through pytest's monkeypatch) by one that hands out EXACTLY the queried bytes, each time a fresh 16-byte aligned view into its own
+    0xA5-filled buffer -- so the two alternating buffers of an ops.FoldChain are covered as well.  close() puts ops._ws back and checks that nothing was
+    written outside any of the queried ranges; required: at least one workspace must have been asked for."""
+
+    def __init__(self, monkeypatch, required=False):
+        self.all, self.mp, self.required = [], monkeypatch, required
+        monkeypatch.setattr(ops, '_ws', self.ws)
+
+    def ws(self, nbytes, device, slot=0):
+        import ctypes
+        n = int(nbytes)
+        big = torch.full((512 + n,), 0xA5, dtype=torch.uint8, device=device)
+        self.all.append((big, n))
+        assert big[256:].data_ptr() % 16 == 0
+        return big[256:256 + n], ctypes.c_size_t(n)
+
+    def close(self):
+        self.mp.undo()
+        torch.cuda.synchronize()
+        assert self.all or not self.required, 'no workspace was asked for'
+        for big, n in self.all:
+            assert bool((big[:256] == 0xA5).all()) and bool((big[256 + n:] == 0xA5).all()), 'wrote outside the queried workspace'
