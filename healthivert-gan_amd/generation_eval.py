@@ -5,6 +5,9 @@ Same entry points as the reference modules, on device tensors (csrc/gen_eval.hip
   calculate_iou / calculate_dice / relative_volume_difference(ori_seg, fake_seg)         binary (0 / 1) volumes (:11-37)
   process_images(ori_ct, fake_ct, ori_seg, fake_seg, label, view)                        (:39-103) -> the seven values
   evaluate_generation(items, view)                                                       the skip and average rule of main() (:140-158)
+  process_images_batch(originals, fakes, view) / evaluate_experiments(originals, experiments, view)    main()'s two loops (:124-162), every
+      validation vertebra x every experiment against the same original, through hv_gen_eval_batch: one launch sequence and one readback,
+      what depends on the original alone computed once per item, every pair's values the bits process_images gives for it
 Volumes are [H, W, Z] with any strides: CT float32 / float64, labels uint8 / float32 / float64 (other dtypes are converted), device tensors
 or numpy arrays (uploaded), e.g. the float64 arrays infer.process_volume returns.  `label` is the vertebra id the reference parses from the
 file name.  File I/O, the vertebra_data.json selection and the .txt report stay on the host.
@@ -124,6 +127,26 @@ def process_images(ori_ct, fake_ct, ori_seg, fake_seg, label, view='sagittal', r
     return res, sl
 
 
+def average_outputs(all_o, what='evaluate_generation (volume %d)'):
+    """main()'s skip and average rule (:140-158) on an [n][16] array of hv_gen_eval outputs, host arithmetic only: a volume whose patch PSNR
+    or SSIM is NaN or 0 is skipped; each key is np.mean over the kept volumes (NaN if none).  Raises ValueError for a volume whose error
+    flags are set, named by `what % index`.  -> dict of the seven averages plus 'count' and 'per_volume'."""
+    lists = {k: [] for k in KEYS}
+    for i, o in enumerate(all_o):
+        _check(o, what % i)
+        pp, ps = float(o[2]), float(o[3])
+        if math.isnan(pp) or math.isnan(ps) or pp == 0 or ps == 0:
+            continue
+        for q, k in enumerate(KEYS):
+            lists[k].append(float(o[q]))
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)     # np.mean([]) -> nan, as main() gets when every volume was skipped
+        res = {k: float(np.mean(v)) for k, v in lists.items()}
+    res['count'] = len(lists['iou'])
+    res['per_volume'] = [tuple(float(v) for v in o[:7]) for o in all_o]
+    return res
+
+
 def evaluate_generation(items, view='sagittal'):
     """main()'s per-experiment body over an iterable of (ori_ct, fake_ct, ori_seg, fake_seg, label): every volume is queued on the device,
     then one readback.  A volume whose patch PSNR or SSIM is NaN or 0 is skipped; each key is np.mean over the kept volumes (NaN if none).
@@ -136,17 +159,189 @@ def evaluate_generation(items, view='sagittal'):
         _launch(ori_ct, fake_ct, ori_seg, fake_seg, label, view, out)
         outs.append(out)
     all_o = torch.stack([o.to(outs[0].device) for o in outs]).cpu().numpy() if outs else np.zeros((0, 16))
-    lists = {k: [] for k in KEYS}
-    for i, o in enumerate(all_o):
-        _check(o, 'evaluate_generation (volume %d)' % i)
-        pp, ps = float(o[2]), float(o[3])
-        if math.isnan(pp) or math.isnan(ps) or pp == 0 or ps == 0:
-            continue
-        for q, k in enumerate(KEYS):
-            lists[k].append(float(o[q]))
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore', RuntimeWarning)     # np.mean([]) -> nan, as main() gets when every volume was skipped
-        res = {k: float(np.mean(v)) for k, v in lists.items()}
-    res['count'] = len(lists['iou'])
-    res['per_volume'] = [tuple(float(v) for v in o[:7]) for o in all_o]
-    return res
+    return average_outputs(all_o)
+
+
+# ------------------------------------------------------------------------------------------------ a whole set, several experiments
+WORKSPACE_BOUND = 1 << 30      # process_images_batch: the default `chunk` keeps one call's workspace below this
+
+
+def _meta(v, allowed, fallback):
+    """(shape, dtype, strides) a volume has once _prep has run on it, without touching a device."""
+    t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+    dt = t.dtype if t.dtype in allowed else fallback
+    return tuple(t.shape), dt, tuple(t.stride())
+
+
+_LABEL_DT = (torch.uint8, torch.float32, torch.float64)
+_CT_DT = (torch.float32, torch.float64)
+
+
+def _item_signature(original, fakes_i, counts_only=False):
+    """What one hv_gen_eval_batch call must share among its volumes, for one item: (shape, CT dtype, CT strides, label dtype, label strides).
+    A dtype that differs inside the item becomes float64, strides that differ become the contiguous ones: what _pair does to a pair."""
+    def common(vols, allowed):
+        metas = [_meta(v, allowed, torch.float64) for v in vols]
+        shapes = {m[0] for m in metas}
+        if len(shapes) != 1 or len(metas[0][0]) != 3:
+            raise ValueError('generation_eval: [H, W, Z] volumes of equal shape expected, got %s' % sorted(shapes))
+        dts = {m[1] for m in metas}
+        dt = metas[0][1] if len(dts) == 1 else torch.float64
+        sts = {m[2] for m in metas}
+        st = metas[0][2] if len(sts) == 1 and len(dts) == 1 else None       # None: made contiguous
+        return metas[0][0], dt, st
+    shape, ldt, lst = common([original[1]] + [f[1] for f in fakes_i], _LABEL_DT)
+    if counts_only:
+        return shape, None, None, ldt, lst
+    cshape, cdt, cst = common([original[0]] + [f[0] for f in fakes_i], _CT_DT)
+    if cshape != shape:
+        raise ValueError('generation_eval: CT %s and label %s volumes differ in shape' % (cshape, shape))
+    return shape, cdt, cst, ldt, lst
+
+
+def group_items(originals, fakes, counts_only=False):
+    """Host-side grouping for process_images_batch: -> (E, [(signature, [item indices])]) in order of first appearance.  Raises ValueError
+    on a ragged `fakes` (before any device work) and on volumes of unequal shape, naming the item."""
+    if len(fakes) != len(originals):
+        raise ValueError('process_images_batch: %d originals but %d rows of fakes' % (len(originals), len(fakes)))
+    E = len(fakes[0]) if len(fakes) else 0
+    for i, row in enumerate(fakes):
+        if len(row) != E:
+            raise ValueError('process_images_batch: ragged fakes, item %d has %d experiments, item 0 has %d' % (i, len(row), E))
+    if len(fakes) and E == 0:
+        raise ValueError('process_images_batch: no experiment')
+    groups = {}
+    for i, (o, row) in enumerate(zip(originals, fakes)):
+        try:
+            sig = _item_signature(o, row, counts_only)
+        except ValueError as e:
+            raise ValueError('%s (item %d)' % (e, i)) from None
+        groups.setdefault(sig, []).append(i)
+    return E, list(groups.items())
+
+
+def _conform(v, device, dtype, strides, allowed):
+    t = _prep(v, device, allowed, torch.float64)
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    if strides is None or tuple(t.stride()) != strides:
+        t = t.contiguous()
+    _lib.require_gpu(t)
+    return t
+
+
+def _launch_batch(sig, originals, fakes, idx, E, view, out, slices, device):
+    """Queue one hv_gen_eval_batch for the items `idx` (all of signature `sig`); `out` [n][E][16] and `slices` are device tensors."""
+    L = _lib.get()
+    shape, cdt, cst, ldt, lst = sig
+    n = len(idx)
+    tab = np.zeros(2 * n + 2 * n * E + n, dtype=np.float64)     # pointer tables (as int64) and the labels: one upload
+    ptrs = tab.view(np.int64)
+    o_ct, f_ct, o_lab, f_lab, lab = 0, n, n + n * E, 2 * n + n * E, 2 * n + 2 * n * E
+    labs, cts = [], []                                           # (table slot, tensor)
+    for a, i in enumerate(idx):
+        oc, ol, label = originals[i]
+        tab[lab + a] = float(label)
+        labs.append((o_lab + a, _conform(ol, device, ldt, lst, _LABEL_DT)))
+        labs += [(f_lab + a * E + e, _conform(fakes[i][e][1], device, ldt, lst, _LABEL_DT)) for e in range(E)]
+        if cdt is not None:
+            cts.append((o_ct + a, _conform(oc, device, cdt, cst, _CT_DT)))
+            cts += [(f_ct + a * E + e, _conform(fakes[i][e][0], device, cdt, cst, _CT_DT)) for e in range(E)]
+    for vols in (labs, cts):                                     # one stride triple per kind, whatever the conversions left
+        if len({tuple(t.stride()) for _, t in vols}) > 1:
+            vols[:] = [(slot, t.contiguous()) for slot, t in vols]
+        for slot, t in vols:
+            ptrs[slot] = t.data_ptr()
+    keep = [t for _, t in labs + cts]
+    lstr = labs[0][1].stride()
+    cstr = cts[0][1].stride() if cdt is not None else (0, 0, 0)
+    dtab = torch.from_numpy(tab).to(device)
+    base = dtab.data_ptr()
+    at = lambda off: ctypes.c_void_p(base + 8 * off)
+    H, W, Z = shape
+    need = L.size('hv_gen_eval_batch_workspace_bytes', H, W, Z, VIEWS[view], n, E)
+    ws, wsz = ops._ws(need, device, slot=3)
+    L.call('hv_gen_eval_batch', at(o_ct) if cdt is not None else None, at(f_ct) if cdt is not None else None, _DT[cdt] if cdt is not None else 5,
+           *[ctypes.c_longlong(v) for v in cstr], at(o_lab), at(f_lab), _DT[ldt], *[ctypes.c_longlong(v) for v in lstr],
+           H, W, Z, VIEWS[view], at(lab), n, E, _lib.ptr(out), _lib.ptr(slices), _lib.ptr(ws), wsz, _lib.stream())
+    return keep + [dtab]       # alive until the caller has synchronised
+
+
+def _batch_outputs(originals, fakes, view, return_slices, chunk, counts_only=False):
+    """-> (out [N][E][16] numpy, records [N][E][S][9] numpy or None): every call queued, then one readback per group of volumes."""
+    if view not in VIEWS:
+        raise ValueError("view must be 'sagittal' or 'coronal', got %r" % (view,))
+    originals, fakes = list(originals), [list(row) for row in fakes]
+    E, groups = group_items(originals, fakes, counts_only)
+    N = len(originals)
+    out = np.zeros((N, E, 16))
+    rec = None
+    if not N:
+        return out, rec
+    L = _lib.get()
+    dev = _device(*[v for o in originals for v in o[:2]], *[v for row in fakes for f in row for v in f])
+    pending, keep = [], []
+    for sig, idx in groups:
+        H, W, Z = sig[0]
+        S = sig[0][VIEWS[view]]
+        per_item = L.size('hv_gen_eval_batch_workspace_bytes', H, W, Z, VIEWS[view], 1, E)
+        step = int(chunk) if chunk else max(1, min(WORKSPACE_BOUND // max(1, per_item), 65535 // E))
+        if step < 1:
+            raise ValueError('process_images_batch: chunk must be at least 1, got %r' % (chunk,))
+        for a in range(0, len(idx), step):
+            part = idx[a:a + step]
+            d_out = torch.zeros(len(part), E, 16, dtype=torch.float64, device=dev)
+            d_rec = torch.zeros(len(part), E, S, len(SLICE_FIELDS), dtype=torch.float64, device=dev) if return_slices else None
+            keep.append(_launch_batch(sig, originals, fakes, part, E, view, d_out, d_rec, dev))
+            pending.append((part, d_out, d_rec))
+    if return_slices:
+        rec = [[None] * E for _ in range(N)]
+    for part, d_out, d_rec in pending:
+        out[part] = d_out.cpu().numpy()
+        if d_rec is not None:
+            r = d_rec.cpu().numpy()
+            for a, i in enumerate(part):
+                for e in range(E):
+                    rec[i][e] = r[a, e]
+    return out, rec
+
+
+def _slice_dict(o, rec):
+    n = int(o[15])
+    rec = rec[:n]
+    rec = rec[rec[:, 0] >= 0]                      # the slices of the 4/5 range that were evaluated
+    return {k: rec[:, i].astype(np.int64) if k in ('z', 'x1', 'x2') else rec[:, i].copy() for i, k in enumerate(SLICE_FIELDS)}
+
+
+def process_images_batch(originals, fakes, view='sagittal', return_slices=False, chunk=None):
+    """process_images for a whole set and several experiments (main() :124-162) in one launch sequence per group of equal volumes.
+    originals: sequence of (ori_ct, ori_seg, label); fakes[i][e] = (fake_ct, fake_seg) of item i in experiment e (every item has the same
+    number of experiments).  -> [N][E][7] numpy array, each row the bits process_images gives for that pair; with return_slices also
+    [N][E] dicts of per-evaluated-slice arrays (SLICE_FIELDS).  Device tensors or numpy arrays.  Items whose shape, dtypes or strides differ
+    go into further calls (within an item, differing dtypes become float64 and differing strides contiguous, as for a pair); `chunk`
+    bounds the items per call (default: a workspace of at most WORKSPACE_BOUND bytes).  Raises ValueError where process_images raises,
+    naming the item and experiment, and before the first launch on a ragged `fakes`."""
+    out, rec = _batch_outputs(originals, fakes, view, return_slices, chunk)
+    for i in range(out.shape[0]):
+        for e in range(out.shape[1]):
+            _check(out[i, e], 'process_images_batch (item %d, experiment %d)' % (i, e))
+    res = out[:, :, :7].copy()
+    if not return_slices:
+        return res
+    return res, [[_slice_dict(out[i, e], rec[i][e]) for e in range(out.shape[1])] for i in range(out.shape[0])]
+
+
+def evaluate_experiments(originals, experiments, view='sagittal'):
+    """main() over every experiment folder: originals as for process_images_batch, experiments {name: [(fake_ct, fake_seg) per item]}.
+    -> {name: the dict evaluate_generation returns for that experiment}; averaging on the host (np.mean, the reference's own summation)."""
+    originals = list(originals)
+    names = list(experiments)
+    rows = {k: list(experiments[k]) for k in names}
+    for k in names:
+        if len(rows[k]) != len(originals):
+            raise ValueError('evaluate_experiments: experiment %r has %d volumes for %d originals' % (k, len(rows[k]), len(originals)))
+    if not names:
+        return {}
+    fakes = [[rows[k][i] for k in names] for i in range(len(originals))]
+    out, _ = _batch_outputs(originals, fakes, view, False, None)
+    return {k: average_outputs(out[:, e], 'evaluate_experiments (experiment %r, volume %%d)' % (k,)) for e, k in enumerate(names)}

@@ -80,7 +80,7 @@ def parse_header(path=HEADER):
         if args and args != 'void':
             for a in args.split(','):
                 a = a.strip()
-                m = re.match(r'((?:const\s+)?(?:long long|size_t|\w+)\s*\**)\s*\w*$', a)
+                m = re.match(r'((?:const\s+)?(?:long long|size_t|\w+)\s*(?:\*\s*(?:const\b\s*)?)*)\s*\w*$', a)   # T, T*, T* const*
                 argtypes.append(_ctype(m.group(1), structs))
         protos[name] = (_ctype(ret, structs), argtypes)
     return structs, protos

@@ -790,6 +790,22 @@ size_t hv_gen_eval_workspace_bytes(int H, int W, int Z, int view);
 int hv_gen_eval(const void* ori_ct, const void* fake_ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* ori_seg,
                 const void* fake_seg, int label_dtype, long long ls0, long long ls1, long long ls2, int H, int W, int Z, int view, double label,
                 double* out, double* slices, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a set, as the reference's main() (:124-162) scores it: N originals, each against E synthesized volumes (one per experiment
+ * folder), in one launch sequence whose length does not depend on N or E.  ori_ct / ori_seg: DEVICE tables of N device pointers; fake_ct /
+ * fake_seg: device tables of N * E device pointers, item i's experiment e at [i * E + e]; labels: device array of N vertebra ids.  Every
+ * volume of a call has the shape, the two dtypes and the two stride triples of the call (rules as above); ori_ct = fake_ct = NULL: the
+ * counts only.  out [N][E][16] and slices (NULL or [N][E][S][9], S the extent of the view axis) in hv_gen_eval's field layout, each pair's
+ * values the SAME BITS hv_gen_eval gives for that pair alone: the kernels share its device functions and its summation orders, whatever N,
+ * E and the order of items and experiments are.  What depends on the original alone (its counts, z0 / z1, the selection, x1 / x2, both data
+ * ranges, the SSIM window sums of x and x^2) is computed once per item.  A pair's [7] / [8] flags concern that pair's item only.
+ * HV_ERR_ARG: hv_gen_eval's conditions, N < 1, E < 1, labels NULL, a workspace that is NULL, not 16-byte aligned or smaller than
+ * hv_gen_eval_batch_workspace_bytes(H, W, Z, view, N, E); HV_ERR_UNSUPPORTED: N * E > 65535.  Nothing is launched on an error.  No host
+ * synchronisation. */
+size_t hv_gen_eval_batch_workspace_bytes(int H, int W, int Z, int view, int N, int E);
+int hv_gen_eval_batch(const void* const* ori_ct, const void* const* fake_ct, int ct_dtype, long long cs0, long long cs1, long long cs2,
+                      const void* const* ori_seg, const void* const* fake_seg, int label_dtype, long long ls0, long long ls1, long long ls2,
+                      int H, int W, int Z, int view, const double* labels, int N, int E, double* out, double* slices, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* ---- SVM grading of the RHLV features at every point of a parameter grid (reference evaluation/SVM_grading.py:21-52,63-71 and
  * evaluation/SVM_grading_2.5d.py:33-59: StandardScaler fitted on the train + test rows, SVC(kernel='linear', class_weight='balanced'),
