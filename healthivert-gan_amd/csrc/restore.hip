@@ -8,6 +8,9 @@
 //                           coordinate in the crop, the coverage test, a trilinear sample of the crop's CT (map_coordinates order 1), a
 //                           nearest sample of its label (order 0), and the write rule.  Knots, frames and cumulative lengths sit in LDS
 //                           (13 doubles per knot); LDS = false reads them from global memory when they do not fit.
+//                           With anisotropic voxels (hv_restore_volume_sp) p enters the scans as p * spacing; the rest is unchanged.
+//   curve_points_kernel<LDS> one lane per point of a list: global_to_local or local_to_global (curve.py:110-114,131-138) through the same
+//                           device function (rs_curve_map) as the restore, no crop involved.
 //   restore_uncrop_kernel   the single-centroid branch (the crop was cut from the raw volume): the plain un-crop of the box.
 // Everything in doubles in the reference's operation order (-ffp-contract=off); element offsets are 64-bit.
 #include <cmath>
@@ -17,7 +20,7 @@
 #define RS_KNOT_DOUBLES 13                                    // knot 3, frame 9, cumulative length 1
 #define RS_LDS_BYTES 65536                                    // what a launch gets without asking for more: 630 knots
 
-struct RsCurve { const double* knots; const double* basis; const double* cumlen; int N; double c1, c2; };
+struct RsCurve { const double* knots; const double* basis; const double* cumlen; int N; double c1, c2, sp0, sp1, sp2; };
 struct RsArgs {
     const void* crop_ct; int crop_dt; long long cs0, cs1, cs2;
     const uint8_t* crop_lab; long long ls0, ls1, ls2;
@@ -62,41 +65,63 @@ __device__ __forceinline__ void rs_write(const RsArgs& A, long long px, long lon
 
 extern __shared__ double rs_lds[];
 
-template <bool LDS>
-__global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs A) {
+// knots, frames and cumulative lengths of the curve into LDS (all lanes of the block; ends in a barrier)
+__device__ __forceinline__ void rs_stage(const RsCurve& cv) {
     const int N = cv.N;
-    if (LDS) {
-        for (int i = threadIdx.x; i < 3 * N; i += RS_THREADS) rs_lds[i] = cv.knots[i];
-        for (int i = threadIdx.x; i < 9 * N; i += RS_THREADS) rs_lds[3 * N + i] = cv.basis[i];
-        for (int i = threadIdx.x; i < N; i += RS_THREADS) rs_lds[12 * N + i] = cv.cumlen[i];
-        __syncthreads();
-    }
+    for (int i = threadIdx.x; i < 3 * N; i += RS_THREADS) rs_lds[i] = cv.knots[i];
+    for (int i = threadIdx.x; i < 9 * N; i += RS_THREADS) rs_lds[3 * N + i] = cv.basis[i];
+    for (int i = threadIdx.x; i < N; i += RS_THREADS) rs_lds[12 * N + i] = cv.cumlen[i];
+    __syncthreads();
+}
+
+// One point through Interpolator._to_local (TO_GLOBAL = false: P in millimetres -> local) or ._to_global (true: P local -> millimetres)
+// and interpolate_coords (curve.py:122-138,223-239).  Per knot n, with centre[n] = (cumlen[n], c1, c2):
+//   _to_local   d = P - knots[n],  to_origin = |d|,  q = basis[n]^T d ('nji,nj->ni'),  to_plane = q[0],  coords = q + centre[n]
+//   _to_global  d = P - centre[n], to_plane = d[0],  q = basis[n] d   ('nij,nj->ni'),  to_origin = |q|,  coords = q + knots[n]
+// then two scans over the knots (the nearest knot, the sign change of to_plane nearest to it) and the interpolation to to_plane = 0 over
+// up to four planes.  The result may be non-finite (a duplicate to_plane in the window).
+template <bool LDS, bool TO_GLOBAL>
+__device__ __forceinline__ void rs_curve_map(const RsCurve& cv, const double P0, const double P1, const double P2, double& l0, double& l1,
+                                             double& l2) {
+    const int N = cv.N;
 #define RS_K(n, i) (LDS ? rs_lds[3 * (n) + (i)] : cv.knots[3 * (long long)(n) + (i)])
 #define RS_B(n, j, i) (LDS ? rs_lds[3 * N + 9 * (n) + 3 * (j) + (i)] : cv.basis[9 * (long long)(n) + 3 * (j) + (i)])
 #define RS_C(n) (LDS ? rs_lds[12 * N + (n)] : cv.cumlen[n])
-    const long long total = (long long)A.rn0 * A.rn1 * A.rn2;
-    const long long e = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
-    if (e >= total) return;
-    const int iz = (int)(e % A.rn2), iy = (int)((e / A.rn2) % A.rn1), ix = (int)(e / ((long long)A.rn1 * A.rn2));
-    const long long px = A.r0 + ix, py = A.r1 + iy, pz = A.r2 + iz;
-    const double P0 = (double)px, P1 = (double)py, P2 = (double)pz;
-
-    // scan 1: idx = to_origin.argmin(), the first minimum of || p - knots[n] ||
+    // scan 1: idx = to_origin.argmin(), the first minimum
     double best = __builtin_inf();
     int idx = 0;
     for (int n = 0; n < N; ++n) {
-        const double d0 = P0 - RS_K(n, 0), d1 = P1 - RS_K(n, 1), d2 = P2 - RS_K(n, 2);
-        const double r = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        double r;
+        if (TO_GLOBAL) {
+            const double d0 = P0 - RS_C(n), d1 = P1 - cv.c1, d2 = P2 - cv.c2;
+            const double g0 = (RS_B(n, 0, 0) * d0 + RS_B(n, 0, 1) * d1) + RS_B(n, 0, 2) * d2;
+            const double g1 = (RS_B(n, 1, 0) * d0 + RS_B(n, 1, 1) * d1) + RS_B(n, 1, 2) * d2;
+            const double g2 = (RS_B(n, 2, 0) * d0 + RS_B(n, 2, 1) * d1) + RS_B(n, 2, 2) * d2;
+            r = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
+        } else {
+            const double d0 = P0 - RS_K(n, 0), d1 = P1 - RS_K(n, 1), d2 = P2 - RS_K(n, 2);
+            r = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        }
         if (r < best) { best = r; idx = n; }
     }
     // scan 2: the candidates n with sign(to_plane[n + 1]) - sign(to_plane[n]) != 0; the one nearest idx, the lowest on ties
     {
         int cand = -1, cand_d = 0x7fffffff;
-        double d0 = P0 - RS_K(0, 0), d1 = P1 - RS_K(0, 1), d2 = P2 - RS_K(0, 2);
-        int s_prev = rs_sign((RS_B(0, 0, 0) * d0 + RS_B(0, 1, 0) * d1) + RS_B(0, 2, 0) * d2);
+        int s_prev;
+        if (TO_GLOBAL) {
+            s_prev = rs_sign(P0 - RS_C(0));
+        } else {
+            const double d0 = P0 - RS_K(0, 0), d1 = P1 - RS_K(0, 1), d2 = P2 - RS_K(0, 2);
+            s_prev = rs_sign((RS_B(0, 0, 0) * d0 + RS_B(0, 1, 0) * d1) + RS_B(0, 2, 0) * d2);
+        }
         for (int n = 0; n + 1 < N; ++n) {
-            d0 = P0 - RS_K(n + 1, 0); d1 = P1 - RS_K(n + 1, 1); d2 = P2 - RS_K(n + 1, 2);
-            const int s_next = rs_sign((RS_B(n + 1, 0, 0) * d0 + RS_B(n + 1, 1, 0) * d1) + RS_B(n + 1, 2, 0) * d2);
+            int s_next;
+            if (TO_GLOBAL) {
+                s_next = rs_sign(P0 - RS_C(n + 1));
+            } else {
+                const double d0 = P0 - RS_K(n + 1, 0), d1 = P1 - RS_K(n + 1, 1), d2 = P2 - RS_K(n + 1, 2);
+                s_next = rs_sign((RS_B(n + 1, 0, 0) * d0 + RS_B(n + 1, 1, 0) * d1) + RS_B(n + 1, 2, 0) * d2);
+            }
             if (s_next != s_prev) {
                 const int dd = n > idx ? n - idx : idx - n;
                 if (dd < cand_d) { cand_d = dd; cand = n; }
@@ -112,14 +137,25 @@ __global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs 
     for (int k = 0; k < 4; ++k) {
         const bool valid = k < L;
         const int n = valid ? w0 + k : w0;
-        const double d0 = P0 - RS_K(n, 0), d1 = P1 - RS_K(n, 1), d2 = P2 - RS_K(n, 2);
-        const double q0 = (RS_B(n, 0, 0) * d0 + RS_B(n, 1, 0) * d1) + RS_B(n, 2, 0) * d2;
-        const double q1 = (RS_B(n, 0, 1) * d0 + RS_B(n, 1, 1) * d1) + RS_B(n, 2, 1) * d2;
-        const double q2 = (RS_B(n, 0, 2) * d0 + RS_B(n, 1, 2) * d1) + RS_B(n, 2, 2) * d2;
-        x[k] = valid ? q0 : __builtin_inf();
-        y0[k] = q0 + RS_C(n);
-        y1[k] = q1 + cv.c1;
-        y2[k] = q2 + cv.c2;
+        if (TO_GLOBAL) {
+            const double d0 = P0 - RS_C(n), d1 = P1 - cv.c1, d2 = P2 - cv.c2;
+            const double g0 = (RS_B(n, 0, 0) * d0 + RS_B(n, 0, 1) * d1) + RS_B(n, 0, 2) * d2;
+            const double g1 = (RS_B(n, 1, 0) * d0 + RS_B(n, 1, 1) * d1) + RS_B(n, 1, 2) * d2;
+            const double g2 = (RS_B(n, 2, 0) * d0 + RS_B(n, 2, 1) * d1) + RS_B(n, 2, 2) * d2;
+            x[k] = valid ? d0 : __builtin_inf();
+            y0[k] = g0 + RS_K(n, 0);
+            y1[k] = g1 + RS_K(n, 1);
+            y2[k] = g2 + RS_K(n, 2);
+        } else {
+            const double d0 = P0 - RS_K(n, 0), d1 = P1 - RS_K(n, 1), d2 = P2 - RS_K(n, 2);
+            const double q0 = (RS_B(n, 0, 0) * d0 + RS_B(n, 1, 0) * d1) + RS_B(n, 2, 0) * d2;
+            const double q1 = (RS_B(n, 0, 1) * d0 + RS_B(n, 1, 1) * d1) + RS_B(n, 2, 1) * d2;
+            const double q2 = (RS_B(n, 0, 2) * d0 + RS_B(n, 1, 2) * d1) + RS_B(n, 2, 2) * d2;
+            x[k] = valid ? q0 : __builtin_inf();
+            y0[k] = q0 + RS_C(n);
+            y1[k] = q1 + cv.c1;
+            y2[k] = q2 + cv.c2;
+        }
     }
     // interp1d to 0 as straighten.interp_linear restates it: stable sort by to_plane (adjacent exchanges on a strict >), searchsorted left,
     // the segment clipped to [1, L - 1], slope * (0 - x_lo) + y_lo
@@ -138,13 +174,26 @@ __global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs 
     const double x_lo = RS_SEL(x, hi - 1), x_hi = RS_SEL(x, hi);
     const double dx = x_hi - x_lo, xn = 0.0 - x_lo;
     const double a0 = RS_SEL(y0, hi - 1), a1 = RS_SEL(y1, hi - 1), a2 = RS_SEL(y2, hi - 1);
-    const double l0 = ((RS_SEL(y0, hi) - a0) / dx) * xn + a0;
-    const double l1 = ((RS_SEL(y1, hi) - a1) / dx) * xn + a1;
-    const double l2 = ((RS_SEL(y2, hi) - a2) / dx) * xn + a2;
+    l0 = ((RS_SEL(y0, hi) - a0) / dx) * xn + a0;
+    l1 = ((RS_SEL(y1, hi) - a1) / dx) * xn + a1;
+    l2 = ((RS_SEL(y2, hi) - a2) / dx) * xn + a2;
 #undef RS_SEL
 #undef RS_K
 #undef RS_B
 #undef RS_C
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs A) {
+    if (LDS) rs_stage(cv);
+    const long long total = (long long)A.rn0 * A.rn1 * A.rn2;
+    const long long e = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int iz = (int)(e % A.rn2), iy = (int)((e / A.rn2) % A.rn1), ix = (int)(e / ((long long)A.rn1 * A.rn2));
+    const long long px = A.r0 + ix, py = A.r1 + iy, pz = A.r2 + iz;
+    // the voxel in millimetres (pixel_to_spatial, curve.py:160-176): the knots are in millimetres
+    double l0, l1, l2;
+    rs_curve_map<LDS, false>(cv, (double)px * cv.sp0, (double)py * cv.sp1, (double)pz * cv.sp2, l0, l1, l2);
     const bool finite = isfinite(l0) && isfinite(l1) && isfinite(l2);
     if (A.local) {
         const double nan = __builtin_nan("");
@@ -197,13 +246,44 @@ __global__ __launch_bounds__(256) void restore_uncrop_kernel(RsArgs A) {
     rs_write(A, px, py, pz, v, l);
 }
 
-extern "C" int hv_restore_volume(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
-                                 long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+// hv_curve_points: one lane per point.  direction 0: the point (voxel indices) times the spacing through _to_local, the local coordinate
+// in the reference's order (no in-plane swap); direction 1: the local point through _to_global, the result divided by the spacing.
+template <bool LDS>
+__global__ __launch_bounds__(RS_THREADS) void curve_points_kernel(RsCurve cv, const double* __restrict__ points, long long M, int direction,
+                                                                  double* __restrict__ out) {
+    if (LDS) rs_stage(cv);
+    const long long m = (long long)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const double p0 = points[3 * m], p1 = points[3 * m + 1], p2 = points[3 * m + 2];
+    double r0, r1, r2;
+    if (direction == HV_CURVE_TO_LOCAL) {
+        rs_curve_map<LDS, false>(cv, p0 * cv.sp0, p1 * cv.sp1, p2 * cv.sp2, r0, r1, r2);
+    } else {
+        rs_curve_map<LDS, true>(cv, p0, p1, p2, r0, r1, r2);
+        r0 = r0 / cv.sp0; r1 = r1 / cv.sp1; r2 = r2 / cv.sp2;        // spatial_to_pixel (curve.py:179-195)
+    }
+    const bool finite = isfinite(r0) && isfinite(r1) && isfinite(r2);
+    const double nan = __builtin_nan("");
+    out[3 * m] = finite ? r0 : nan;
+    out[3 * m + 1] = finite ? r1 : nan;
+    out[3 * m + 2] = finite ? r2 : nan;
+}
+
+static bool rs_spacing_ok(const double* sp) {
+    if (!sp) return false;
+    for (int i = 0; i < 3; ++i)
+        if (!(sp[i] > 0.0) || !std::isfinite(sp[i])) return false;
+    return true;
+}
+
+extern "C" int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2,
+                                    const uint8_t* crop_label, long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
                                  const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
                                  int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region,
                                  int where, int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out,
                                  long long qs0, long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2,
-                                 double* local_out, void* stream) {
+                                 double* local_out, const double* spacing, void* stream) {
+    if (!rs_spacing_ok(spacing)) return HV_ERR_ARG;
     if (!crop_ct || !crop_label || !box || !region || !ct_out || !label_out || O0 <= 0 || O1 <= 0 || O2 <= 0 || D0 <= 0 || D1 <= 0 || D2 <= 0 ||
         (crop_dtype != HV_DT_F32 && crop_dtype != HV_DT_F64) || (where != HV_RESTORE_CROP && where != HV_RESTORE_VERTEBRA) || vert_id < 0 ||
         vert_id > 255)
@@ -238,10 +318,43 @@ extern "C" int hv_restore_volume(const void* crop_ct, int crop_dtype, long long 
     }
     RsCurve cv;
     cv.knots = knots; cv.basis = basis; cv.cumlen = cumlen; cv.N = N; cv.c1 = centre1; cv.c2 = centre2;
+    cv.sp0 = spacing[0]; cv.sp1 = spacing[1]; cv.sp2 = spacing[2];
     const size_t lds = (size_t)N * RS_KNOT_DOUBLES * sizeof(double);
     const int grid = hv_cdiv(total, RS_THREADS);
     if (lds <= RS_LDS_BYTES) hipLaunchKernelGGL(restore_kernel<true>, dim3(grid), dim3(RS_THREADS), lds, s, cv, A);
     else hipLaunchKernelGGL(restore_kernel<false>, dim3(grid), dim3(RS_THREADS), 0, s, cv, A);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+// the entry from before the spacing: voxel indices are millimetres (x * 1.0 is exact: the same bits)
+extern "C" int hv_restore_volume(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
+                                 long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+                                 const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
+                                 int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region,
+                                 int where, int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out,
+                                 long long qs0, long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2,
+                                 double* local_out, void* stream) {
+    const double ones[3] = {1.0, 1.0, 1.0};
+    return hv_restore_volume_sp(crop_ct, crop_dtype, cs0, cs1, cs2, crop_label, ls0, ls1, ls2, O0, O1, O2, box, knots, basis, cumlen, N, centre1,
+                                centre2, patient_label, label_dtype, ps0, ps1, ps2, D0, D1, D2, region, where, vert_id, ct_out, os0, os1, os2,
+                                label_out, qs0, qs1, qs2, covered, vs0, vs1, vs2, local_out, ones, stream);
+}
+
+extern "C" int hv_curve_points(const double* points, long long M, const double* knots, const double* basis, const double* cumlen, int N,
+                               double centre1, double centre2, const double* spacing, int direction, double* out, void* stream) {
+    if (!points || !knots || !basis || !cumlen || !out || M <= 0 || N < 2 || !rs_spacing_ok(spacing) ||
+        (direction != HV_CURVE_TO_LOCAL && direction != HV_CURVE_TO_GLOBAL))
+        return HV_ERR_ARG;
+    if (M > 0x7fffffffLL * 64) return HV_ERR_UNSUPPORTED;
+    RsCurve cv;
+    cv.knots = knots; cv.basis = basis; cv.cumlen = cumlen; cv.N = N; cv.c1 = centre1; cv.c2 = centre2;
+    cv.sp0 = spacing[0]; cv.sp1 = spacing[1]; cv.sp2 = spacing[2];
+    const size_t lds = (size_t)N * RS_KNOT_DOUBLES * sizeof(double);
+    const int grid = hv_cdiv(M, RS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    if (lds <= RS_LDS_BYTES) hipLaunchKernelGGL(curve_points_kernel<true>, dim3(grid), dim3(RS_THREADS), lds, s, cv, points, M, direction, out);
+    else hipLaunchKernelGGL(curve_points_kernel<false>, dim3(grid), dim3(RS_THREADS), 0, s, cv, points, M, direction, out);
     HV_LAUNCH_CHECK();
     return HV_OK;
 }

@@ -6,13 +6,15 @@
 //                                     (the centroids of location_json_local.py, exact), a flag for non-integer / out-of-range labels, and
 //                                     the raw-geometry presence bits of the split cleanup (the single-centroid branch, :499-502)
 //   straighten_sample_kernel<T>       one lane per (n, a, b) of the straight volumes [N][PA][PB]: the fp64 sample coordinate
-//                                     knots[n] + basis[n][:,1] (b - PB/2) + basis[n][:,2] (a - PA/2) (curve.py:54-102), trilinear on the
+//                                     (knots[n] + basis[n][:,1] (b - PB/2) + basis[n][:,2] (a - PA/2)) / spacing (curve.py:54-102; knots and
+//                                     frame in millimetres, the quotient per axis in voxel indices of the scan), trilinear on the
 //                                     windowed CT (map_coordinates order 1, mode 'constant'), nearest on the label (order 0), and the
 //                                     presence bits of column b = PB/2, rows a >= PA/2 (remove_spine_labels_after_split, :123-146)
 //   straighten_crop_kernel            every requested vertebra in one launch: extract_3d_volume (:222-247) from the straight volumes (or the
 //                                     raw ones, windowed on the fly), the per-label row cutoff of the split cleanup applied on the way
 // Everything in doubles in the reference's operation order (-ffp-contract=off); element offsets are 64-bit (a float64 CT passes 2^31 bytes).
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include "hv_common.h"
 
@@ -140,6 +142,8 @@ __global__ __launch_bounds__(256) void straighten_stats_label_kernel(const T* __
     }
 }
 
+struct SsSpacing { double s0, s1, s2; };      // millimetres per voxel along axes 0, 1, 2: a kernel argument, no device allocation
+
 // one lane per sample; workgroups are renumbered so that consecutive planes (which read the same voxels) run on one XCD
 // (the hardware hands workgroup i to XCD i % 8)
 template <typename T>
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(256) void straighten_sample_kernel(const T* __restr
                                                                 int D0, int D1, int D2, const double* __restrict__ knots,
                                                                 const double* __restrict__ basis, int N, int PA, int PB, int win, double wmin,
                                                                 double wmax, double* __restrict__ sct, uint8_t* __restrict__ slab,
-                                                                u64* __restrict__ pres, int nblk) {
+                                                                u64* __restrict__ pres, int nblk, SsSpacing sp) {
     const int per_xcd = gridDim.x / 8;
     const int blk = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (blk >= nblk) return;
@@ -164,6 +168,8 @@ __global__ __launch_bounds__(256) void straighten_sample_kernel(const T* __restr
     double c[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) c[i] = ((B[3 * i] * 0.0 + B[3 * i + 1] * gb) + B[3 * i + 2] * ga) + K[i];
+    // knots and frame are in millimetres: back to voxel indices (spatial_to_pixel, curve.py:74,179-195)
+    c[0] = c[0] / sp.s0; c[1] = c[1] / sp.s1; c[2] = c[2] / sp.s2;
     const int D[3] = {D0, D1, D2};
     bool in = true;
 #pragma unroll
@@ -302,10 +308,15 @@ extern "C" int hv_straighten_stats(const void* ct, int ct_dtype, long long cs0, 
     return HV_OK;
 }
 
-extern "C" int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
-                                    long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis,
-                                    int N, int PA, int PB, int window, double win_min, double win_max, double* straight_ct,
-                                    uint8_t* straight_label, uint64_t* presence, size_t presence_bytes, void* stream) {
+extern "C" int hv_straighten_sample_sp(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label,
+                                       int label_dtype, long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots,
+                                       const double* basis, int N, int PA, int PB, int window, double win_min, double win_max,
+                                       double* straight_ct, uint8_t* straight_label, uint64_t* presence, size_t presence_bytes,
+                                       const double* spacing, void* stream) {
+    if (!spacing) return HV_ERR_ARG;
+    for (int i = 0; i < 3; ++i)
+        if (!(spacing[i] > 0.0) || !std::isfinite(spacing[i])) return HV_ERR_ARG;
+    const SsSpacing sp = {spacing[0], spacing[1], spacing[2]};
     if (!ct || !label || !knots || !basis || !straight_ct || !straight_label || !presence || D0 <= 0 || D1 <= 0 || D2 <= 0 || N <= 0 ||
         PA <= 0 || PB <= 0 || !ss_ct_dtype(ct_dtype) || !ss_label_dtype(label_dtype))
         return HV_ERR_ARG;
@@ -318,7 +329,7 @@ extern "C" int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0,
     const int grid = hv_cdiv(nblk, 8) * 8;
 #define SS_SMP(T) hipLaunchKernelGGL(straighten_sample_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)ct, cs0, cs1, cs2, label, label_dtype, \
                                      ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, window, win_min, win_max, straight_ct, straight_label, \
-                                     (u64*)presence, nblk)
+                                     (u64*)presence, nblk, sp)
     switch (ct_dtype) {
         case HV_DT_I16: SS_SMP(int16_t); break;
         case HV_DT_F32: SS_SMP(float); break;
@@ -327,6 +338,16 @@ extern "C" int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0,
 #undef SS_SMP
     HV_LAUNCH_CHECK();
     return HV_OK;
+}
+
+// the entry from before the spacing: the scan is on a 1 mm grid (x / 1.0 is exact: the same bits)
+extern "C" int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                                    long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis,
+                                    int N, int PA, int PB, int window, double win_min, double win_max, double* straight_ct,
+                                    uint8_t* straight_label, uint64_t* presence, size_t presence_bytes, void* stream) {
+    const double ones[3] = {1.0, 1.0, 1.0};
+    return hv_straighten_sample_sp(ct, ct_dtype, cs0, cs1, cs2, label, label_dtype, ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, window,
+                                   win_min, win_max, straight_ct, straight_label, presence, presence_bytes, ones, stream);
 }
 
 extern "C" int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,

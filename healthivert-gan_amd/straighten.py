@@ -18,6 +18,14 @@ requested vertebra (csrc/straighten.hip).
                                                             the way back: Interpolator.global_to_local (curve.py:104-150,223-239) for every
                                                             voxel of a vertebra's patient-space box (restore_box) and a resample of the
                                                             (synthesized) crop there (csrc/restore.hip)
+  points_to_local(plan, points) / points_to_global(plan, points)   Interpolator.global_to_local / local_to_global (curve.py:104-114) for a
+                                                            list of points on the device: where in the patient's scan a position of the
+                                                            straightened frame lies, and back
+
+Scans with anisotropic voxels: straighten_patient, plan, curve_frame, global_to_local, local_to_global and restore_box take
+spacing=(sx, sy, sz), millimetres per voxel, the `spacing` of the reference's Interpolator (curve.py:26-52,160-195), which process_mask3d
+leaves at 1.  The scan is read at its native spacing, the crops come out on the 1 mm grid the later stages assume, and restore_patient
+(which reads the spacing from the plan) writes back onto the scan's own grid.
 
 Volumes are [X, Y, Z] device tensors as nibabel hands them over (any strides; a Fortran-ordered array passes as it lies).  The CT may be
 int16, float32 or float64 and is windowed in double for every dtype.  Deviation: the reference reads CT files over 500 MB as float32
@@ -89,11 +97,35 @@ def local_basis(grad):
     return np.stack([g, second, np.cross(second, g)], -1)
 
 
-def curve_frame(curve, step=1):
-    """Interpolator(curve, step, get_local_basis=get_local_basis) (curve.py:26-52 with get_derivatives :209-221): knots at
-    arange(0, L, step) of the cumulative length, np.gradient of the points interpolated the same way, the frame of local_basis.
-    -> knots [N][3], basis [N][3][3]."""
-    curve = np.asarray(curve, dtype=np.float64)
+def check_spacing(spacing):
+    """The `spacing` of Interpolator (curve.py:26-44) as three positive finite floats, millimetres per voxel along axes 0, 1, 2; a scalar
+    stands for all three.  The library's per-axis position tables (a sequence per axis, curve.py:172-173,191-192) are out of scope."""
+    if isinstance(spacing, (int, float, np.integer, np.floating)) and not isinstance(spacing, bool):
+        spacing = [spacing] * 3
+    try:
+        spacing = list(spacing)
+    except TypeError:
+        raise ValueError('spacing: three positive floats or one, got %r' % (spacing,))
+    if len(spacing) != 3:
+        raise ValueError('spacing: one value per axis (3), got %d' % len(spacing))
+    out = []
+    for s in spacing:
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)):
+            if np.ndim(s) > 0 or isinstance(s, (list, tuple)):
+                raise ValueError('spacing: per-axis position tables (a sequence per axis) are out of scope, one positive float per axis')
+            raise ValueError('spacing: one positive float per axis, got %r' % (s,))
+        s = float(s)
+        if not (np.isfinite(s) and s > 0.0):
+            raise ValueError('spacing: values must be positive and finite, got %r' % (spacing,))
+        out.append(s)
+    return tuple(out)
+
+
+def curve_frame(curve, step=1, spacing=(1.0, 1.0, 1.0)):
+    """Interpolator(curve, step, spacing, get_local_basis=get_local_basis) (curve.py:26-52 with get_derivatives :209-221): the curve (voxel
+    indices) times the spacing (pixel_to_spatial, :160-176), knots at arange(0, L, step) of its cumulative length in millimetres, np.gradient
+    of the points interpolated the same way, the frame of local_basis.  -> knots [N][3] (millimetres), basis [N][3][3]."""
+    curve = np.asarray(curve, dtype=np.float64) * np.asarray(check_spacing(spacing))
     lengths = cumulative_length(curve)
     xs = np.arange(0, lengths[-1], step)
     knots = interp_linear(lengths, curve, xs)
@@ -101,18 +133,16 @@ def curve_frame(curve, step=1):
     return knots, local_basis(grad)
 
 
-def global_to_local(point, knots, basis, shape=PLANE):
-    """Interpolator.global_to_local (curve.py:104-150,223-239) for one point: its offsets from every knot in that knot's frame, plus the
-    plane centres (cumulative length, shape / 2); the plane is chosen where the distance to the plane changes sign closest to the nearest
-    knot, and the coordinates are interpolated linearly to distance 0 over up to four planes around it."""
-    p = np.asarray(point, dtype=np.float64) - knots
-    to_origin = np.linalg.norm(p, axis=-1)
-    p = np.einsum('nji,nj->ni', basis, p)
-    to_plane = p[:, 0]
+def _centers(knots, shape):
+    """Interpolator._get_centers (curve.py:116-120): per knot (cumulative length, shape / 2)."""
     centers = np.zeros_like(knots)
     centers[:, 0] = cumulative_length(knots)
     centers[:, 1:] = np.broadcast_to(shape, 2) / 2
-    coords = p + centers
+    return centers
+
+
+def _interpolate_coords(coords, to_origin, to_plane):
+    """interpolate_coords (curve.py:223-239)."""
     idx = to_origin.argmin()
     cand, = np.diff(np.sign(to_plane)).nonzero()
     if len(cand) != 1:
@@ -121,6 +151,36 @@ def global_to_local(point, knots, basis, shape=PLANE):
         idx = cand[np.abs(cand - idx).argmin()]
     slc = slice(max(0, idx - 2), idx + 2)
     return interp_linear(to_plane[slc], coords[slc], 0.0)[0]
+
+
+def global_to_local(point, knots, basis, shape=PLANE, spacing=(1.0, 1.0, 1.0)):
+    """Interpolator.global_to_local (curve.py:104-150,223-239) for one point (voxel indices): times the spacing (pixel_to_spatial), its
+    offsets from every knot in that knot's frame, plus the plane centres (cumulative length, shape / 2); the plane is chosen where the
+    distance to the plane changes sign closest to the nearest knot, and the coordinates are interpolated linearly to distance 0 over up to
+    four planes around it."""
+    p = np.asarray(point, dtype=np.float64) * np.asarray(check_spacing(spacing)) - knots
+    to_origin = np.linalg.norm(p, axis=-1)
+    p = np.einsum('nji,nj->ni', basis, p)
+    to_plane = p[:, 0]
+    return _interpolate_coords(p + _centers(knots, shape), to_origin, to_plane)
+
+
+def local_to_global(points, knots, basis, shape=PLANE, spacing=(1.0, 1.0, 1.0)):
+    """Interpolator.local_to_global (curve.py:110-114,131-138,223-239) for one local point or an array [..., 3] of them (cumulative length,
+    offset along frame vector 1, along frame vector 2): per knot the offset from the plane centre, carried into the scan by the knot's
+    frame and added to the knot; the plane is chosen and the result interpolated to distance 0 as in global_to_local; the millimetres are
+    divided by the spacing (spatial_to_pixel, :179-195).  -> voxel indices, the shape of `points`."""
+    sp = np.asarray(check_spacing(spacing))
+    pts = np.asarray(points, dtype=np.float64)
+    centers = _centers(knots, shape)
+    out = np.empty((pts.size // 3, 3))
+    for k, point in enumerate(pts.reshape(-1, 3)):
+        p = point - centers
+        to_plane = p[:, 0]
+        p = np.einsum('nij,nj->ni', basis, p)
+        to_origin = np.linalg.norm(p, axis=-1)
+        out[k] = _interpolate_coords(p + knots, to_origin, to_plane)
+    return (out / sp).reshape(pts.shape)
 
 
 def crop_box(center, src_shape, size):
@@ -229,10 +289,19 @@ def vertebra_centroids(label):
     return centroids_from_counts(st.counts, st.sums)
 
 
-def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE):
+class Plan(tuple):
+    """What plan() returns: the tuple (knots, basis, local, boxes) with the spacing it was made with as `.spacing`."""
+    spacing = (1.0, 1.0, 1.0)
+
+
+def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE, spacing=(1.0, 1.0, 1.0)):
     """Host part of process_mask3d (straighten_mask_3d.py:485-541) for a centroid list and a volume shape: the extended curve, knots and
     frame (None, None with one centroid), and per requested vertebra the local centroid and its crop box.  Raises ValueError for a
-    missing id or a degenerate curve (the reference would divide by zero or hit a NameError)."""
+    missing id or a degenerate curve (the reference would divide by zero or hit a NameError).
+    spacing: millimetres per voxel of the scan, handed to the Interpolator (:505 with spacing=spacing).  Centroids, the curve extension and
+    its clamp stay in voxel indices as in the reference; knots, frame and local centroids are in millimetres, so the straight volume is on
+    a 1 mm grid.  The single-centroid branch crops the raw volume and ignores the spacing.  -> Plan (knots, basis, local, boxes)."""
+    spacing = check_spacing(spacing)
     coords = [[e['X'], e['Y'], e['Z']] for e in centroids if isinstance(e, dict) and 'X' in e]
     if not coords:
         raise ValueError('straighten: no centroid')
@@ -244,7 +313,7 @@ def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE):
         curve = extend_curve(curve, EXTENSION, (0, 0, 0), tuple(shape))
         if (np.linalg.norm(np.diff(curve, axis=0), axis=1) == 0).any():
             raise ValueError('straighten: degenerate curve after the extension')
-        knots, basis = curve_frame(curve, 1)
+        knots, basis = curve_frame(curve, 1, spacing)
         if len(knots) == 0 or not (np.isfinite(knots).all() and np.isfinite(basis).all()):
             raise ValueError('straighten: degenerate curve (no finite frame)')
         src_shape = (len(knots), plane[1], plane[0])
@@ -263,12 +332,14 @@ def plan(centroids, shape, vertebrae_ids, out_size=(256, 256, 64), plane=PLANE):
         if knots is not None:
             with warnings.catch_warnings():
                 warnings.simplefilter('ignore')
-                centroid = global_to_local(centroid, knots, basis, plane)
+                centroid = global_to_local(centroid, knots, basis, plane, spacing)
             if not np.isfinite(centroid).all():
                 raise ValueError('straighten: vertebra %r: no local position on the curve' % (vid,))
         local[vid] = np.asarray(centroid, dtype=np.float64)
         boxes.append(crop_box(centroid, src_shape, out_size))
-    return knots, basis, local, boxes
+    res = Plan((knots, basis, local, boxes))
+    res.spacing = spacing
+    return res
 
 
 def _depedicle_launch(vol4, out4, counts):
@@ -365,13 +436,17 @@ def single_component_range(label_vol, label, offset=10):
 _depedicle = depedicle
 
 
-def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False, depedicle=False):
+def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False, depedicle=False,
+                       spacing=(1.0, 1.0, 1.0)):
     """process_mask3d(ct, label, json, vertebrae_ids, out, out_size) on device tensors (straighten_mask_3d.py:463-563, mask_2d and file I/O
     excepted).  ct: [X, Y, Z] int16 / float32 / float64; label: [X, Y, Z] integer values 0..255 in any integer or float dtype.  centroids:
     the list location_json_local.py writes, or None = computed on the device from the same stats pass.
     depedicle: the label crops of all requested vertebrae go through one de-pedicling launch, in place, before they are returned (the
     process_3d_array call the reference keeps commented out in process_mask3d).
+    spacing: millimetres per voxel of the scan along its three axes (a scalar: all three), the Interpolator's `spacing` (curve.py:26-52):
+    the scan is read at its native spacing and the crops come out on the 1 mm grid the later stages assume; no resampled copy is made.
     -> {vert_id: (ct_vol float64, label_vol uint8)}, each [out_size] on the device, the orientation the reference saves."""
+    spacing = check_spacing(spacing)          # before any GPU work
     ctc, lc = _check(ct, label)
     L = _lib.get()
     dev = ct.device
@@ -380,7 +455,7 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
     if centroids is None:
         centroids = centroids_from_counts(st.counts, st.sums)
     vertebrae_ids = list(vertebrae_ids)
-    knots, basis, local, boxes = plan(centroids, (X, Y, Z), vertebrae_ids, out_size)
+    knots, basis, local, boxes = plan(centroids, (X, Y, Z), vertebrae_ids, out_size, spacing=spacing)
     # window(): the whole volume inside (-300, 800) is returned unchanged (:172-176)
     win = 0 if (st.ct_max < WINDOW[1] and st.ct_min > WINDOW[0]) else 1
     wmin, wmax = ctypes.c_double(WINDOW[0]), ctypes.c_double(WINDOW[1])
@@ -398,9 +473,9 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
             slab = torch.empty(N, PA, PB, dtype=torch.uint8, device=dev)
             pbytes = L.size('hv_straighten_presence_bytes', PA)
             pres = torch.empty(pbytes // 8, dtype=torch.int64, device=dev)
-            L.call('hv_straighten_sample', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z,
+            L.call('hv_straighten_sample_sp', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z,
                    _lib.ptr(d_knots), _lib.ptr(d_basis), N, PA, PB, win, wmin, wmax, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres),
-                   ctypes.c_size_t(pbytes), _lib.stream())
+                   ctypes.c_size_t(pbytes), (ctypes.c_double * 3)(*spacing), _lib.stream())
             L.call('hv_straighten_crop', _lib.ptr(sct), 5, *_strides(sct), _lib.ptr(slab), 0, *_strides(slab), PA, 0, wmin, wmax,
                    _lib.ptr(pres), _lib.ptr(d_boxes), V, O0, O1, O2, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
         else:   # one centroid: the windowed raw CT and the raw label are cropped at the raw position (:499-502)
@@ -410,7 +485,8 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
             _depedicle(lab_out, out=lab_out)
     out = {vid: (ct_out[i], lab_out[i]) for i, vid in enumerate(vertebrae_ids)}
     if return_plan:
-        return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win)}
+        return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win),
+                     'spacing': spacing}
     return out
 
 
@@ -418,13 +494,15 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
 RESTORE = {'crop': 0, 'vertebra': 1}          # HV_RESTORE_CROP / HV_RESTORE_VERTEBRA (include/hvgan.h)
 
 
-def restore_box(knots, basis, box, shape, plane=PLANE, pad=2):
+def restore_box(knots, basis, box, shape, plane=PLANE, pad=2, spacing=(1.0, 1.0, 1.0)):
     """Patient-space integer box that holds every voxel a crop's filled part can reach: -> [x0, y0, z0, nx, ny, nz] (all zero when nothing
     is filled).  box: the crop_box row of the vertebra.  With a curve, the filled part is the knots whose cumulative length lies in the
     row's axis-0 range (one knot more at each end: global_to_local interpolates between neighbouring planes) times the in-plane rectangle
     [lo1, lo1 + n1 - 1] x [lo2, lo2 + n2 - 1]; the box is the min / max over those knots of the rectangle's four corners
-    knots[n] + basis[n][:, 1] (b - plane[0] / 2) + basis[n][:, 2] (a - plane[1] / 2), widened by `pad` and clipped to the volume.  Without
-    one (knots None: the crop was cut from the raw volume) it is the row's source range itself."""
+    knots[n] + basis[n][:, 1] (b - plane[0] / 2) + basis[n][:, 2] (a - plane[1] / 2), in millimetres, divided by the spacing, widened by
+    `pad` (voxels) and clipped to the volume.  Without one (knots None: the crop was cut from the raw volume) it is the row's source range
+    itself, whatever the spacing."""
+    sp = np.asarray(check_spacing(spacing))
     lo, n = [int(v) for v in box[0:3]], [int(v) for v in box[3:6]]
     shape = [int(s) for s in shape]
     if min(n) <= 0:
@@ -442,7 +520,7 @@ def restore_box(knots, basis, box, shape, plane=PLANE, pad=2):
     a = np.array([lo[1], lo[1] + n[1] - 1], dtype=np.float64) - plane[1] / 2      # axis 1 of the straight volume runs along frame vector 2
     b = np.array([lo[2], lo[2] + n[2] - 1], dtype=np.float64) - plane[0] / 2
     corners = K[:, None, None, :] + B[:, None, None, :, 1] * b[None, None, :, None] + B[:, None, None, :, 2] * a[None, :, None, None]
-    corners = corners.reshape(-1, 3)
+    corners = corners.reshape(-1, 3) / sp
     mn = np.floor(corners.min(0)).astype(np.int64) - pad
     mx = np.ceil(corners.max(0)).astype(np.int64) + pad
     mn = np.maximum(mn, 0)
@@ -452,8 +530,16 @@ def restore_box(knots, basis, box, shape, plane=PLANE, pad=2):
     return [int(v) for v in mn] + [int(v) for v in mx - mn + 1]
 
 
+def _plan_spacing(plan, spacing=None):
+    """The spacing a plan was made with (ones for a plan from before plans recorded it); a `spacing` argument has to agree with it."""
+    own = check_spacing(plan.get('spacing', (1.0, 1.0, 1.0)))
+    if spacing is not None and check_spacing(spacing) != own:
+        raise ValueError('spacing %r is not the spacing %r the plan was made with' % (tuple(check_spacing(spacing)), own))
+    return own
+
+
 def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebra', return_covered=False, return_local=False, out=None,
-                    regions=None):
+                    regions=None, spacing=None):
     """The way back from the straightened crops to the patient's scan: Interpolator.global_to_local (curve.py:104-150,223-239) for every
     voxel of each vertebra's patient-space box and a resample of the crop there, on the device (csrc/restore.hip), where the reference
     offers the transform one point at a time in Python.
@@ -465,12 +551,15 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
     patient-space boxes to visit instead of restore_box's (a region of interest; voxels outside are not touched).
     where = 'crop': every voxel the crop covers is written (trilinear CT sample, nearest label sample); 'vertebra' (needs `label`): only
     where the label sample or the patient's own label is vert_id.  The crop's zero padding never reaches the patient.
+    spacing: None = plan['spacing'], the spacing of the scan the plan was made for ((1, 1, 1) for a plan without the entry); a value that
+    disagrees with the plan is a ValueError.  The outputs are on the scan's own grid: a box voxel enters the curve math in millimetres.
     -> (ct_out float64, label_out uint8[, covered uint8: 1 where written][, {vert_id: (box, local)}: the patient-space box
     [x0, y0, z0, nx, ny, nz] and the local coordinate of each of its voxels, float64 [nx, ny, nz, 3], NaN where there is none])."""
     if where not in RESTORE:
         raise ValueError("restore: where must be 'crop' or 'vertebra', got %r" % (where,))
     if where == 'vertebra' and label is None:
         raise ValueError("restore: where='vertebra' needs the patient's label volume")
+    spacing = _plan_spacing(plan, spacing)
     crops = dict(crops)
     if not crops:
         raise ValueError('restore: no crop')
@@ -514,7 +603,7 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
             box = None
         if box != own_box[vid]:        # the row the vertebra's crop was cut with: another size gives another row
             raise ValueError('restore: vertebra %r: a crop of size %s is not what the plan cut' % (vid, tuple(cvol.shape)))
-        region = restore_box(knots, basis, box, shape)
+        region = restore_box(knots, basis, box, shape, spacing=spacing)
         if regions is not None and vid in regions:
             region = [int(v) for v in regions[vid]]
             if len(region) != 6 or any(region[i] < 0 or region[3 + i] < 0 or region[i] + region[3 + i] > shape[i] for i in range(3)):
@@ -568,15 +657,67 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
             local[vid] = (region, loc)
         if min(region[3:]) <= 0:
             continue
-        L.call('hv_restore_volume', _lib.ptr(cvol), _DT[cvol.dtype], *_strides(cvol), _lib.ptr(lvol), *_strides(lvol), *cvol.shape,
+        L.call('hv_restore_volume_sp', _lib.ptr(cvol), _DT[cvol.dtype], *_strides(cvol), _lib.ptr(lvol), *_strides(lvol), *cvol.shape,
                (ctypes.c_int * 9)(*box), _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), N, ctypes.c_double(PLANE[0] / 2),
                ctypes.c_double(PLANE[1] / 2), _lib.ptr(label), 0 if label is None else _DT[label.dtype],
                *(zero3 if label is None else _strides(label)), *shape, (ctypes.c_int * 6)(*region), RESTORE[where], vid, _lib.ptr(ct_out),
                *_strides(ct_out), _lib.ptr(lab_out), *_strides(lab_out), _lib.ptr(covered), *(zero3 if covered is None else _strides(covered)),
-               _lib.ptr(loc), _lib.stream())
+               _lib.ptr(loc), (ctypes.c_double * 3)(*spacing), _lib.stream())
     res = (ct_out, lab_out)
     if return_covered:
         res += (covered,)
     if return_local:
         res += (local,)
     return res
+
+
+# ------------------------------------------------------------------------------------------------ points between the two spaces
+CURVE = {'local': 0, 'global': 1}             # HV_CURVE_TO_LOCAL / HV_CURVE_TO_GLOBAL (include/hvgan.h)
+
+
+def _plan_curve(plan):
+    """knots, basis, spacing of a plan: the dictionary straighten_patient(..., return_plan=True) returns, or what plan() returns."""
+    if isinstance(plan, Plan):
+        return plan[0], plan[1], check_spacing(plan.spacing)
+    return plan['knots'], plan['basis'], _plan_spacing(plan)
+
+
+def _points(plan, points, direction):
+    knots, basis, spacing = _plan_curve(plan)
+    on_device = isinstance(points, torch.Tensor)
+    pts = points if on_device else np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] <= 0 or (on_device and pts.dtype != torch.float64):
+        raise ValueError('points: expected [M, 3] float64 with M > 0, got %s %s' % (tuple(pts.shape), pts.dtype))
+    if on_device:
+        _lib.require_gpu(pts)
+    else:
+        pts = torch.from_numpy(pts).cuda()
+    pts = pts.contiguous()
+    if knots is None:               # one centroid: the crops were cut from the raw volume, local is global
+        return pts.clone()
+    dev = pts.device
+    d_knots = torch.from_numpy(np.ascontiguousarray(knots, dtype=np.float64)).to(dev)
+    d_basis = torch.from_numpy(np.ascontiguousarray(basis, dtype=np.float64)).to(dev)
+    d_cum = torch.from_numpy(np.ascontiguousarray(cumulative_length(knots), dtype=np.float64)).to(dev)
+    out = torch.empty_like(pts)
+    with torch.cuda.device(dev):
+        _lib.get().call('hv_curve_points', _lib.ptr(pts), ctypes.c_longlong(pts.shape[0]), _lib.ptr(d_knots), _lib.ptr(d_basis),
+                        _lib.ptr(d_cum), len(knots), ctypes.c_double(PLANE[0] / 2), ctypes.c_double(PLANE[1] / 2),
+                        (ctypes.c_double * 3)(*spacing), CURVE[direction], _lib.ptr(out), _lib.stream())
+    return out
+
+
+def points_to_local(plan, points):
+    """Interpolator.global_to_local (curve.py:104-108) for a list of points on the device: points [M, 3] float64, voxel indices of the
+    patient's scan (a numpy array is uploaded; a device tensor is read where it lies) -> device tensor [M, 3]: (cumulative length along
+    the curve, offset along frame vector 1, offset along frame vector 2), the reference's order; the index in the straight volume is
+    (row 0, row 2, row 1) and a crop adds its box: crop index = that - box[0:3] + box[6:9].  A row without a finite result is NaN.  With a
+    single-centroid plan the points come back unchanged."""
+    return _points(plan, points, 'local')
+
+
+def points_to_global(plan, points):
+    """Interpolator.local_to_global (curve.py:110-114) for a list of points on the device: where in the patient's scan (voxel indices, at
+    the plan's spacing) a local position lies, for example a column of height_loss_map.  Same conventions as points_to_local, of which it
+    is the inverse inside the curve's range."""
+    return _points(plan, points, 'global')

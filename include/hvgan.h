@@ -702,6 +702,13 @@ int hv_volume_merge_view(const float* src, const int* flag, int A0, int A1, int 
  *   knots[n] + basis[n][:,1] (b - PB/2) + basis[n][:,2] (a - PA/2) (knots [N][3], basis [N][3][3] row-major, fp64), trilinear on the CT
  *   (windowed when `window`: 255 (v - win_min) / (win_max - win_min) clipped to [0, 255]), nearest on the label, 0 outside [0, D - 1];
  *   presence (hv_straighten_presence_bytes(PA) bytes, zeroed by the call) for the straight label.
+ * hv_straighten_sample_sp: the same for a scan with anisotropic voxels (Interpolator(curve, step, spacing=...), curve.py:26-52,74,160-195).
+ *   spacing (HOST pointer, 3 doubles: millimetres per voxel along axes 0, 1, 2; copied into the kernel's arguments, no device allocation);
+ *   knots and basis are those of the curve in millimetres (curve * spacing) and sample (n, a, b) lies at
+ *   (knots[n] + basis[n][:,1] (b - PB/2) + basis[n][:,2] (a - PA/2)) / spacing, per axis, in voxel indices of the scan; everything after the
+ *   coordinate is hv_straighten_sample's.  The straight volumes are on a 1 mm grid whatever the scan's spacing.  hv_straighten_sample is
+ *   this entry with spacing {1, 1, 1} (x / 1.0 is exact: the same bits).  HV_ERR_ARG as for hv_straighten_sample, and for a NULL,
+ *   non-positive or non-finite spacing: nothing is launched and nothing is written.
  * hv_straighten_crop: extract_3d_volume for V vertebrae in one launch from a source volume (the straight ones: dtype F64 / U8, D1 = PA; or the
  *   raw ones, windowed when `window`): boxes (device, V x 9 ints) {lo0, lo1, lo2, len0, len1, len2, start0, start1, start2}: output (i, j, k)
  *   of vertebra v = source (lo + (i, j, k) - start) where 0 <= (i, j, k) - start < len, else 0.  A label voxel in a source row (axis 1) at or
@@ -716,6 +723,10 @@ int hv_straighten_sample(const void* ct, int ct_dtype, long long cs0, long long 
                          long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis, int N,
                          int PA, int PB, int window, double win_min, double win_max, double* straight_ct, uint8_t* straight_label,
                          uint64_t* presence, size_t presence_bytes, void* stream);
+int hv_straighten_sample_sp(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                            long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis, int N,
+                            int PA, int PB, int window, double win_min, double win_max, double* straight_ct, uint8_t* straight_label,
+                            uint64_t* presence, size_t presence_bytes, const double* spacing, void* stream);
 int hv_straighten_crop(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
                        long long ls0, long long ls1, long long ls2, int D1, int window, double win_min, double win_max, const uint64_t* presence,
                        const int* boxes, int V, int O0, int O1, int O2, double* ct_out, uint8_t* label_out, void* stream);
@@ -761,8 +772,25 @@ int hv_depedicle(const void* label, int label_dtype, long long ls0, long long ls
  *   [D0][D1][D2] with their own strides; every other voxel is left as it is.  local_out: NULL or [nx][ny][nz][3] fp64, the local coordinate of
  *   every box voxel (NaN where it is not finite; p itself with knots == NULL).  One call per vertebra; calls on one stream apply in order.
  * HV_ERR_ARG: null pointer, non-positive size, crop dtype not F32 / F64, unknown `where`, vert_id outside 0..255, N < 2, a box that leaves the
- *   crop, a region that leaves the patient volume: nothing is launched and nothing is written.  An empty region or box is HV_OK. */
+ *   crop, a region that leaves the patient volume: nothing is launched and nothing is written.  An empty region or box is HV_OK.
+ * hv_restore_volume_sp: the same for a scan with anisotropic voxels: spacing (HOST pointer, 3 doubles, millimetres per voxel along axes
+ *   0, 1, 2; copied into the kernel's arguments), knots / basis / cumlen those of the curve in millimetres; a box voxel p enters the knot
+ *   scans as p * spacing (pixel_to_spatial, curve.py:108,160-176) and everything after the local coordinate is unchanged (the crop is on
+ *   the 1 mm grid of the straight volumes).  With knots == NULL the spacing plays no part.  hv_restore_volume is this entry with spacing
+ *   {1, 1, 1} (x * 1.0 is exact: the same bits).  A NULL, non-positive or non-finite spacing is HV_ERR_ARG as above.
+ * hv_curve_points: Interpolator.global_to_local / local_to_global (curve.py:104-150,223-239) for M points ([M][3] fp64, device), one lane
+ *   per point, with the knot scans and the interpolation of hv_restore_volume_sp (one device function serves both; knots, frame and
+ *   cumulative lengths in LDS up to 630 knots, global memory beyond).
+ *   direction = HV_CURVE_TO_LOCAL: out[m] = global_to_local(points[m] * spacing), points in voxel indices of the scan.
+ *   direction = HV_CURVE_TO_GLOBAL: per knot n q = points[m] - (cumlen[n], centre1, centre2), to_plane = q[0], g = basis[n] q (summed over
+ *     the frame's columns, einsum 'nij,nj->ni'), to_origin = |g|, coords = g + knots[n]; the same choice of idx and the same window and
+ *     interpolation to to_plane = 0 as above; out[m] = that / spacing, in voxel indices of the scan.
+ *   The local coordinate keeps the reference's order (cumulative length, offset along frame vector 1, offset along frame vector 2): the
+ *   in-plane swap described above, which hv_restore_volume applies to index the crop, is NOT part of this entry; straight-volume index
+ *   (n, a, b) is local (n, b, a).  A row whose result is not finite is NaN.  out may be points.
+ *   HV_ERR_ARG: null pointer, M <= 0, N < 2, a non-positive or non-finite spacing, an unknown direction: nothing is launched or written. */
 enum { HV_RESTORE_CROP = 0, HV_RESTORE_VERTEBRA = 1 };
+enum { HV_CURVE_TO_LOCAL = 0, HV_CURVE_TO_GLOBAL = 1 };
 int hv_restore_volume(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
                       long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
                       const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
@@ -770,6 +798,15 @@ int hv_restore_volume(const void* crop_ct, int crop_dtype, long long cs0, long l
                       int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out, long long qs0,
                       long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2, double* local_out,
                       void* stream);
+int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
+                         long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+                         const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
+                         int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region, int where,
+                         int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out, long long qs0,
+                         long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2, double* local_out,
+                         const double* spacing, void* stream);
+int hv_curve_points(const double* points, long long M, const double* knots, const double* basis, const double* cumlen, int N, double centre1,
+                    double centre2, const double* spacing, int direction, double* out, void* stream);
 
 /* ---- generation-quality evaluation of a synthesized volume (reference evaluation/generation_eval_sagittal.py:11-37 calculate_iou /
  * calculate_dice / relative_volume_difference, :39-103 process_images; generation_eval_coronal.py the same with the slice axis 1; SURVEY.md

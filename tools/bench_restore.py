@@ -2,14 +2,15 @@
 csrc/restore.hip) vs the numpy restatement tests/restore_ref.py on the host.  Synthetic 512 x 512 x 400 int16 CT with a 15-vertebra uint8
 label, the reference's parameters (plane 128 x 128, out_size (256, 256, 64)), one vertebra in the middle of the spine.  Prints one JSON line:
   knots / box / box_voxels / covered      the curve's knot count, the patient-space box, its voxels and how many of them the crop covers
-  restore_ms                              the restore kernel alone: one hv_restore_volume launch with the curve already on the device, events around it, median
+  restore_ms                              the restore kernel alone: one hv_restore_volume_sp launch with the curve already on the device, events around it, median
   voxels_per_s                            box voxels / that
   patient_ms                              restore_patient end to end with zero bases handed in (host box arithmetic, three small blocking uploads, the launch), median
   copy_ms                                 a plain device copy of the box's bytes (fp64 CT + uint8 label + uint8 covered written per voxel)
   cpu_ref_s_extrapolated                  restore_ref on the host for a sub-box of --cpu-voxels voxels, scaled to the whole box
                                           (EXTRAPOLATED: the per-point Python loop takes minutes per vertebra)
 
-    timeout -k 10 600 python tools/bench_restore.py [--reps 10] [--cpu-voxels 4000] [--no-cpu]
+    timeout -k 10 600 python tools/bench_restore.py [--reps 10] [--cpu-voxels 4000] [--no-cpu] [--spacing a,b,c]
+--spacing: millimetres per voxel of the same 512 x 512 x 400 voxel patient (default 1,1,1).
 """
 import argparse
 import ctypes
@@ -44,14 +45,16 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--cpu-voxels', type=int, default=4000)
     ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--spacing', default='1,1,1')
     args = ap.parse_args()
+    spacing = S.check_spacing([float(v) for v in args.spacing.split(',')])
     shape = (512, 512, 400)
     ct, label = synth.make_spine_patient(seed=11, shape=shape, n_vert=15, radius=(40, 30, 9), end_radius=(14, 12, 5), margin=16, curve=(20.0, 40.0))
     tct, tlab = torch.from_numpy(ct).cuda(), torch.from_numpy(label).cuda()
     vid = [e['label'] for e in S.vertebra_centroids(tlab)][6]
-    crops, plan = S.straighten_patient(tct, tlab, [vid], return_plan=True)
+    crops, plan = S.straighten_patient(tct, tlab, [vid], return_plan=True, spacing=spacing)
     box = plan['boxes'][0]
-    region = S.restore_box(plan['knots'], plan['basis'], box, shape)
+    region = S.restore_box(plan['knots'], plan['basis'], box, shape, spacing=spacing)
     nvox = int(np.prod(region[3:]))
     out = (torch.zeros(shape, dtype=torch.float64, device='cuda'), torch.zeros(shape, dtype=torch.uint8, device='cuda'))
 
@@ -61,7 +64,7 @@ def main():
     covered = int(run()[2].sum())
     torch.cuda.synchronize()
     patient_ms = _timed(run, args.reps)
-    # the kernel alone: the curve uploaded once, hv_restore_volume launched directly, events around each launch
+    # the kernel alone: the curve uploaded once, hv_restore_volume_sp launched directly, events around each launch
     cvol, lvol = crops[vid]
     d_knots = torch.from_numpy(np.ascontiguousarray(plan['knots'])).cuda()
     d_basis = torch.from_numpy(np.ascontiguousarray(plan['basis'])).cuda()
@@ -72,10 +75,11 @@ def main():
     st = lambda t: [ctypes.c_longlong(v) for v in t.stride()]      # noqa: E731
 
     def launch():
-        L.call('hv_restore_volume', _lib.ptr(cvol), S._DT[cvol.dtype], *st(cvol), _lib.ptr(lvol), *st(lvol), *cvol.shape, c_box,
+        L.call('hv_restore_volume_sp', _lib.ptr(cvol), S._DT[cvol.dtype], *st(cvol), _lib.ptr(lvol), *st(lvol), *cvol.shape, c_box,
                _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), len(plan['knots']), ctypes.c_double(S.PLANE[0] / 2),
                ctypes.c_double(S.PLANE[1] / 2), _lib.ptr(tlab), S._DT[tlab.dtype], *st(tlab), *shape, c_region, S.RESTORE['crop'], int(vid),
-               _lib.ptr(out[0]), *st(out[0]), _lib.ptr(out[1]), *st(out[1]), _lib.ptr(cov), *st(cov), None, _lib.stream())
+               _lib.ptr(out[0]), *st(out[0]), _lib.ptr(out[1]), *st(out[1]), _lib.ptr(cov), *st(cov), None,
+               (ctypes.c_double * 3)(*spacing), _lib.stream())
 
     launch()
     torch.cuda.synchronize()
@@ -91,14 +95,15 @@ def main():
 
     copy()
     copy_ms = _timed(copy, args.reps)
-    res = {'knots': len(plan['knots']), 'box': region, 'box_voxels': nvox, 'covered': covered, 'restore_ms': round(restore_ms, 4),
+    res = {'spacing': list(spacing), 'knots': len(plan['knots']), 'box': region, 'box_voxels': nvox, 'covered': covered, 'restore_ms': round(restore_ms, 4),
            'voxels_per_s': round(nvox / (restore_ms * 1e-3), 1), 'patient_ms': round(patient_ms, 4), 'copy_ms': round(copy_ms, 4)}
     if not args.no_cpu:
         import restore_ref as R
+        import spacing_ref as SR
         side = max(2, int(round(args.cpu_voxels ** (1 / 3))))
         sub = [region[i] + (region[3 + i] - side) // 2 for i in range(3)] + [min(side, region[3 + i]) for i in range(3)]
         t0 = time.perf_counter()
-        loc = R.local_coords(plan['knots'], plan['basis'], sub)
+        loc = SR.local_coords(plan['knots'], plan['basis'], sub, spacing)
         c, cov = R.crop_coords(loc, box)
         from scipy.ndimage import map_coordinates
         cc, cl = crops[vid][0].cpu().numpy(), crops[vid][1].cpu().numpy()

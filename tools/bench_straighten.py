@@ -9,7 +9,8 @@ parameters (plane 128 x 128, out_size (256, 256, 64), every kept vertebra reques
   cpu_mirror_s                            the same patient on the host: centroids per label (np.where), window, map_coordinates x 2,
                                           split cleanup, crops
 
-    timeout -k 10 600 python tools/bench_straighten.py [--reps 10] [--no-cpu]
+    timeout -k 10 600 python tools/bench_straighten.py [--reps 10] [--no-cpu] [--spacing a,b,c]
+--spacing: millimetres per voxel of the same 512 x 512 x 400 voxel patient (default 1,1,1); the host mirror is skipped at other spacings.
 """
 import argparse
 import ctypes
@@ -83,7 +84,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--spacing', default='1,1,1')
     args = ap.parse_args()
+    spacing = S.check_spacing([float(v) for v in args.spacing.split(',')])
+    c_spacing = (ctypes.c_double * 3)(*spacing)
     shape = (512, 512, 400)
     ct, label = synth.make_spine_patient(seed=5, shape=shape, n_vert=15, radius=(40, 30, 10), end_radius=(14, 12, 6), margin=16,
                                          curve=(20.0, 40.0))
@@ -102,7 +106,7 @@ def main():
     stats_ms = _timed(stats, args.reps)
     cents = S.vertebra_centroids(tlab)
     ids = [e['label'] for e in cents]
-    out, plan = S.straighten_patient(tct, tlab, ids, return_plan=True)
+    out, plan = S.straighten_patient(tct, tlab, ids, return_plan=True, spacing=spacing)
     knots, basis, boxes = plan['knots'], plan['basis'], plan['boxes']
     N = len(knots)
     d_knots, d_basis = torch.from_numpy(knots).to(dev), torch.from_numpy(basis).to(dev)
@@ -111,9 +115,9 @@ def main():
     pbytes = L.size('hv_straighten_presence_bytes', 128)
     pres = torch.empty(pbytes // 8, dtype=torch.int64, device=dev)
     wmin, wmax = ctypes.c_double(-300.0), ctypes.c_double(800.0)
-    sample = lambda: L.call('hv_straighten_sample', _lib.ptr(tct), 1, *st(tct), _lib.ptr(tlab), 0, *st(tlab), X, Y, Z, _lib.ptr(d_knots),  # noqa: E731
+    sample = lambda: L.call('hv_straighten_sample_sp', _lib.ptr(tct), 1, *st(tct), _lib.ptr(tlab), 0, *st(tlab), X, Y, Z, _lib.ptr(d_knots),  # noqa: E731
                             _lib.ptr(d_basis), N, 128, 128, int(plan['window']), wmin, wmax, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres),
-                            ctypes.c_size_t(pbytes), _lib.stream())
+                            ctypes.c_size_t(pbytes), c_spacing, _lib.stream())
     sample_ms = _timed(sample, args.reps)
     V = len(ids)
     d_boxes = torch.tensor(boxes, dtype=torch.int32).to(dev)
@@ -123,14 +127,14 @@ def main():
                           _lib.ptr(pres), _lib.ptr(d_boxes), V, 256, 256, 64, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
     crop_ms = _timed(crop, args.reps)
     assert torch.equal(ct_out, torch.stack([out[v][0] for v in ids])) and torch.equal(lab_out, torch.stack([out[v][1] for v in ids]))
-    patient_ms = _timed(lambda: S.straighten_patient(tct, tlab, ids), args.reps)
+    patient_ms = _timed(lambda: S.straighten_patient(tct, tlab, ids, spacing=spacing), args.reps)
     read = ct.nbytes + label.nbytes
-    res = {'shape': list(shape), 'vertebrae': V, 'planes': N, 'stats_ms': round(stats_ms, 4),
+    res = {'shape': list(shape), 'spacing': list(spacing), 'vertebrae': V, 'planes': N, 'stats_ms': round(stats_ms, 4),
            'stats_GBps': round(read / stats_ms / 1e6, 1), 'stats_of_copy': round(read / stats_ms / 1e9 / COPY_TBPS, 3),
            'sample_ms': round(sample_ms, 4), 'samples_per_s': float('%.4g' % (N * 128 * 128 / sample_ms * 1e3)), 'crop_ms': round(crop_ms, 4),
            'crop_out_MB': round(V * 256 * 256 * 64 * 9 / 1e6, 1), 'patient_ms': round(patient_ms, 3), 'h2d_ct_ms': round(h2d_ct, 3),
            'h2d_label_ms': round(h2d_lab, 3)}
-    if not args.no_cpu:
+    if not args.no_cpu and spacing == (1.0, 1.0, 1.0):
         res['cpu_mirror_s'] = round(cpu_mirror(ct, label, ids), 3)
     res['device'] = torch.cuda.get_device_name(0)
     print(json.dumps(res))
