@@ -2,7 +2,10 @@
 pinned against oracle/restate.py and torch autograd by tests/test_attention_ref_cpu.py.  Layouts are the device's: feature maps are [B][H][W][C], patch
 tables [B][L][taps][C] with L = (H/2)(W/2) patch positions in row order, score matrices [B][p][l] (p: foreground position, l: background patch).
 
-The second half holds the soft-max test rows (inputs, fp64 expectation, element bound, decided rows): tests/test_attention_gpu.py compares the kernels
+The batched NT GEMM, the fold and the Gram-route stages (csrc/bgemm.hip, csrc/attention_gram.hip) follow, with the rows and cases that
+tests/test_attention_gemm_gpu.py runs them on.
+
+The last part holds the soft-max test rows (inputs, fp64 expectation, element bound, decided rows): tests/test_attention_gpu.py compares the kernels
 with them and tests/test_attention_ref_cpu.py checks, without a GPU, that the chosen seeds leave at most 1 % of the rows' arg-max undecided."""
 import functools
 import math
@@ -135,6 +138,169 @@ def patches_backward(dwp, wp, coef, H, W):
 
 def transpose(x):
     return x.transpose(1, 2).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------- batched GEMM, fold, Gram route
+def bgemm_nt(A, B, alpha=1.0, colscale=None, b_split=0):
+    """C[b][m][n] = alpha cs[b][n] sum_k A[b][m][k] B'[b][n][k] for A [batch][M][K], B [batch][N][K] as stored: with b_split the logical row
+    n = t b_split + c of B' is the stored row c (N / b_split) + t.  -> C and S = |alpha cs| sum_k |A B'| (what the rounding error of any summation
+    order is bounded by), both fp64."""
+    A, B = A.double(), B.double()
+    batch, N, K = B.shape
+    if b_split:
+        n = torch.arange(N)
+        B = B[:, (n % b_split) * (N // b_split) + n // b_split, :]
+    cs = torch.full((batch, N), float(alpha), dtype=F64)
+    if colscale is not None:
+        cs = cs * colscale.double()
+    C = torch.einsum('bmk,bnk->bmn', A, B) * cs.unsqueeze(1)
+    S = torch.einsum('bmk,bnk->bmn', A.abs(), B.abs()) * cs.abs().unsqueeze(1)
+    return C, S
+
+
+def fold4(src, H, W, alpha=1.0):
+    """Overlap-add of 4x4 stride-2 pad-1 patches src [B][L][16][C] (L = (H/2)(W/2), taps in row order) -> alpha times the sum per pixel, [B][H][W][C]:
+    the adjoint of raw_patches4."""
+    return alpha * _unwindows(src.double(), 4, 2, H, W)
+
+
+def gram_down(f):
+    """f [B][H][W][C] -> fd [B][h][w][C] (nearest x1/2), fdT [B][C][L] and q [B][L] = |fd|^2 per pixel."""
+    fd = down(f)
+    flat = fd.flatten(1, 2)
+    return fd, flat.transpose(1, 2).contiguous(), flat.pow(2).sum(dim=2)
+
+
+def gram_scores(fd):
+    """The matching scores from the patch definition, fd [B][h][w][C] -> S0 [B][p][l] = rnorm[l] <wp[p], wp[l]>, the element bound
+    rnorm[l] <|wp[p]|, |wp[l]|>, norm, rnorm [B][L]."""
+    wp, _ = patches3(fd.double())
+    norm, rnorm = norms(wp)
+    w = wp.flatten(2)
+    S0 = torch.einsum('bpk,blk->bpl', w, w) * rnorm.unsqueeze(1)
+    Sb = torch.einsum('bpk,blk->bpl', w.abs(), w.abs()) * rnorm.unsqueeze(1)
+    return S0, Sb, norm, rnorm
+
+
+def box_diag(G, h, w):
+    """E[a][b] = sum over the 3x3 offsets t of G[a + t][b + t] for G [B][L][L] over an h x w grid; terms with a + t or b + t outside the grid dropped."""
+    B = G.shape[0]
+    Gp = F.pad(G.reshape(B, h, w, h, w), (1, 1, 1, 1, 1, 1, 1, 1))
+    E = torch.zeros(B, h, w, h, w, dtype=G.dtype)
+    for ty in range(3):
+        for tx in range(3):
+            E += Gp[:, ty:ty + h, tx:tx + w, ty:ty + h, tx:tx + w]
+    return E.reshape(B, h * w, h * w)
+
+
+def gram_scores_box(fd):
+    """gram_scores by the box-filter identity <wp[p], wp[l]> = sum_t <fd[p + t], fd[l + t]> (K = C instead of 9C; for the large cases): the same four
+    results.  The bound's identity holds with |fd| in place of fd."""
+    fd = fd.double()
+    B, h, w, C = fd.shape
+    x = fd.flatten(1, 2)
+    norm, rnorm = norms(patches3(fd)[0])
+    S0 = box_diag(x @ x.transpose(1, 2), h, w) * rnorm.unsqueeze(1)
+    Sb = box_diag(x.abs() @ x.abs().transpose(1, 2), h, w) * rnorm.unsqueeze(1)
+    return S0, Sb, norm, rnorm
+
+
+def coef_box(coef, h, w):
+    """[B][L] -> [B][h][w][1]: sum_t coef[a - t], the coefficient of every patch that holds pixel a."""
+    B, L = coef.shape
+    return _unwindows(coef.reshape(B, L, 1, 1).expand(B, L, 9, 1), 3, 1, h, w)
+
+
+def gram_backward(Gs, fd, coef):
+    """d fd [B][h][w][C] = col2im(Gs wp) + (sum_t coef[a - t]) fd[a]: the K = 9C route written out (hv_ca_gram_backward takes it through E = box_diag(Gs))."""
+    fd, Gs = fd.double(), Gs.double()
+    B, h, w, C = fd.shape
+    wp, _ = patches3(fd)
+    dwp = torch.einsum('bij,bjk->bik', Gs, wp.flatten(2)).reshape(B, h * w, 9, C)
+    return _unwindows(dwp, 3, 1, h, w) + coef_box(coef.double(), h, w) * fd
+
+
+def gram_backward_bound(Gs, fd, coef):
+    """sum_b |E[a][b] fd[b]| + |sum_t coef[a - t]| |fd[a]|: the L + 1 terms of the Gram form's sum per element, [B][h][w][C]."""
+    fd = fd.double()
+    B, h, w, C = fd.shape
+    E = box_diag(Gs.double(), h, w)
+    return (E.abs() @ fd.flatten(1, 2).abs()).reshape(B, h, w, C) + coef_box(coef.double(), h, w).abs() * fd.abs()
+
+
+def gram_lg(B, h):
+    """Grid rows of l per workgroup, by hv_ca_gram_scores' rule (csrc/attention_gram.hip): 16, halved down to 4 while fewer than 1024 workgroups result."""
+    lg = 16
+    while lg > 4 and B * h * ((h + lg - 1) // lg) < 1024:
+        lg >>= 1
+    return (lg + 3) // 4 * 4
+
+
+def draw_f16(shape, gen):
+    """Values of magnitude 0.5 .. 1.5 with random sign, rounded to fp16 (returned as fp32): no term of a sum is negligible beside the others."""
+    v = (torch.rand(shape, generator=gen) + 0.5) * (torch.randint(0, 2, shape, generator=gen) * 2 - 1)
+    return v.half().float()
+
+
+def draw_eighths(shape, gen):
+    """Multiples of 1/8 in [-1/2, 1/2]: sums of a few of them are exact in fp32 and fp16."""
+    return torch.randint(-4, 5, shape, generator=gen).float() / 8
+
+
+def tol_sum(S, nterms, ref=None):
+    """(nterms + 2) u S: the worst case of an fp32 sum of nterms exact products in any order; 2^-11 |ref| + 2^-25 more for a result stored as fp16."""
+    t = (nterms + 2) * U * S
+    return t if ref is None else t + 2.0 ** -11 * ref.abs() + 2.0 ** -25
+
+
+def one_term_shows(bound, S, nterms):
+    """The bound lies below 1/20 of the mean |term| = S / nterms wherever the sum has a term at all: a dropped or doubled term cannot hide in it."""
+    m = S > 0
+    return bool((bound[m] < S[m] / (20.0 * nterms)).all())
+
+
+# name: (M, N, K, batch, alpha, column scale, b_split, padded leading dimensions and batch strides)
+GEMM_ROWS = {
+    'one_kstep': (16, 4, 32, 1, 1.0, False, 0, False),
+    'ragged_bn64': (129, 132, 96, 3, 0.25, True, 4, True),
+    'swizzle': (128, 128, 64, 8, 1.0, False, 32, False),
+    'plain_bn128': (130, 256, 64, 9, -0.5, True, 0, True),
+    'dma_128_tiles': (256, 256, 64, 128, 1.0, False, 0, False),
+    'dma_ragged': (257, 260, 128, 32, 0.5, False, 0, False),
+    'dma_one_tile_short': (256, 256, 64, 127, 1.0, False, 0, False),
+    'dma_k96': (256, 256, 96, 128, 1.0, False, 0, False),
+    'dma_split_scaled_padded': (256, 512, 64, 65, 0.25, True, 4, True),
+}
+
+
+def gemm_takes_dma(M, N, K, batch):
+    """bgemm_impl's rule for fp16 x fp16 operands (csrc/bgemm.hip)."""
+    t256 = -(-M // 256) * -(-N // 256) * batch
+    return K % 64 == 0 and M >= 256 and N >= 256 and t256 >= 128
+
+
+@functools.lru_cache(maxsize=1)
+def gemm_case(name):
+    M, N, K, batch, alpha, scaled, split, padded = GEMM_ROWS[name]
+    gen = torch.Generator().manual_seed(7000 + sorted(GEMM_ROWS).index(name))
+    A, B = draw_f16((batch, M, K), gen), draw_f16((batch, N, K), gen)
+    cs = (torch.rand(batch, N, generator=gen) + 0.5) if scaled else None
+    ref, S = bgemm_nt(A, B, alpha, cs, split)
+    return dict(A=A, B=B, cs=cs, ref=ref, S=S)
+
+
+FOLD_SHAPES = [(2, 4, 6, 8), (1, 2, 2, 16), (3, 6, 4, 24), (2, 4, 6, 12)]
+FOLD_ALPHA = 0.25
+
+
+@functools.lru_cache(maxsize=4)
+def fold_case(shape):
+    """src [B][L][16][C], old [B][H][W][C] (fp16 values) -> for accumulate 0 / 1: the fp64 result, the sum of its |terms| and their number."""
+    B, H, W, C = shape
+    gen = torch.Generator().manual_seed(8000 + FOLD_SHAPES.index(shape))
+    src, old = draw_f16((B, (H // 2) * (W // 2), 16, C), gen), draw_f16((B, H, W, C), gen)
+    f, fa = fold4(src, H, W, FOLD_ALPHA), fold4(src.abs(), H, W, FOLD_ALPHA)
+    return dict(src=src, old=old, ref=(f, old.double() + f), S=(fa, old.double().abs() + fa), nterms=(4, 5))
 
 
 # ---------------------------------------------------------------------------------------------------------------- the block, composed

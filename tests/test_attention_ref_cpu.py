@@ -217,3 +217,136 @@ def test_flow_to_image_reproduces_the_flow_of_fixture_g2():
     up = g['flow'].shape[2] // hh
     flow = img.permute(0, 3, 1, 2).repeat_interleave(up, dim=2).repeat_interleave(up, dim=3)
     assert flow.shape == g['flow'].shape and float((flow - g['flow']).abs().max()) < 0.5 / 255
+
+
+# ---------------------------------------------------------------------------------------------------------------- batched GEMM, fold, Gram route
+@pytest.mark.parametrize('split', [0, 4, 3])
+def test_bgemm_reference_matches_bmm_on_explicitly_permuted_rows(split):
+    gen = torch.Generator().manual_seed(21 + split)
+    bt, M, N, K = 3, 5, 12, 7
+    A = torch.randn(bt, M, K, generator=gen, dtype=F64)
+    Bm = torch.randn(bt, N, K, generator=gen, dtype=F64)
+    cs = torch.randn(bt, N, generator=gen, dtype=F64)
+    Bl = Bm
+    if split:       # stored row c (N / split) + t is the logical row t split + c
+        Bl = torch.empty_like(Bm)
+        for c in range(split):
+            for t in range(N // split):
+                Bl[:, t * split + c] = Bm[:, c * (N // split) + t]
+    for alpha, scale in ((1.0, None), (-0.25, cs)):
+        Cr, S = AR.bgemm_nt(A, Bm, alpha, scale, split)
+        want = alpha * torch.bmm(A, Bl.transpose(1, 2)) * (1 if scale is None else scale[:, None, :])
+        close(Cr, want, 'C')
+        close(S, abs(alpha) * torch.bmm(A.abs(), Bl.abs().transpose(1, 2)) * (1 if scale is None else scale.abs()[:, None, :]), 'S')
+        assert bool((S >= Cr.abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize('HH,WW', [(4, 6), (6, 4), (2, 2), (8, 8)])
+def test_fold_reference_is_F_fold_and_the_adjoint_of_the_raw_patches(HH, WW):
+    gen = torch.Generator().manual_seed(HH * 16 + WW)
+    LL = (HH // 2) * (WW // 2)
+    src = torch.randn(B, LL, 16, C, generator=gen, dtype=F64)
+    cols = src.permute(0, 3, 2, 1).reshape(B, C * 16, LL)                  # F.fold wants [b][c * 16 + tap][p]
+    want = 0.25 * F.fold(cols, (HH, WW), kernel_size=4, stride=2, padding=1)
+    close(AR.fold4(src, HH, WW, 0.25), nhwc(want), 'fold')
+    f = torch.randn(B, HH, WW, C, generator=gen, dtype=F64)
+    raw, _ = AR.raw_patches4(f)
+    lhs, rhs = (AR.fold4(src, HH, WW) * f).sum().item(), (src * raw).sum().item()
+    assert abs(lhs - rhs) <= 1e-12 * (src.abs() * raw.abs()).sum().item()
+
+
+def test_gram_down_and_both_score_references_agree_on_a_non_square_map():
+    f, _, _ = draw(13)
+    f[:, 0:6, 0:6] = 0                                                    # four all-zero patches: the floor
+    fd, fdT, q = AR.gram_down(f)
+    close(fd, AR.down(f), 'fd')
+    assert fdT.shape == (B, C, L) and fdT.is_contiguous()
+    close(fdT, fd.reshape(B, L, C).transpose(1, 2), 'fdT')
+    close(q, (fd.reshape(B, L, C) ** 2).sum(dim=2), 'q')
+    S0, Sb, norm, rnorm = AR.gram_scores(fd)
+    wp, _ = AR.patches3(fd)
+    n2, r2 = AR.norms(wp)
+    close(S0, AR.scores(wp, r2), 'S0 against scores()')
+    close(S0, restate_scores(nchw(fd)), 'S0 against the restatement')
+    close(norm, n2, 'norm')
+    close(rnorm, r2, 'rnorm')
+    assert norm[0, 0] == 1e-4 and bool((S0[:, :, 0] == 0).all()) and bool((Sb >= S0.abs() * (1 - 1e-12)).all())
+    T0, Tb, n3, r3 = AR.gram_scores_box(fd)
+    close(T0, S0, 'box-filter S0')
+    close(Tb, Sb, 'box-filter bound')
+    close(n3, norm, 'box-filter norm')
+    close(r3, rnorm, 'box-filter rnorm')
+
+
+def test_gram_backward_reference_matches_autograd_and_the_explicit_box_form():
+    f, _, gen = draw(17)
+    fd = AR.down(f)
+    # symmetric Gs: autograd of sum 1/2 Gs[p][l] <wp[p], wp[l]>
+    Gs = torch.randn(B, L, L, generator=gen, dtype=F64)
+    Gs = Gs + Gs.transpose(1, 2)
+    fa = fd.clone().requires_grad_(True)
+    wpa = AR.patches3(fa)[0].flatten(2)
+    (0.5 * Gs * torch.einsum('bpk,blk->bpl', wpa, wpa)).sum().backward()
+    zero = torch.zeros(B, L, dtype=F64)
+    close(AR.gram_backward(Gs, fd, zero), fa.grad, 'd fd, symmetric Gs')
+    # non-symmetric Gs and a coefficient: E[a][b] = sum_t Gs[a + t][b + t], every term written out
+    Gn = torch.randn(B, L, L, generator=gen, dtype=F64)
+    coef = torch.randn(B, L, generator=gen, dtype=F64)
+    E = torch.zeros(B, L, L, dtype=F64)
+    cb = torch.zeros(B, h, w, dtype=F64)
+    for ay in range(h):
+        for ax in range(w):
+            for ty in (-1, 0, 1):
+                for tx in (-1, 0, 1):
+                    if 0 <= ay - ty < h and 0 <= ax - tx < w:             # every patch a - t inside the grid holds pixel a
+                        cb[:, ay, ax] += coef[:, (ay - ty) * w + ax - tx]
+                    if not (0 <= ay + ty < h and 0 <= ax + tx < w):
+                        continue
+                    for by in range(h):
+                        for bx in range(w):
+                            if 0 <= by + ty < h and 0 <= bx + tx < w:
+                                E[:, ay * w + ax, by * w + bx] += Gn[:, (ay + ty) * w + ax + tx, (by + ty) * w + bx + tx]
+    close(AR.box_diag(Gn, h, w), E, 'E')
+    close(AR.coef_box(coef, h, w)[..., 0], cb, 'coefficient sum')
+    want = (E @ fd.reshape(B, L, C)).reshape(B, h, w, C) + cb.unsqueeze(3) * fd
+    got = AR.gram_backward(Gn, fd, coef)
+    close(got, want, 'd fd, non-symmetric Gs')
+    # the same through the patch-table pieces that test_score_gradient_pieces... pins against autograd
+    wp, _ = AR.patches3(fd)
+    dwp = torch.einsum('bij,bjk->bik', Gn, wp.flatten(2))
+    close(got, AR.patches_backward(dwp, wp, coef, H, W)[:, ::2, ::2], 'd fd against patches_backward')
+    assert (got - AR.gram_backward(Gn.transpose(1, 2), fd, coef)).abs().max() > 1e-3      # the transposed Gs is another result
+    bound = AR.gram_backward_bound(Gn, fd, coef)
+    assert bool((bound >= got.abs() * (1 - 1e-12)).all())
+
+
+def test_gram_lg_rule_and_the_exact_draws():
+    assert [AR.gram_lg(*c) for c in ((1, 1), (2, 5), (3, 12), (2, 16), (2, 32), (2, 64))] == [4, 4, 4, 4, 4, 8]
+    assert [AR.gram_lg(*c) for c in ((31, 17), (16, 32), (57, 9))] == [16, 16, 8]
+    gen = torch.Generator().manual_seed(1)
+    v = AR.draw_f16((1000,), gen)
+    assert torch.equal(v, v.half().float()) and 0.5 <= v.abs().min().item() and v.abs().max().item() <= 1.5 and 0.3 < (v > 0).float().mean().item() < 0.7
+    e = AR.draw_eighths((1000,), gen)
+    assert torch.equal(e * 8, (e * 8).round()) and e.min().item() == -0.5 and e.max().item() == 0.5
+
+
+@pytest.mark.parametrize('name', list(AR.GEMM_ROWS))
+def test_gemm_rows_show_one_term_in_both_storage_types(name):
+    """By the reference alone, for the seeds of tests/test_attention_gemm_gpu.py: the element bound (fp32 and fp16 result) lies below 1/20 of the mean
+    |term| everywhere, and the results stay in fp16's normal range.  (The fp32 bound is (K + 2) u S against S / 20K: true whenever 20 K (K + 2) < 2^24,
+    as for the Gram kernels' K = 576 and L + 1 <= 513; the fp16 share depends on the data.)"""
+    M, N, K, batch = AR.GEMM_ROWS[name][:4]
+    e = AR.gemm_case(name)
+    assert e['ref'].shape == (batch, M, N) and bool((e['S'] > 0).all())
+    assert AR.one_term_shows(AR.tol_sum(e['S'], K), e['S'], K) and AR.one_term_shows(AR.tol_sum(e['S'], K, e['ref']), e['S'], K)
+    assert e['ref'].abs().max().item() < 6e4 and (e['ref'].abs() < 2.0 ** -14).double().mean().item() < 1e-3
+    assert 20 * 576 * 578 < 2 ** 24 and 20 * 514 * 515 < 2 ** 24
+
+
+@pytest.mark.parametrize('shape', AR.FOLD_SHAPES)
+def test_fold_cases_show_one_term_in_both_storage_types(shape):
+    e = AR.fold_case(shape)
+    for acc in (0, 1):
+        ref, S, n = e['ref'][acc], e['S'][acc], e['nterms'][acc]
+        assert bool((S > 0).all()) and AR.one_term_shows(AR.tol_sum(S, n), S, n) and AR.one_term_shows(AR.tol_sum(S, n, ref), S, n)
+    assert (e['ref'][1] - e['ref'][0]).abs().min().item() >= 0.5      # accumulate adds a non-zero map

@@ -301,7 +301,9 @@ def test_module_api_backward_in_fp16_storage_mode_scales_its_gradients():
 def test_batched_nt_gemm_against_torch(M, N, K, batch, scaled, split):
     """hv_bgemm_nt (the fp16 mode's attention contractions): operands rounded to fp16, fp32 accumulation -- against torch on the same rounded
     operands in fp64; ragged tile edges, the column scale, the XCD batch swizzle (batch % 8 == 0) and the plain mapping.  The fp16 x fp16 form of the
-    large shapes runs in bgemm_dma_kernel (256 x 256 tiles on an LDS-DMA ring) and must give the bits of the register-staged kernel (same k order)."""
+    large shapes runs in bgemm_dma_kernel (256 x 256 tiles on an LDS-DMA ring) and must give the bits of the register-staged kernel (same k order).
+    Padded leading dimensions and batch strides, the fp16 C of hv_bgemm_nt_h and the LDS-DMA kernel's dispatch border are held to fp64 element
+    bounds in tests/test_attention_gemm_gpu.py."""
     import ctypes
     from hvgan import lib
     dev = torch.device('cuda:0')
