@@ -97,10 +97,17 @@ __global__ __launch_bounds__(1024) void slice_components_kernel(const T* __restr
 extern "C" size_t hv_slice_components_workspace_bytes(int S, int H, int W) {
     return (size_t)2 * S * H * W * sizeof(int);
 }
+// HV_OK, or the status to return before any launch.  Pixel indices are ints; the row sum (s_sum, the per-thread rsum and stats[3] are ints) of a full slice
+// is W * (0 + 1 + ... + (H - 1)) = H * W * (H - 1) / 2, which must not pass INT_MAX: 65536 x 1 is the tallest column accepted.
+static int components_shape(int H, int W) {
+    if ((long long)H * W > (1 << 24)) return HV_ERR_UNSUPPORTED;
+    if ((long long)H * W * (H - 1) / 2 > 2147483647ll) return HV_ERR_UNSUPPORTED;
+    return HV_OK;
+}
 extern "C" int hv_slice_components(const float* label, int S, int H, int W, float value, int min_size, int* stats, void* workspace,
                                    size_t workspace_bytes, void* stream) {
     if (!label || !stats || S <= 0 || H <= 0 || W <= 0) return HV_ERR_ARG;
-    if ((long long)H * W > (1 << 24)) return HV_ERR_UNSUPPORTED;     // row sums stay below 2^31
+    if (components_shape(H, W) != HV_OK) return HV_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < hv_slice_components_workspace_bytes(S, H, W)) return HV_ERR_WORKSPACE;
     int* L = reinterpret_cast<int*>(workspace);
     hipLaunchKernelGGL(slice_components_kernel<float>, dim3(S), dim3(1024), 0, (hipStream_t)stream, label, H, W, value, min_size, L,
@@ -111,7 +118,7 @@ extern "C" int hv_slice_components(const float* label, int S, int H, int W, floa
 extern "C" int hv_slice_components_u8(const void* plane, int S, int H, int W, int value, int min_size, int* stats, void* filtered,
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!plane || !stats || S <= 0 || H <= 0 || W <= 0 || value <= 0 || value > 255) return HV_ERR_ARG;
-    if ((long long)H * W > (1 << 24)) return HV_ERR_UNSUPPORTED;
+    if (components_shape(H, W) != HV_OK) return HV_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < hv_slice_components_workspace_bytes(S, H, W)) return HV_ERR_WORKSPACE;
     int* L = reinterpret_cast<int*>(workspace);
     hipLaunchKernelGGL(slice_components_kernel<unsigned char>, dim3(S), dim3(1024), 0, (hipStream_t)stream, (const unsigned char*)plane, H, W,

@@ -636,7 +636,8 @@ int hv_assemble_batch(const hv_assemble_item* d_items, int B, int H, int W, floa
 /* ---- slice preparation of the inference driver on the device (reference eval_3d_sagittal_twostage.py:15-30,46-98; 8f rows f1 / f2) ----
  * hv_slice_components: per slice s of label [S][H][W]: 8-connected components of (label == value), components with fewer than min_size
  * pixels dropped (remove_small_connected_components); stats[s] = {pixel count, first row, last row, sum of row indices} of what remains
- * (count 0: first row -1).  workspace: hv_slice_components_workspace_bytes(S, H, W) bytes.
+ * (count 0: first row -1).  workspace: hv_slice_components_workspace_bytes(S, H, W) bytes.  HV_ERR_UNSUPPORTED, before any launch, unless
+ * H * W <= 2^24 and H * W * (H - 1) / 2 <= INT_MAX (the row sum of a full slice is an int); the same for hv_slice_components_u8.
  * hv_infer_prepare: from those stats the rows run_model works with (x1, x2, height; the 40-row window around the mean row when the vertebra
  * is taller than maxheight) and the generator's four input planes [S][1][H][W]: ct_masked / cam = uint8-quantised slice re-stacked around the
  * band [min_x, max_x), ori_ct = the quantised slice, mask = rows [min_x, max_x] -- ToTensor / Normalize applied.  ct / cam: [S][H][W] float32 in
