@@ -13,6 +13,9 @@
 //   svm_vote_kernel<F>       one workgroup per (fold, grid point): pairwise decisions w.x - b of every val row, libsvm's vote, the prediction,
 //                            the K x K confusion matrix (LDS integer atomics: order-free), the four scores by one lane.
 //   svm_fold_stats_kernel    one thread per (grid point, score): mean and population variance over the five folds.
+//   svm_fit_kernel / svm_predict_kernel / svm_features_kernel   the same grader fitted once on chosen rows, kept and applied to new rows (further
+//                            down).  The staging, the solver and the row vote are device functions (svm_stage, svm_solve, svm_vote_row) that both
+//                            families call: there is one body of each, so the two families give the same bits.
 //
 // Block size: ONE wave.  An SMO iteration is two dependent arg-reductions over the pair's rows and a two-variable update, about 40 flops per
 // row (F <= 6): there is no work to hide a workgroup barrier behind, and with one wave there is none -- a barrier of a workgroup that fits a
@@ -138,6 +141,195 @@ __device__ __forceinline__ bool svm_plan_ok(const SvmArgs& A) {
     return A.hdr[0] == SVM_MAGIC && A.hdr[1] == A.M && A.hdr[2] == A.Mv && A.hdr[3] == A.K;
 }
 
+// Staging of one pair's problem by one wave (svm_smo_kernel and svm_fit_kernel): the rows k of X [M][F] with sel[k] != skip and class ca, then those
+// of class cb (libsvm groups the rows by class: the lower class first, each class in row order), scaled, into the LDS arrays of CAP rows.
+// -> the number of rows that were selected (rows past CAP are counted, not stored: the caller refuses n > CAP).
+template <int F, int CAP>
+__device__ __forceinline__ int svm_stage(const double* __restrict__ X, int M, const int* __restrict__ y, const int* __restrict__ sel, int skip, int ca,
+                                         int cb, double bound_a, double bound_b, const double (&mean)[F], const double (&scale)[F], int lane,
+                                         double* sx, double* sa, double* sg, double* sc, double* sq) {
+    int n = 0;
+    for (int side = 0; side < 2; ++side) {
+        const int cls = side ? cb : ca;
+        const double bound = side ? bound_b * -1.0 : bound_a * 1.0;
+        for (int base = 0; base < M; base += 64) {
+            const int k = base + lane;
+            const bool take = k < M && sel[k] != skip && y[k] == cls;
+            const unsigned long long mask = __ballot(take);
+            const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+            if (take && pos < CAP) {
+                double q = 0.0;
+#pragma unroll
+                for (int c = 0; c < F; ++c) {
+                    const double v = (X[(long long)k * F + c] - mean[c]) / scale[c];
+                    sx[c * CAP + pos] = v;
+                    q += v * v;
+                }
+                sa[pos] = 0.0;
+                sg[pos] = -1.0;
+                sc[pos] = bound;
+                sq[pos] = q;
+            }
+            n += __popcll(mask);
+        }
+    }
+    return n;
+}
+
+// THE solver body (svm_smo_kernel and svm_fit_kernel): SMO over the n staged rows by one wave, then calculate_rho.  w leaves as the primal weights,
+// gap as the final KKT gap, rho as libsvm's rho, iter / nsv / status as info reports them.
+template <int F, int CAP>
+__device__ __forceinline__ void svm_solve(double* sx, double* sa, double* sg, const double* sc, const double* sq, int n, int lane, double tol,
+                                          int max_iter, double (&w)[F], double& gap, double& rho, int& iter, int& nsv, int& status) {
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < F; ++c) w[c] = 0.0;
+    const double inf = __builtin_inf();
+    for (;;) {
+        // gradient of every row from w, the most violating row of I_up and the largest y G of I_low
+        double gmax = -inf, gmax2 = -inf;
+        int gi = 0x7fffffff;
+        for (int k = lane; k < n; k += 64) {
+            const double cs = sc[k], a = sa[k], C = fabs(cs);
+            const bool pos = cs > 0.0;
+            double d = 0.0;
+#pragma unroll
+            for (int c = 0; c < F; ++c) d += w[c] * sx[c * CAP + k];
+            const double yg = d - (pos ? 1.0 : -1.0);          // y G = w.x - y
+            sg[k] = pos ? yg : -yg;
+            const bool up = pos ? a < C : a > 0.0, low = pos ? a > 0.0 : a < C;
+            if (up && -yg > gmax) { gmax = -yg; gi = k; }
+            if (low && yg > gmax2) gmax2 = yg;
+        }
+        svm_wave_argmax(gmax, gi);
+        gmax2 = svm_wave_max(gmax2);
+        gap = gmax + gmax2;
+        if (gi == 0x7fffffff || !(gap > tol)) { status = HV_SVM_CONVERGED; break; }
+        if (iter >= max_iter) { status = HV_SVM_MAX_ITER; break; }
+        __syncthreads();
+        const int i = gi;
+        double xi[F];
+#pragma unroll
+        for (int c = 0; c < F; ++c) xi[c] = sx[c * CAP + i];
+        const double qi = sq[i];
+        // second variable: the row of I_low with the largest second-order decrease of the objective
+        double best = -inf;
+        int bj = 0x7fffffff;
+        for (int k = lane; k < n; k += 64) {
+            const double cs = sc[k], a = sa[k], C = fabs(cs);
+            const bool pos = cs > 0.0;
+            const bool low = pos ? a > 0.0 : a < C;
+            const double diff = gmax + (pos ? sg[k] : -sg[k]);
+            if (low && diff > 0.0) {
+                double kij = 0.0;
+#pragma unroll
+                for (int c = 0; c < F; ++c) kij += xi[c] * sx[c * CAP + k];
+                double quad = qi + sq[k] - 2.0 * kij;
+                if (!(quad > 0.0)) quad = SVM_TAU;
+                const double gain = diff * diff / quad;
+                if (gain > best) { best = gain; bj = k; }
+            }
+        }
+        svm_wave_argmax(best, bj);
+        if (bj == 0x7fffffff) { status = HV_SVM_CONVERGED; break; }
+        const int j = bj;
+        double xj[F], kij = 0.0;
+#pragma unroll
+        for (int c = 0; c < F; ++c) { xj[c] = sx[c * CAP + j]; kij += xi[c] * xj[c]; }
+        const double ci = fabs(sc[i]), cj = fabs(sc[j]), yi = sc[i] > 0.0 ? 1.0 : -1.0, yj = sc[j] > 0.0 ? 1.0 : -1.0;
+        const double Gi = sg[i], Gj = sg[j], oi = sa[i], oj = sa[j];
+        double ai = oi, aj = oj;
+        double quad = qi + sq[j] - 2.0 * kij;
+        if (!(quad > 0.0)) quad = SVM_TAU;
+        if (yi != yj) {
+            const double delta = (-Gi - Gj) / quad, diff = ai - aj;
+            ai += delta;
+            aj += delta;
+            if (diff > 0.0) { if (aj < 0.0) { aj = 0.0; ai = diff; } }
+            else { if (ai < 0.0) { ai = 0.0; aj = -diff; } }
+            if (diff > ci - cj) { if (ai > ci) { ai = ci; aj = ci - diff; } }
+            else { if (aj > cj) { aj = cj; ai = cj + diff; } }
+        } else {
+            const double delta = (Gi - Gj) / quad, sum = ai + aj;
+            ai -= delta;
+            aj += delta;
+            if (sum > ci) { if (ai > ci) { ai = ci; aj = sum - ci; } }
+            else { if (aj < 0.0) { aj = 0.0; ai = sum; } }
+            if (sum > cj) { if (aj > cj) { aj = cj; ai = sum - cj; } }
+            else { if (ai < 0.0) { ai = 0.0; aj = sum; } }
+        }
+        __syncthreads();          // every lane has read alpha_i / alpha_j (one wave: no instruction)
+        if (lane == 0) { sa[i] = ai; sa[j] = aj; }
+        const double ti = yi * (ai - oi), tj = yj * (aj - oj);
+#pragma unroll
+        for (int c = 0; c < F; ++c) w[c] += ti * xi[c] + tj * xj[c];
+        ++iter;
+        __syncthreads();
+    }
+    // calculate_rho: the mean of y G over the free rows, else the midpoint of the two bounds
+    double fsum = 0.0, ub = inf, lb = -inf;
+    int nfree = 0;
+    for (int k = lane; k < n; k += 64) {
+        const double cs = sc[k], a = sa[k], C = fabs(cs);
+        const bool pos = cs > 0.0;
+        const double yg = pos ? sg[k] : -sg[k];
+        if (a > 0.0) ++nsv;
+        if (a >= C) { if (pos) lb = fmax(lb, yg); else ub = fmin(ub, yg); }
+        else if (a <= 0.0) { if (pos) ub = fmin(ub, yg); else lb = fmax(lb, yg); }
+        else { ++nfree; fsum += yg; }
+    }
+    fsum = svm_wave_sum(fsum);
+    nfree = svm_wave_sum_int(nfree);
+    nsv = svm_wave_sum_int(nsv);
+    ub = svm_wave_min(ub);
+    lb = svm_wave_max(lb);
+    rho = nfree > 0 ? fsum / (double)nfree : (ub + lb) / 2.0;
+}
+
+// THE row vote (svm_vote_kernel and svm_predict_kernel), one lane per row: scale the row, the P decisions w.x_scaled summed in column order then
+// - b (NaN for a pair that was not solved), libsvm's vote -- a decision > 0 votes for the pair's lower class, the most votes win, ties to the
+// lowest class, only classes present in the training rows are candidates.  -> the class index, -1 if no class is present.  decision [P], votes [K]
+// and contrib [P][F] (w[p][c] * x_scaled[c], the very products the decision sums) are written where the pointer is not null.
+template <int F>
+__device__ __forceinline__ int svm_vote_row(const double* __restrict__ xrow, const double (&mean)[F], const double (&scale)[F], const double* sw,
+                                            const double* sb, const int* sok, const int* __restrict__ present, int K, double* __restrict__ decision,
+                                            int* __restrict__ votes_out, double* __restrict__ contrib) {
+    const double nan = __builtin_nan("");
+    double x[F];
+#pragma unroll
+    for (int c = 0; c < F; ++c) x[c] = (xrow[c] - mean[c]) / scale[c];
+    int votes[SVM_MAXK] = {0, 0, 0, 0};
+    int q = 0;
+    for (int a = 0; a < K; ++a)
+        for (int b = a + 1; b < K; ++b, ++q) {
+            double d = nan;
+            if (sok[q]) {
+                d = 0.0;
+#pragma unroll
+                for (int c = 0; c < F; ++c) {
+                    const double t = sw[q * F + c] * x[c];
+                    if (contrib) contrib[q * F + c] = t;
+                    d += t;
+                }
+                d -= sb[q];
+                const int win = d > 0.0 ? a : b;
+#pragma unroll
+                for (int v = 0; v < SVM_MAXK; ++v) votes[v] += v == win;
+            } else if (contrib) {
+#pragma unroll
+                for (int c = 0; c < F; ++c) contrib[q * F + c] = nan;
+            }
+            if (decision) decision[q] = d;
+        }
+    int best = -1, bv = -1;
+#pragma unroll
+    for (int v = 0; v < SVM_MAXK; ++v) {
+        if (v < K && present[v] && votes[v] > bv) { bv = votes[v]; best = v; }
+        if (votes_out && v < K) votes_out[v] = votes[v];
+    }
+    return best;
+}
+
 template <int F, int CAP>
 __global__ __launch_bounds__(64) void svm_smo_kernel(SvmArgs A) {
     __shared__ double sx[F * CAP];
@@ -164,139 +356,11 @@ __global__ __launch_bounds__(64) void svm_smo_kernel(SvmArgs A) {
         solve = false;
     }
     if (solve) {
-        // the pair's training rows of this fold, the lower class first (libsvm groups the rows by class), each class in row order
-        const double* X = A.xtt + (long long)g * A.M * F;
-        for (int side = 0; side < 2; ++side) {
-            const int cls = side ? cb : ca;
-            const double bound = A.bound[f * SVM_MAXK + cls] * (side ? -1.0 : 1.0);
-            for (int base = 0; base < A.M; base += 64) {
-                const int k = base + lane;
-                const bool take = k < A.M && fold[k] != f && ytt[k] == cls;
-                const unsigned long long mask = __ballot(take);
-                const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                if (take && pos < CAP) {
-                    double q = 0.0;
-#pragma unroll
-                    for (int c = 0; c < F; ++c) {
-                        const double v = (X[(long long)k * F + c] - mean[c]) / scale[c];
-                        sx[c * CAP + pos] = v;
-                        q += v * v;
-                    }
-                    sa[pos] = 0.0;
-                    sg[pos] = -1.0;
-                    sc[pos] = bound;
-                    sq[pos] = q;
-                }
-                n += __popcll(mask);
-            }
-        }
+        n = svm_stage<F, CAP>(A.xtt + (long long)g * A.M * F, A.M, ytt, fold, f, ca, cb, A.bound[f * SVM_MAXK + ca], A.bound[f * SVM_MAXK + cb], mean,
+                              scale, lane, sx, sa, sg, sc, sq);
         if (n > CAP) { status = HV_SVM_BAD_PLAN; solve = false; }
     }
-    if (solve) {
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < F; ++c) w[c] = 0.0;
-        const double inf = __builtin_inf();
-        for (;;) {
-            // gradient of every row from w, the most violating row of I_up and the largest y G of I_low
-            double gmax = -inf, gmax2 = -inf;
-            int gi = 0x7fffffff;
-            for (int k = lane; k < n; k += 64) {
-                const double cs = sc[k], a = sa[k], C = fabs(cs);
-                const bool pos = cs > 0.0;
-                double d = 0.0;
-#pragma unroll
-                for (int c = 0; c < F; ++c) d += w[c] * sx[c * CAP + k];
-                const double yg = d - (pos ? 1.0 : -1.0);          // y G = w.x - y
-                sg[k] = pos ? yg : -yg;
-                const bool up = pos ? a < C : a > 0.0, low = pos ? a > 0.0 : a < C;
-                if (up && -yg > gmax) { gmax = -yg; gi = k; }
-                if (low && yg > gmax2) gmax2 = yg;
-            }
-            svm_wave_argmax(gmax, gi);
-            gmax2 = svm_wave_max(gmax2);
-            gap = gmax + gmax2;
-            if (gi == 0x7fffffff || !(gap > A.tol)) { status = HV_SVM_CONVERGED; break; }
-            if (iter >= A.max_iter) { status = HV_SVM_MAX_ITER; break; }
-            __syncthreads();
-            const int i = gi;
-            double xi[F];
-#pragma unroll
-            for (int c = 0; c < F; ++c) xi[c] = sx[c * CAP + i];
-            const double qi = sq[i];
-            // second variable: the row of I_low with the largest second-order decrease of the objective
-            double best = -inf;
-            int bj = 0x7fffffff;
-            for (int k = lane; k < n; k += 64) {
-                const double cs = sc[k], a = sa[k], C = fabs(cs);
-                const bool pos = cs > 0.0;
-                const bool low = pos ? a > 0.0 : a < C;
-                const double diff = gmax + (pos ? sg[k] : -sg[k]);
-                if (low && diff > 0.0) {
-                    double kij = 0.0;
-#pragma unroll
-                    for (int c = 0; c < F; ++c) kij += xi[c] * sx[c * CAP + k];
-                    double quad = qi + sq[k] - 2.0 * kij;
-                    if (!(quad > 0.0)) quad = SVM_TAU;
-                    const double gain = diff * diff / quad;
-                    if (gain > best) { best = gain; bj = k; }
-                }
-            }
-            svm_wave_argmax(best, bj);
-            if (bj == 0x7fffffff) { status = HV_SVM_CONVERGED; break; }
-            const int j = bj;
-            double xj[F], kij = 0.0;
-#pragma unroll
-            for (int c = 0; c < F; ++c) { xj[c] = sx[c * CAP + j]; kij += xi[c] * xj[c]; }
-            const double ci = fabs(sc[i]), cj = fabs(sc[j]), yi = sc[i] > 0.0 ? 1.0 : -1.0, yj = sc[j] > 0.0 ? 1.0 : -1.0;
-            const double Gi = sg[i], Gj = sg[j], oi = sa[i], oj = sa[j];
-            double ai = oi, aj = oj;
-            double quad = qi + sq[j] - 2.0 * kij;
-            if (!(quad > 0.0)) quad = SVM_TAU;
-            if (yi != yj) {
-                const double delta = (-Gi - Gj) / quad, diff = ai - aj;
-                ai += delta;
-                aj += delta;
-                if (diff > 0.0) { if (aj < 0.0) { aj = 0.0; ai = diff; } }
-                else { if (ai < 0.0) { ai = 0.0; aj = -diff; } }
-                if (diff > ci - cj) { if (ai > ci) { ai = ci; aj = ci - diff; } }
-                else { if (aj > cj) { aj = cj; ai = cj + diff; } }
-            } else {
-                const double delta = (Gi - Gj) / quad, sum = ai + aj;
-                ai -= delta;
-                aj += delta;
-                if (sum > ci) { if (ai > ci) { ai = ci; aj = sum - ci; } }
-                else { if (aj < 0.0) { aj = 0.0; ai = sum; } }
-                if (sum > cj) { if (aj > cj) { aj = cj; ai = sum - cj; } }
-                else { if (ai < 0.0) { ai = 0.0; aj = sum; } }
-            }
-            __syncthreads();          // every lane has read alpha_i / alpha_j (one wave: no instruction)
-            if (lane == 0) { sa[i] = ai; sa[j] = aj; }
-            const double ti = yi * (ai - oi), tj = yj * (aj - oj);
-#pragma unroll
-            for (int c = 0; c < F; ++c) w[c] += ti * xi[c] + tj * xj[c];
-            ++iter;
-            __syncthreads();
-        }
-        // calculate_rho: the mean of y G over the free rows, else the midpoint of the two bounds
-        double fsum = 0.0, ub = inf, lb = -inf;
-        int nfree = 0;
-        for (int k = lane; k < n; k += 64) {
-            const double cs = sc[k], a = sa[k], C = fabs(cs);
-            const bool pos = cs > 0.0;
-            const double yg = pos ? sg[k] : -sg[k];
-            if (a > 0.0) ++nsv;
-            if (a >= C) { if (pos) lb = fmax(lb, yg); else ub = fmin(ub, yg); }
-            else if (a <= 0.0) { if (pos) ub = fmin(ub, yg); else lb = fmax(lb, yg); }
-            else { ++nfree; fsum += yg; }
-        }
-        fsum = svm_wave_sum(fsum);
-        nfree = svm_wave_sum_int(nfree);
-        nsv = svm_wave_sum_int(nsv);
-        ub = svm_wave_min(ub);
-        lb = svm_wave_max(lb);
-        rho = nfree > 0 ? fsum / (double)nfree : (ub + lb) / 2.0;
-    }
+    if (solve) svm_solve<F, CAP>(sx, sa, sg, sc, sq, n, lane, A.tol, A.max_iter, w, gap, rho, iter, nsv, status);
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < F; ++c) wout[c] = w[c];
@@ -339,29 +403,8 @@ __global__ __launch_bounds__(64) void svm_vote_kernel(SvmArgs A) {
     }
     const double* X = A.xval + (long long)g * A.Mv * F;
     for (int r = lane; r < A.Mv; r += 64) {
-        double x[F];
-#pragma unroll
-        for (int c = 0; c < F; ++c) x[c] = (X[(long long)r * F + c] - mean[c]) / scale[c];
-        int votes[SVM_MAXK] = {0, 0, 0, 0};
-        int q = 0;
-        for (int a = 0; a < K; ++a)
-            for (int b = a + 1; b < K; ++b, ++q) {
-                double d = nan;
-                if (sok[q]) {
-                    d = 0.0;
-#pragma unroll
-                    for (int c = 0; c < F; ++c) d += sw[q * F + c] * x[c];
-                    d -= sb[q];
-                    const int win = d > 0.0 ? a : b;
-#pragma unroll
-                    for (int v = 0; v < SVM_MAXK; ++v) votes[v] += v == win;
-                }
-                if (A.decision) A.decision[(gf * A.Mv + r) * P + q] = d;
-            }
-        int best = -1, bv = -1;
-#pragma unroll
-        for (int v = 0; v < SVM_MAXK; ++v)
-            if (v < K && present[v] && votes[v] > bv) { bv = votes[v]; best = v; }
+        const int best = svm_vote_row<F>(X + (long long)r * F, mean, scale, sw, sb, sok, present, K,
+                                         A.decision ? A.decision + (gf * A.Mv + r) * P : nullptr, nullptr, nullptr);
         A.pred[gf * A.Mv + r] = best;
         const int t = yval[r];
         if (best >= 0 && t >= 0 && t < K) atomicAdd(&scm[t * K + best], 1);
@@ -489,6 +532,224 @@ extern "C" int hv_svm_grade_grid(const double* X_tt, const double* X_val, const 
     HV_LAUNCH_CHECK();
     const long long n = (long long)G * 4;
     hipLaunchKernelGGL(svm_fold_stats_kernel, dim3(hv_cdiv(n, 64)), dim3(64), 0, s, (const double*)scores, mean, var, n);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+// ---------------------------------------------------------------- fit at a chosen setting, keep the model, grade new rows
+//   svm_fit_kernel<F, CAP>   one wave per (class pair, grid point): svm_scaler over ALL M rows of the grid point (the reference scales before it
+//                            splits), svm_stage of the rows with train[k] != 0, svm_solve -- the grading kernels' own bodies, so a fit on the rows
+//                            `fold != f` is bit for bit svm_smo_kernel's problem of fold f.  The pair-0 wave also writes the grid point's scaler.
+//   svm_predict_kernel<F>    one lane per row, 256-lane blocks, the grid point's model staged in LDS once per block; svm_vote_row per row.  No
+//                            atomics, no cross-lane traffic, no workspace: a row's outputs depend on that row and the model alone.
+//   svm_features_kernel      hv_rhlv_views_batch's records -> the feature rows, one lane per row.
+// the fit plan (hv_svm_fit_plan): bound[4] doubles, then ints: header[8] = {magic, M, K, largest pair, 0, 0, 0, 0}, present[4], y[M] (class index),
+// train[M] (0 / 1)
+#define SVM_FIT_MAGIC 0x53564d32
+#define SVM_FIT_PLAN_INTS(M) (SVM_HDR + SVM_MAXK + 2 * (size_t)(M))
+#define SVM_FIT_PLAN_BYTES(M) (SVM_MAXK * sizeof(double) + ((SVM_FIT_PLAN_INTS(M) + 1) / 2) * 2 * sizeof(int))
+
+struct SvmFitArgs {
+    const double* x; const double* bound; const int* hdr;
+    int G, M, K, P, max_iter;
+    double tol;
+    double* mean; double* scale; double* w; double* b; double* gap; int* info;
+};
+
+template <int F, int CAP>
+__global__ __launch_bounds__(64) void svm_fit_kernel(SvmFitArgs A) {
+    __shared__ double sx[F * CAP];
+    __shared__ double sa[CAP], sg[CAP], sc[CAP], sq[CAP];
+    const int lane = threadIdx.x, p = blockIdx.x, g = blockIdx.z;
+    const long long prob = (long long)g * A.P + p;
+    int ca, cb;
+    svm_pair(p, A.K, ca, cb);
+    const int* present = A.hdr + SVM_HDR;
+    const int* y = present + SVM_MAXK;
+    const int* train = y + A.M;
+    const double* X = A.x + (long long)g * A.M * F;
+    const double nan = __builtin_nan("");
+    int status = HV_SVM_CONVERGED, n = 0, iter = 0, nsv = 0;
+    double w[F], mean[F], scale[F], gap = nan, rho = nan;
+#pragma unroll
+    for (int c = 0; c < F; ++c) w[c] = nan;
+    bool solve = true, scaled = false;
+    if (!(A.hdr[0] == SVM_FIT_MAGIC && A.hdr[1] == A.M && A.hdr[2] == A.K)) { status = HV_SVM_BAD_PLAN; solve = false; }
+    else if (!(scaled = svm_scaler<F>(X, A.M, X, 0, lane, mean, scale))) { status = HV_SVM_UNUSABLE; solve = false; }
+    else if (!present[ca] || !present[cb]) { status = HV_SVM_ABSENT; solve = false; }
+    if (solve) {
+        n = svm_stage<F, CAP>(X, A.M, y, train, 0, ca, cb, A.bound[ca], A.bound[cb], mean, scale, lane, sx, sa, sg, sc, sq);
+        if (n > CAP) { status = HV_SVM_BAD_PLAN; solve = false; }
+    }
+    if (solve) svm_solve<F, CAP>(sx, sa, sg, sc, sq, n, lane, A.tol, A.max_iter, w, gap, rho, iter, nsv, status);
+    if (lane == 0) {
+        int* info = A.info + prob * 4;
+#pragma unroll
+        for (int c = 0; c < F; ++c) A.w[prob * F + c] = w[c];
+        A.b[prob] = rho;
+        A.gap[prob] = gap;
+        info[0] = iter; info[1] = status; info[2] = nsv; info[3] = n;
+        if (p == 0) {
+#pragma unroll
+            for (int c = 0; c < F; ++c) {
+                A.mean[(long long)g * F + c] = scaled ? mean[c] : nan;
+                A.scale[(long long)g * F + c] = scaled ? scale[c] : nan;
+            }
+        }
+    }
+}
+
+struct SvmPredictArgs {
+    const double* x; const int* present; const double* mean; const double* scale; const double* w; const double* b; const int* info;
+    int G, N, K, P;
+    int* pred; double* decision; int* votes; double* contrib;
+};
+
+template <int F>
+__global__ __launch_bounds__(256) void svm_predict_kernel(SvmPredictArgs A) {
+    __shared__ double sw[SVM_MAXP * F], sb[SVM_MAXP], sms[2 * F];
+    __shared__ int sok[SVM_MAXP], spresent[SVM_MAXK], sbad;
+    const int t = threadIdx.x, g = blockIdx.y, K = A.K, P = A.P;
+    if (t == 0) sbad = 0;
+    __syncthreads();
+    if (t < P * F) sw[t] = A.w[(long long)g * P * F + t];
+    if (t < 2 * F) sms[t] = t < F ? A.mean[(long long)g * F + t] : A.scale[(long long)g * F + t - F];
+    if (t < SVM_MAXK) spresent[t] = t < K ? A.present[t] : 0;
+    if (t < P) {
+        const int st = A.info[((long long)g * P + t) * 4 + 1];
+        sok[t] = st == HV_SVM_CONVERGED || st == HV_SVM_MAX_ITER;
+        sb[t] = A.b[(long long)g * P + t];
+        if (st == HV_SVM_UNUSABLE || st == HV_SVM_BAD_PLAN) sbad = 1;          // every writer stores the same value
+    }
+    __syncthreads();
+    const long long r = (long long)blockIdx.x * 256 + t;
+    if (r >= A.N) return;
+    const double nan = __builtin_nan("");
+    const double* xrow = A.x + ((long long)g * A.N + r) * F;
+    const long long row = (long long)g * A.N + r;
+    double mean[F], scale[F];
+    bool ok = !sbad;
+#pragma unroll
+    for (int c = 0; c < F; ++c) {
+        mean[c] = sms[c];
+        scale[c] = sms[F + c];
+        ok = ok && isfinite(xrow[c]) && isfinite(mean[c]) && isfinite(scale[c]);
+    }
+    double* dec = A.decision ? A.decision + row * P : nullptr;
+    int* votes = A.votes ? A.votes + row * K : nullptr;
+    double* contrib = A.contrib ? A.contrib + row * P * F : nullptr;
+    if (!ok) {
+        A.pred[row] = -1;
+        if (dec) for (int q = 0; q < P; ++q) dec[q] = nan;
+        if (votes) for (int v = 0; v < K; ++v) votes[v] = 0;
+        if (contrib) for (int q = 0; q < P * F; ++q) contrib[q] = nan;
+        return;
+    }
+    A.pred[row] = svm_vote_row<F>(xrow, mean, scale, sw, sb, sok, spresent, K, dec, votes, contrib);
+}
+
+// records [N][2][16] -> X [N][F]: columns 1..3 (Pre / Mid / Post RHLV) of view `first` (0 sagittal, 1 coronal), with F = 6 then the other view's.
+// The row is NaN where the original lacks the vertebra (sagittal [13] == 0) or the coronal script would have raised (coronal [14] != 0).
+__global__ __launch_bounds__(256) void svm_features_kernel(const double* __restrict__ records, long long N, int first, int F, double* __restrict__ X) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    const double* rec = records + r * 32;
+    const bool bad = rec[13] == 0.0 || rec[16 + 14] != 0.0;
+    const double nan = __builtin_nan("");
+    for (int c = 0; c < F; ++c) {
+        const int view = c < 3 ? first : 1 - first;
+        X[r * F + c] = bad ? nan : rec[view * 16 + 1 + c % 3];
+    }
+}
+
+extern "C" size_t hv_svm_fit_plan_bytes(int M) {
+    if (M <= 0) return 0;
+    return SVM_FIT_PLAN_BYTES(M);
+}
+
+extern "C" int hv_svm_fit_plan(const int* y, const int* train, int M, const int* classes, int K, void* plan, size_t plan_bytes, int* max_rows) {
+    if (!y || !classes || !plan || !max_rows || M <= 0) return HV_ERR_ARG;
+    if (K < 2 || K > SVM_MAXK) return HV_ERR_UNSUPPORTED;
+    if (plan_bytes < SVM_FIT_PLAN_BYTES(M)) return HV_ERR_WORKSPACE;
+    for (int c = 0; c < K; ++c)
+        if (classes[c] < 0 || (c && classes[c] <= classes[c - 1])) return HV_ERR_ARG;
+    auto index = [&](int label) { for (int c = 0; c < K; ++c) if (classes[c] == label) return c; return -1; };
+    // every check first: a refusal leaves the plan as it was
+    int count[SVM_MAXK] = {};
+    for (int k = 0; k < M; ++k) {
+        const int c = index(y[k]);
+        if (c < 0) return HV_ERR_ARG;
+        if (!train || train[k] != 0) ++count[c];
+    }
+    int n = 0, ncls = 0, largest = 0;
+    for (int c = 0; c < K; ++c) { n += count[c]; ncls += count[c] > 0; }
+    for (int c = 0; c < K; ++c)
+        for (int d = c + 1; d < K; ++d)
+            if (count[c] > 0 && count[d] > 0 && count[c] + count[d] > largest) largest = count[c] + count[d];
+    *max_rows = largest;
+    if (largest > HV_SVM_MAX_ROWS) return HV_ERR_UNSUPPORTED;
+    memset(plan, 0, SVM_FIT_PLAN_BYTES(M));
+    double* bound = (double*)plan;
+    int* hdr = (int*)(bound + SVM_MAXK);
+    int* present = hdr + SVM_HDR;
+    int* yi = present + SVM_MAXK;
+    int* tr = yi + M;
+    for (int c = 0; c < K; ++c) {
+        present[c] = count[c] > 0;
+        // class_weight='balanced' with C = 1: n_train / (n_classes_in_train * count(class))
+        bound[c] = count[c] > 0 ? (double)n / ((double)ncls * (double)count[c]) : 0.0;
+    }
+    for (int k = 0; k < M; ++k) {
+        yi[k] = index(y[k]);
+        tr[k] = !train || train[k] != 0;
+    }
+    hdr[0] = SVM_FIT_MAGIC; hdr[1] = M; hdr[2] = K; hdr[3] = largest;
+    return HV_OK;
+}
+
+extern "C" int hv_svm_fit(const double* X, const void* plan, int G, int M, int F, int K, int max_rows, double tol, int max_iter, double* mean,
+                          double* scale, double* w, double* b, double* gap, int* info, void* stream) {
+    if (!X || !plan || !mean || !scale || !w || !b || !gap || !info || G <= 0 || M <= 0 || max_rows < 0 || max_iter < 1 || !(tol > 0.0))
+        return HV_ERR_ARG;
+    if ((F != 3 && F != 6) || K < 2 || K > SVM_MAXK || max_rows > HV_SVM_MAX_ROWS || G > 65535) return HV_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    SvmFitArgs A;
+    A.x = X;
+    A.bound = (const double*)plan;
+    A.hdr = (const int*)(A.bound + SVM_MAXK);
+    A.G = G; A.M = M; A.K = K; A.P = K * (K - 1) / 2; A.max_iter = max_iter; A.tol = tol;
+    A.mean = mean; A.scale = scale; A.w = w; A.b = b; A.gap = gap; A.info = info;
+    const dim3 grid(A.P, 1, G);
+#define SVM_RUN(FF, CAP) hipLaunchKernelGGL((svm_fit_kernel<FF, CAP>), grid, dim3(64), 0, s, A)
+#define SVM_CAPS(FF) do { if (max_rows <= 256) SVM_RUN(FF, 256); else if (max_rows <= 512) SVM_RUN(FF, 512); \
+                          else if (max_rows <= 1024) SVM_RUN(FF, 1024); else SVM_RUN(FF, HV_SVM_MAX_ROWS); } while (0)
+    if (F == 3) SVM_CAPS(3); else SVM_CAPS(6);
+#undef SVM_CAPS
+#undef SVM_RUN
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+extern "C" int hv_svm_predict(const double* X, int G, int N, int F, int K, const int* present, const double* mean, const double* scale, const double* w,
+                              const double* b, const int* info, int* pred, double* decision, int* votes, double* contrib, void* stream) {
+    if (!X || !present || !mean || !scale || !w || !b || !info || !pred || G <= 0 || N <= 0) return HV_ERR_ARG;
+    if ((F != 3 && F != 6) || K < 2 || K > SVM_MAXK || G > 65535) return HV_ERR_UNSUPPORTED;
+    SvmPredictArgs A;
+    A.x = X; A.present = present; A.mean = mean; A.scale = scale; A.w = w; A.b = b; A.info = info;
+    A.G = G; A.N = N; A.K = K; A.P = K * (K - 1) / 2;
+    A.pred = pred; A.decision = decision; A.votes = votes; A.contrib = contrib;
+    const dim3 grid((unsigned)hv_cdiv((long long)N, 256), G);
+    if (F == 3) hipLaunchKernelGGL(svm_predict_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(svm_predict_kernel<6>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    HV_LAUNCH_CHECK();
+    return HV_OK;
+}
+
+extern "C" int hv_svm_features(const double* records, int N, int first_view, int F, double* X, void* stream) {
+    if (!records || !X || N <= 0 || first_view < 0 || first_view > 1) return HV_ERR_ARG;
+    if (F != 3 && F != 6) return HV_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(svm_features_kernel, dim3((unsigned)hv_cdiv((long long)N, 256)), dim3(256), 0, (hipStream_t)stream, records, (long long)N,
+                       first_view, F, X);
     HV_LAUNCH_CHECK();
     return HV_OK;
 }

@@ -17,6 +17,10 @@ ratios without the sagittal script's + 1e-6, ValueError where it takes max() of 
                                                            val-set scores) of every grid point in one launch sequence (hv_svm_grade_grid)
   stratified_folds(y)                                      the unshuffled StratifiedKFold assignment the grading uses (host, labels only)
   best_setting(sweep, grades, score='f1')                  the (length_divisor, height_threshold) with the best mean score
+  svm_fit(features, labels, train=None, ...)               the grader svm_grade_grid scores, fitted on chosen rows and KEPT (hv_svm_fit)
+  svm_predict(model, features, ...)                        grades, decisions, votes and per-feature contributions of new rows (hv_svm_predict)
+  fit_grader(sweep, labels, dataset, ...) -> Grader        the grader at the best (or a given) setting; Grader.grade_dataset goes from resident
+                                                           volumes to grades on the device with one readback (the reference stops at the fold scores)
 and what the reference's README draws from those scripts' per-column heights (the distribution of height loss over the vertebra's
 cross-section and the curve of height loss along it), left on the device:
   height_loss_map(vol_fake, vol_label, label_index, ...)       per view: loss / height maps [S, C], flags, column and slice profiles
@@ -376,6 +380,269 @@ def best_setting(sweep, grades, score='f1'):
         raise ValueError('best_setting: no usable grid point whose problems all converged')
     d, t = np.unravel_index(int(np.argmax(np.where(ok, mean, -np.inf))), mean.shape)
     return int(divs[d]), float(thrs[t])
+
+
+# ---------------------------------------------------------------- fit at a chosen setting, keep the model, grade new vertebrae
+MODEL_KEYS = ('mean', 'scale', 'w', 'b', 'gap', 'iterations', 'status', 'support', 'pair_rows', 'unusable', 'classes', 'present')
+
+
+def _layout(outs):
+    """[(name, dtype, shape)] -> (name -> byte offset, total bytes): one buffer, the 8-byte types first."""
+    offs, total = {}, 0
+    for name, dt, shape in outs:
+        offs[name] = total
+        total += int(np.prod(shape)) * np.dtype(dt).itemsize
+    return offs, total
+
+
+def _unpack(host, outs, offs, lead=None):
+    return {name: host[offs[name]:offs[name] + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape if lead is None else lead + shape[1:]).copy()
+            for name, dt, shape in outs}
+
+
+def svm_fit(features, labels, train=None, tol=1e-3, max_iter=100000):
+    """Fit the grader svm_grade_grid scores -- StandardScaler over ALL the rows given, SVC(kernel='linear', class_weight='balanced') on the rows
+    with train != 0 (default: every row) -- at every grid point, and keep the models (hv_svm_fit: the grading kernels' own scaler and solver, so
+    train = (folds != f) gives bit for bit svm_grade_grid's model of fold f).
+    features [N, G..., F], labels [N] small non-negative integer grades (at most 4 different ones), train [N] flags.  Rows that are NaN at every
+    grid point (vertebra absent) are dropped.  One upload, one launch, one readback.  ->
+      {'mean', 'scale' [G..., F], 'w' [G..., P, F], 'b', 'gap' [G..., P] (decision = w . x_scaled - b, the pairs (0,1), (0,2), ... of `classes`,
+       positive = the lower class), 'iterations', 'status', 'support', 'pair_rows' [G..., P], 'unusable' [G...] (a feature of that grid point is
+       not finite: NaN model), 'classes' [K], 'present' [K] (the class has train rows), 'rows' (the rows of `features` used)}
+    ValueError before any launch: F not 3 or 6, fewer than 2 or more than 4 grades, a class pair with more than 1792 train rows, bad tol /
+    max_iter, no rows."""
+    feats = np.asarray(features, dtype=np.float64)
+    labels = np.asarray(labels)
+    if feats.ndim < 2 or labels.shape != feats.shape[:1]:
+        raise ValueError('svm_fit: features [N, G..., F] with one label per row expected')
+    grid, F = feats.shape[1:-1], feats.shape[-1]
+    if F not in (3, 6):
+        raise ValueError('svm_fit: 3 or 6 feature columns expected, got %d' % F)
+    if not np.all(labels == np.floor(labels)) or np.any(labels < 0):
+        raise ValueError('svm_fit: labels must be non-negative integers')
+    if not (tol > 0) or int(max_iter) < 1:
+        raise ValueError('svm_fit: tol > 0 and max_iter >= 1 expected')
+    flat = feats.reshape(feats.shape[0], -1, F)
+    G = flat.shape[1]
+    if G == 0 or G > MAX_GRID:
+        raise ValueError('svm_fit: between 1 and %d grid points expected' % MAX_GRID)
+    if train is not None:
+        train = np.asarray(train)
+        if train.shape != labels.shape:
+            raise ValueError('svm_fit: one train flag per row expected')
+    rows = np.flatnonzero(~np.isnan(flat).any(axis=2).all(axis=1))
+    M = len(rows)
+    if M == 0:
+        raise ValueError('svm_fit: no usable rows')
+    y = np.ascontiguousarray(labels[rows].astype(np.int32))
+    flags = None if train is None else np.ascontiguousarray(train[rows] != 0, dtype=np.int32)
+    classes = np.unique(y).astype(np.int32)
+    K = len(classes)
+    if K < 2 or K > MAX_CLASSES:
+        raise ValueError('svm_fit: between 2 and %d different grades expected, got %d' % (MAX_CLASSES, K))
+    L = _lib.get()
+    plan = np.zeros(L.size('hv_svm_fit_plan_bytes', M), dtype=np.uint8)
+    max_rows = ctypes.c_int(0)
+    rc = L.cdll.hv_svm_fit_plan(y.ctypes.data, None if flags is None else flags.ctypes.data, M, classes.ctypes.data, K, plan.ctypes.data,
+                                ctypes.c_size_t(plan.nbytes), ctypes.byref(max_rows))
+    if rc != 0:
+        raise ValueError('svm_fit: %s' % ('a class pair has %d train rows, more than the %d the solver keeps in LDS' % (max_rows.value, MAX_PAIR_ROWS)
+                                          if max_rows.value > MAX_PAIR_ROWS else 'hv_svm_fit_plan: %s' % _lib.ERRORS.get(rc, rc)))
+    present = plan[8 * MAX_CLASSES + 32:8 * MAX_CLASSES + 32 + 4 * K].view(np.int32) != 0
+    dev = torch.device('cuda', torch.cuda.current_device())
+    x = np.ascontiguousarray(flat[rows].transpose(1, 0, 2))
+    blob = torch.from_numpy(np.concatenate([x.reshape(-1).view(np.uint8), plan])).to(dev)
+    _lib.require_gpu(blob)
+    P = K * (K - 1) // 2
+    outs = [('mean', np.float64, (G, F)), ('scale', np.float64, (G, F)), ('w', np.float64, (G, P, F)), ('b', np.float64, (G, P)),
+            ('gap', np.float64, (G, P)), ('info', np.int32, (G, P, 4))]
+    offs, total = _layout(outs)
+    buf = torch.zeros(total + 8, dtype=torch.uint8, device=dev)
+    at = lambda name: ctypes.c_void_p(buf.data_ptr() + offs[name])
+    base = blob.data_ptr()
+    L.call('hv_svm_fit', ctypes.c_void_p(base), ctypes.c_void_p(base + x.nbytes), G, M, F, K, max_rows.value, ctypes.c_double(tol), int(max_iter),
+           at('mean'), at('scale'), at('w'), at('b'), at('gap'), at('info'), _lib.stream())
+    res = _unpack(buf.cpu().numpy(), outs, offs, grid)
+    info = res.pop('info')
+    res['iterations'], res['status'], res['support'], res['pair_rows'] = (info[..., k].copy() for k in range(4))
+    res['unusable'] = np.any(res['status'] == UNUSABLE, axis=-1)
+    res.update(classes=classes, present=present.copy(), rows=rows)
+    return res
+
+
+def _model_arrays(model):
+    """-> (grid shape, F, K, P, the float64 arrays mean, scale, w, b and info [G, P, 4], present [K] as int32, classes), checked."""
+    try:
+        classes = np.asarray(model['classes'], dtype=np.int32)
+        present = np.ascontiguousarray(np.asarray(model['present']) != 0, dtype=np.int32)
+        mean, scale, w, b = (np.ascontiguousarray(model[k], dtype=np.float64) for k in ('mean', 'scale', 'w', 'b'))
+        cols = [np.asarray(model[k], dtype=np.int32) for k in ('iterations', 'status', 'support', 'pair_rows')]
+    except (KeyError, TypeError) as e:
+        raise ValueError('svm_predict: a model of svm_fit expected (%s)' % e)
+    K = len(classes)
+    P = K * (K - 1) // 2
+    if K < 2 or K > MAX_CLASSES or present.shape != (K,) or mean.ndim < 1 or mean.shape[-1] not in (3, 6):
+        raise ValueError('svm_predict: a model of 2 to %d classes and 3 or 6 feature columns expected' % MAX_CLASSES)
+    grid, F = mean.shape[:-1], mean.shape[-1]
+    if scale.shape != grid + (F,) or w.shape != grid + (P, F) or b.shape != grid + (P,) or any(c.shape != grid + (P,) for c in cols):
+        raise ValueError('svm_predict: the model arrays do not belong together')
+    G = int(np.prod(grid, dtype=np.int64))
+    if G == 0 or G > MAX_GRID:
+        raise ValueError('svm_predict: between 1 and %d grid points expected' % MAX_GRID)
+    info = np.ascontiguousarray(np.stack(cols, axis=-1).reshape(G, P, 4))
+    return grid, F, K, P, (mean, scale, w, b), info, present, classes
+
+
+def _model_blob(arrays, info, present, extra=()):
+    """The model (and `extra` float64 arrays in front) as one upload -> (byte array, offsets in upload order)."""
+    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in tuple(extra) + tuple(arrays) + (info, present)]
+    offs = np.concatenate([[0], np.cumsum([p.nbytes for p in parts])]).astype(np.int64)
+    return np.concatenate(parts), [int(o) for o in offs[:-1]]
+
+
+def svm_predict(model, features, decisions=False, contributions=False):
+    """Grade rows with a model of svm_fit (hv_svm_predict: svm_grade_grid's own scaling, decisions and libsvm vote, one lane per row).
+    features [N', G..., F] with the model's grid and F.  -> grade [G..., N'] (the grades themselves; -1 where the row has a non-finite feature, the
+    grid point's model is unusable or no class has train rows), or with decisions / contributions a dict {'grade', 'decision' [G..., N', P],
+    'votes' [G..., N', K] (decisions=True), 'contrib' [G..., N', P, F] = w[p][c] * x_scaled[c] (contributions=True): contrib summed in column order
+    minus b is the decision, bit for bit}.  One upload, one launch, one readback."""
+    grid, F, K, P, arrays, info, present, classes = _model_arrays(model)
+    feats = np.asarray(features, dtype=np.float64)
+    if feats.ndim < 2 or feats.shape[1:] != grid + (F,) or feats.shape[0] == 0:
+        raise ValueError('svm_predict: features [N, G..., F] of the model\'s grid %s and %d columns expected' % (grid, F))
+    N, G = feats.shape[0], info.shape[0]
+    L = _lib.get()
+    dev = torch.device('cuda', torch.cuda.current_device())
+    x = np.ascontiguousarray(feats.reshape(N, G, F).transpose(1, 0, 2))
+    host, o = _model_blob(arrays, info, present, extra=(x,))
+    blob = torch.from_numpy(host).to(dev)
+    _lib.require_gpu(blob)
+    outs = ([('decision', np.float64, (G, N, P))] if decisions else []) + ([('contrib', np.float64, (G, N, P, F))] if contributions else [])
+    outs += [('pred', np.int32, (G, N))] + ([('votes', np.int32, (G, N, K))] if decisions else [])
+    offs, total = _layout(outs)
+    buf = torch.zeros(total + 8, dtype=torch.uint8, device=dev)
+    at = lambda name: ctypes.c_void_p(buf.data_ptr() + offs[name]) if name in offs else None
+    src = lambda k: ctypes.c_void_p(blob.data_ptr() + o[k])
+    L.call('hv_svm_predict', src(0), G, N, F, K, src(6), src(1), src(2), src(3), src(4), src(5), at('pred'), at('decision'), at('votes'), at('contrib'),
+           _lib.stream())
+    res = _unpack(buf.cpu().numpy(), outs, offs, grid)
+    pred = res.pop('pred')
+    grade = np.where(pred >= 0, classes[np.clip(pred, 0, K - 1)], -1)
+    if not (decisions or contributions):
+        return grade
+    res['grade'] = grade
+    return res
+
+
+class Grader:
+    """The fracture grader at one setting: (length_divisor, height_threshold), the classes and the model svm_fit kept.  fit_grader builds one,
+    state_dict() / from_state_dict() carry it as plain numpy arrays and python scalars (np.savez-able; reloading gives the same bytes)."""
+
+    def __init__(self, setting, model, file1='sagittal'):
+        if file1 not in VIEWS:
+            raise ValueError("Grader: file1 must be 'sagittal' or 'coronal'")
+        self.setting = (int(setting[0]), float(setting[1]))
+        self.file1 = file1
+        self.model = {k: np.array(model[k], copy=True) for k in MODEL_KEYS}
+        grid = _model_arrays(self.model)[0]
+        if grid != ():
+            raise ValueError('Grader: the model of one setting expected, got a grid %s' % (grid,))
+        self.classes = self.model['classes']
+
+    def state_dict(self):
+        d = {k: np.array(v, copy=True) for k, v in self.model.items()}
+        d.update(length_divisor=self.setting[0], height_threshold=self.setting[1], file1=self.file1)
+        return d
+
+    @classmethod
+    def from_state_dict(cls, state):
+        """state_dict()'s result, or what np.load gives of its np.savez."""
+        try:
+            setting = (int(state['length_divisor']), float(state['height_threshold']))
+            return cls(setting, {k: np.asarray(state[k]) for k in MODEL_KEYS}, str(state['file1']))
+        except KeyError as e:
+            raise ValueError('Grader.from_state_dict: %s is missing' % e)
+
+    def predict(self, features, decisions=False, contributions=False):
+        """svm_predict of the kept model: features [N, F] in svm_features' column order for this grader's file1."""
+        return svm_predict(self.model, features, decisions, contributions)
+
+    def grade_dataset(self, fakes, labels, label_indices, chunk=256, contributions=False):
+        """Resident volume pairs -> grades with ONE readback: hv_rhlv_views_batch at the grader's setting exactly as rhlv_dataset launches it, then
+        hv_svm_features and hv_svm_predict on the device.  fakes / labels / label_indices as for rhlv_dataset.  ->
+          {'grade' [N] (-1: ungradable), 'present' bool [N] (False: the original lacks the vertebra), 'raised' bool [N] (the coronal script would
+           have raised), 'records' [N, 2, 16] (rhlv_dataset's), 'features' [N, F], 'decision' [N, P], 'votes' [N, K], and with contributions=True
+           'contrib' [N, P, F]}
+        Nothing raises per vertebra: an absent vertebra or a raised coronal slice comes back as grade -1 with its flag."""
+        L = _lib.get()
+        grid, F, K, P, arrays, info, present, classes = _model_arrays(self.model)
+        n = len(fakes)
+        if n == 0 or len(labels) != n or len(label_indices) != n:
+            raise ValueError('grade_dataset: equally many (at least one) generated volumes, original volumes and label indices expected')
+        dev = fakes[0].device
+        geo = (fakes[0].shape, fakes[0].stride(), fakes[0].dtype)
+        for t in list(fakes) + list(labels):
+            _lib.require_gpu(t)
+            if t.dim() != 3 or (t.shape, t.stride(), t.dtype) != geo or t.dtype not in (torch.float32, torch.uint8) or t.device != dev:
+                raise ValueError('grade_dataset: [H, W, Z] float32 or uint8 device volumes of one shape, dtype and stride pattern expected')
+        H, W, Z = geo[0]
+        views = SAGITTAL | CORONAL
+        table = torch.tensor([p for f, l in zip(fakes, labels) for p in (f.data_ptr(), l.data_ptr())], dtype=torch.int64).to(dev)
+        ids = torch.tensor([float(i) for i in label_indices], dtype=torch.float32).to(dev)
+        host, o = _model_blob(arrays, info, present)
+        blob = torch.from_numpy(host).to(dev)
+        outs = [('records', np.float64, (n, 2, 16)), ('features', np.float64, (n, F)), ('decision', np.float64, (n, P))]
+        outs += ([('contrib', np.float64, (n, P, F))] if contributions else []) + [('pred', np.int32, (n,)), ('votes', np.int32, (n, K))]
+        offs, total = _layout(outs)
+        buf = torch.zeros(total + 8, dtype=torch.uint8, device=dev)
+        at = lambda name, skip=0: ctypes.c_void_p(buf.data_ptr() + offs[name] + skip) if name in offs else None
+        src = lambda k: ctypes.c_void_p(blob.data_ptr() + o[k])
+        chunk = max(1, min(int(chunk), n))
+        ws, _ = ops._ws(L.size('hv_rhlv_views_workspace_bytes', W, Z, views, chunk), dev, slot=3)
+        sag, cor = _view_args(L, views, self.setting[0], INT_MIN, 0, self.setting[1])
+        for i in range(0, n, chunk):
+            m = min(chunk, n - i)
+            L.call('hv_rhlv_views_batch', _lib.ptr(table[2 * i:]), _lib.ptr(ids[i:]), m, *_geometry(fakes[0]), views, sag, cor,
+                   at('records', i * 2 * 16 * 8), _lib.ptr(ws), ctypes.c_size_t(ws.numel()), _lib.stream())
+        L.call('hv_svm_features', at('records'), n, 0 if VIEWS[self.file1] == SAGITTAL else 1, F, at('features'), _lib.stream())
+        L.call('hv_svm_predict', at('features'), 1, n, F, K, src(5), src(0), src(1), src(2), src(3), src(4), at('pred'), at('decision'), at('votes'),
+               at('contrib'), _lib.stream())
+        res = _unpack(buf.cpu().numpy(), outs, offs)
+        pred = res.pop('pred')
+        res['grade'] = np.where(pred >= 0, classes[np.clip(pred, 0, K - 1)], -1)
+        res['present'] = res['records'][:, 0, 13] != 0
+        res['raised'] = res['records'][:, 1, 14] != 0
+        return res
+
+
+def fit_grader(sweep, labels, dataset, grades=None, score='f1', setting=None, file1='sagittal', tol=1e-3, max_iter=100000):
+    """The grader of a sweep: fitted at `setting` = (length_divisor, height_threshold) of the sweep's grid, by default best_setting(sweep, grades,
+    score) with grades = svm_grade_grid(svm_feature_grid(sweep), labels, dataset) where none are given, on the train + test rows -- scaler and SVC as
+    the reference's grading fits them, the val rows stay untouched.  file1: the view whose three columns come first (svm_features' order).
+    -> Grader"""
+    feats = svm_feature_grid(sweep)
+    labels, dataset = np.asarray(labels), np.asarray(dataset)
+    if labels.shape != feats.shape[:1] or dataset.shape != feats.shape[:1]:
+        raise ValueError('fit_grader: one label and one dataset name per row of the sweep expected')
+    if not np.all(np.isin(dataset, ('train', 'test', 'val'))):
+        raise ValueError("fit_grader: dataset entries must be 'train', 'test' or 'val'")
+    if file1 not in VIEWS:
+        raise ValueError("fit_grader: file1 must be 'sagittal' or 'coronal'")
+    if setting is None:
+        if grades is None:
+            grades = svm_grade_grid(feats, labels, dataset, tol=tol, max_iter=max_iter)
+        setting = best_setting(sweep, grades, score)
+    divs, thrs = [int(d) for d in sweep['length_divisors']], [float(t) for t in sweep['height_thresholds']]
+    setting = (int(setting[0]), float(setting[1]))
+    if setting[0] not in divs or setting[1] not in thrs:
+        raise ValueError('fit_grader: setting %s is not a point of the sweep\'s grid' % (setting,))
+    at = feats[:, divs.index(setting[0]), thrs.index(setting[1])]
+    if VIEWS[file1] == CORONAL:
+        at = np.concatenate([at[:, 3:], at[:, :3]], axis=1)
+    # as svm_grade_grid: a row that is NaN at every grid point (vertebra absent) is dropped, a row that is NaN at this one makes the model unusable
+    keep = (dataset != 'val') & ~np.isnan(feats.reshape(len(feats), -1, 6)).any(axis=2).all(axis=1)
+    model = svm_fit(at[keep], labels[keep], tol=tol, max_iter=max_iter)
+    return Grader(setting, model, file1)
 
 
 # ---------------------------------------------------------------- per-column height-loss maps and profiles (hv_rhlv_maps)

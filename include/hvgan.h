@@ -883,6 +883,39 @@ int hv_svm_grade_grid(const double* X_tt, const double* X_val, const void* plan,
                       int max_iter, double* w, double* b, double* gap, int* info, int* pred, int* confusion, double* scores, double* mean,
                       double* var, int* unusable, double* decision, void* stream);
 
+/* ---- fit the grader at one chosen setting, keep the model, grade rows that were not in the table ----
+ * The same scaler, solver and vote as hv_svm_grade_grid (one solver body and one row-vote body in csrc/svm_grade.hip, called by both): a fit on
+ * the rows `fold != f` of a table gives bit for bit that call's w, b, gap and info of fold f, and hv_svm_predict of that model on the val rows its
+ * pred and decision.  Float64, fixed-order reductions, no workspace; a grid point's bytes do not depend on G or on its place in the grid.
+ * hv_svm_fit_plan: HOST arithmetic only.  y [M]: the grade of every row, train [M] (NULL = every row): non-zero = the row enters the solver,
+ *   classes [K] sorted, strictly increasing, non-negative.  Writes into `plan` (host, hv_svm_fit_plan_bytes(M) bytes): the bound on alpha per class
+ *   n_train / (n_classes_in_train * count(class)) over the train rows (0 for a class without train rows), present [K], the class index and the
+ *   train flag of every row; *max_rows = the train rows of the largest class pair.  HV_ERR_ARG: null pointer, M <= 0, classes not sorted, a grade
+ *   not in classes; HV_ERR_UNSUPPORTED: K outside 2..HV_SVM_MAX_CLASSES, *max_rows > HV_SVM_MAX_ROWS (then *max_rows is still set);
+ *   HV_ERR_WORKSPACE: plan_bytes too small.  A refusal leaves `plan` untouched.
+ * hv_svm_fit: X [G][M][F] (device, F = 3 or 6), plan (device copy).  One wave per (class pair, grid point): StandardScaler over ALL M rows of the
+ *   grid point (the reference scales before it splits), then the C-SVC dual of the pair's train rows, the lower class first, each class in row
+ *   order.  mean, scale [G][F], w [G][P][F], b, gap [G][P], info [G][P][4] = { iterations, status, support vectors, rows }.  A non-finite feature
+ *   among the M rows: every pair of that grid point reports HV_SVM_UNUSABLE and its w, b, mean, scale are NaN; the other grid points are not
+ *   affected.  HV_SVM_ABSENT: a class of the pair has no train row.
+ * hv_svm_predict: X [G][N][F] (device), present [K] (device: the plan's present flags), the model of hv_svm_fit.  One lane per row:
+ *   pred [G][N] the class index, -1 where the row has a non-finite feature, the model is unusable or no class is present; decision [G][N][P]
+ *   (w.x_scaled - b, NaN for a pair that was not solved), votes [G][N][K], contrib [G][N][P][F] = w[p][c] * x_scaled[c] -- its sum in column
+ *   order minus b is the decision, bit for bit.  decision, votes, contrib may be NULL.  A bad row has pred -1, NaN decision and contrib, zero
+ *   votes and touches nothing else.
+ * hv_svm_features: records [N][2][16] (what hv_rhlv_views_batch leaves on the device, both views) -> X [N][F]: columns 1..3 of view first_view
+ *   (0 sagittal, 1 coronal), with F = 6 followed by the other view's.  The row is NaN where the original lacks the vertebra (sagittal [13] == 0)
+ *   or the coronal script would have raised (coronal [14] != 0).
+ * All three device entries refuse before any launch -- HV_ERR_ARG: null required pointer, G, M or N <= 0, tol <= 0, max_iter < 1, first_view not
+ * 0 / 1; HV_ERR_UNSUPPORTED: F not 3 or 6, K outside 2..HV_SVM_MAX_CLASSES, max_rows > HV_SVM_MAX_ROWS, G > 65535. */
+size_t hv_svm_fit_plan_bytes(int M);
+int hv_svm_fit_plan(const int* y, const int* train, int M, const int* classes, int K, void* plan, size_t plan_bytes, int* max_rows);
+int hv_svm_fit(const double* X, const void* plan, int G, int M, int F, int K, int max_rows, double tol, int max_iter, double* mean, double* scale,
+               double* w, double* b, double* gap, int* info, void* stream);
+int hv_svm_predict(const double* X, int G, int N, int F, int K, const int* present, const double* mean, const double* scale, const double* w,
+                   const double* b, const int* info, int* pred, double* decision, int* votes, double* contrib, void* stream);
+int hv_svm_features(const double* records, int N, int first_view, int F, double* X, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
