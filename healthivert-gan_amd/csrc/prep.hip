@@ -779,5 +779,5 @@ extern "C" int hv_mul3(float* y, const float* x, const float* z, long long n, vo
     return HV_OK;
 }
 
-extern "C" int hv_version(void) { return 105; }
+extern "C" int hv_version(void) { return 106; }
 extern "C" const char* hv_arch(void) { return "gfx950"; }

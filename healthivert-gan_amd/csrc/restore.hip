@@ -8,6 +8,8 @@
 //                           coordinate in the crop, the coverage test, a trilinear sample of the crop's CT (map_coordinates order 1), a
 //                           nearest sample of its label (order 0), and the write rule.  Knots, frames and cumulative lengths sit in LDS
 //                           (13 doubles per knot); LDS = false reads them from global memory when they do not fit.
+//                           ORDER = 3 (hv_restore_volume_spline): the CT sample is cubic (map_coordinates order 3), 4 x 4 x 4 taps of the
+//                           B-spline coefficients of the crop's filled sub-box; everything else is shared.
 //                           With anisotropic voxels (hv_restore_volume_sp) p enters the scans as p * spacing; the rest is unchanged.
 //   curve_points_kernel<LDS> one lane per point of a list: global_to_local or local_to_global (curve.py:110-114,131-138) through the same
 //                           device function (rs_curve_map) as the restore, no crop involved.
@@ -15,6 +17,7 @@
 // Everything in doubles in the reference's operation order (-ffp-contract=off); element offsets are 64-bit.
 #include <cmath>
 #include "hv_common.h"
+#include "spline_tap.h"                                    // hv_spline_sample
 
 #define RS_THREADS 512
 #define RS_KNOT_DOUBLES 13                                    // knot 3, frame 9, cumulative length 1
@@ -183,7 +186,7 @@ __device__ __forceinline__ void rs_curve_map(const RsCurve& cv, const double P0,
 #undef RS_C
 }
 
-template <bool LDS>
+template <bool LDS, int ORDER>
 __global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs A) {
     if (LDS) rs_stage(cv);
     const long long total = (long long)A.rn0 * A.rn1 * A.rn2;
@@ -208,21 +211,27 @@ __global__ __launch_bounds__(RS_THREADS) void restore_kernel(RsCurve cv, RsArgs 
     const double c0 = (l0 - (double)A.lo0) + (double)A.st0, c1 = (l2 - (double)A.lo1) + (double)A.st1, c2 = (l1 - (double)A.lo2) + (double)A.st2;
     const int e0 = A.st0 + A.n0 - 1, e1 = A.st1 + A.n1 - 1, e2 = A.st2 + A.n2 - 1;     // last filled index per axis
     if (!(c0 >= (double)A.st0 && c0 <= (double)e0 && c1 >= (double)A.st1 && c1 <= (double)e1 && c2 >= (double)A.st2 && c2 <= (double)e2)) return;
-    const double f0 = floor(c0), f1 = floor(c1), f2 = floor(c2);
-    const double t0 = c0 - f0, t1 = c1 - f1, t2 = c2 - f2;
-    const long long i0 = (long long)f0, i1 = (long long)f1, i2 = (long long)f2;
-    // at c = the last filled index the upper weight is 0 and the upper neighbour (the crop's zero padding) is not read
-    const long long ox[2] = {i0 * A.cs0, (i0 + 1 <= e0 ? i0 + 1 : i0) * A.cs0}, oy[2] = {i1 * A.cs1, (i1 + 1 <= e1 ? i1 + 1 : i1) * A.cs1},
-                    oz[2] = {i2 * A.cs2, (i2 + 1 <= e2 ? i2 + 1 : i2) * A.cs2};
-    const double wx[2] = {1.0 - t0, t0}, wy[2] = {1.0 - t1, t1}, wz[2] = {1.0 - t2, t2};
     double v = 0.0;
-    // map_coordinates order 1: sum over the 8 corners, last axis fastest, coefficient = value * w_x * w_y * w_z
+    if constexpr (ORDER == 3) {
+        // crop_ct holds the coefficients of the filled sub-box alone ([n0][n1][n2] contiguous, mirrored at its own edges): the sample lies at
+        // c - start, inside [0, n - 1] by the coverage test (the difference is monotonic in c)
+        v = hv_spline_sample((const double*)A.crop_ct, A.n0, A.n1, A.n2, c0 - (double)A.st0, c1 - (double)A.st1, c2 - (double)A.st2);
+    } else {
+        const double f0 = floor(c0), f1 = floor(c1), f2 = floor(c2);
+        const double t0 = c0 - f0, t1 = c1 - f1, t2 = c2 - f2;
+        const long long i0 = (long long)f0, i1 = (long long)f1, i2 = (long long)f2;
+        // at c = the last filled index the upper weight is 0 and the upper neighbour (the crop's zero padding) is not read
+        const long long ox[2] = {i0 * A.cs0, (i0 + 1 <= e0 ? i0 + 1 : i0) * A.cs0}, oy[2] = {i1 * A.cs1, (i1 + 1 <= e1 ? i1 + 1 : i1) * A.cs1},
+                        oz[2] = {i2 * A.cs2, (i2 + 1 <= e2 ? i2 + 1 : i2) * A.cs2};
+        const double wx[2] = {1.0 - t0, t0}, wy[2] = {1.0 - t1, t1}, wz[2] = {1.0 - t2, t2};
+        // map_coordinates order 1: sum over the 8 corners, last axis fastest, coefficient = value * w_x * w_y * w_z
 #pragma unroll
-    for (int hx = 0; hx < 2; ++hx)
+        for (int hx = 0; hx < 2; ++hx)
 #pragma unroll
-        for (int hy = 0; hy < 2; ++hy)
+            for (int hy = 0; hy < 2; ++hy)
 #pragma unroll
-            for (int hz = 0; hz < 2; ++hz) v += ((rs_ld_ct(A.crop_ct, A.crop_dt, ox[hx] + oy[hy] + oz[hz]) * wx[hx]) * wy[hy]) * wz[hz];
+                for (int hz = 0; hz < 2; ++hz) v += ((rs_ld_ct(A.crop_ct, A.crop_dt, ox[hx] + oy[hy] + oz[hz]) * wx[hx]) * wy[hy]) * wz[hz];
+    }
     const long long m0 = (long long)floor(c0 + 0.5), m1 = (long long)floor(c1 + 0.5), m2 = (long long)floor(c2 + 0.5);   // order 0
     const int l = (int)A.crop_lab[m0 * A.ls0 + m1 * A.ls1 + m2 * A.ls2];
     rs_write(A, px, py, pz, v, l);
@@ -276,14 +285,16 @@ static bool rs_spacing_ok(const double* sp) {
     return true;
 }
 
-extern "C" int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2,
-                                    const uint8_t* crop_label, long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
-                                 const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
-                                 int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region,
-                                 int where, int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out,
-                                 long long qs0, long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2,
-                                 double* local_out, const double* spacing, void* stream) {
+// both restore entries: order 1 reads the crop's CT (crop_dtype, strides), order 3 the contiguous float64 coefficients of its filled sub-box
+static int rs_restore(int order, const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2, const uint8_t* crop_label,
+                      long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+                      const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
+                      int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region, int where,
+                      int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out, long long qs0,
+                      long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2, double* local_out,
+                      const double* spacing, void* stream) {
     if (!rs_spacing_ok(spacing)) return HV_ERR_ARG;
+    if (order == 3 && !knots) return HV_ERR_ARG;         // the un-crop branch copies voxels: it has no cubic form
     if (!crop_ct || !crop_label || !box || !region || !ct_out || !label_out || O0 <= 0 || O1 <= 0 || O2 <= 0 || D0 <= 0 || D1 <= 0 || D2 <= 0 ||
         (crop_dtype != HV_DT_F32 && crop_dtype != HV_DT_F64) || (where != HV_RESTORE_CROP && where != HV_RESTORE_VERTEBRA) || vert_id < 0 ||
         vert_id > 255)
@@ -321,10 +332,41 @@ extern "C" int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long lo
     cv.sp0 = spacing[0]; cv.sp1 = spacing[1]; cv.sp2 = spacing[2];
     const size_t lds = (size_t)N * RS_KNOT_DOUBLES * sizeof(double);
     const int grid = hv_cdiv(total, RS_THREADS);
-    if (lds <= RS_LDS_BYTES) hipLaunchKernelGGL(restore_kernel<true>, dim3(grid), dim3(RS_THREADS), lds, s, cv, A);
-    else hipLaunchKernelGGL(restore_kernel<false>, dim3(grid), dim3(RS_THREADS), 0, s, cv, A);
+    if (order == 3) {
+        if (lds <= RS_LDS_BYTES) hipLaunchKernelGGL((restore_kernel<true, 3>), dim3(grid), dim3(RS_THREADS), lds, s, cv, A);
+        else hipLaunchKernelGGL((restore_kernel<false, 3>), dim3(grid), dim3(RS_THREADS), 0, s, cv, A);
+    } else {
+        if (lds <= RS_LDS_BYTES) hipLaunchKernelGGL((restore_kernel<true, 1>), dim3(grid), dim3(RS_THREADS), lds, s, cv, A);
+        else hipLaunchKernelGGL((restore_kernel<false, 1>), dim3(grid), dim3(RS_THREADS), 0, s, cv, A);
+    }
     HV_LAUNCH_CHECK();
     return HV_OK;
+}
+
+extern "C" int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long long cs0, long long cs1, long long cs2,
+                                    const uint8_t* crop_label, long long ls0, long long ls1, long long ls2, int O0, int O1, int O2, const int* box, const double* knots,
+                                 const double* basis, const double* cumlen, int N, double centre1, double centre2, const void* patient_label,
+                                 int label_dtype, long long ps0, long long ps1, long long ps2, int D0, int D1, int D2, const int* region,
+                                 int where, int vert_id, double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out,
+                                 long long qs0, long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2,
+                                 double* local_out, const double* spacing, void* stream) {
+    return rs_restore(1, crop_ct, crop_dtype, cs0, cs1, cs2, crop_label, ls0, ls1, ls2, O0, O1, O2, box, knots, basis, cumlen, N, centre1, centre2,
+                      patient_label, label_dtype, ps0, ps1, ps2, D0, D1, D2, region, where, vert_id, ct_out, os0, os1, os2, label_out, qs0, qs1,
+                      qs2, covered, vs0, vs1, vs2, local_out, spacing, stream);
+}
+
+// order 3: the CT sample is cubic, taken from `crop_coef`, hv_spline_prefilter's output for the filled sub-box of the crop alone
+// ([len0][len1][len2] of the box row, contiguous); the label crop, the coverage test and the write rules are hv_restore_volume_sp's
+extern "C" int hv_restore_volume_spline(const double* crop_coef, const uint8_t* crop_label, long long ls0, long long ls1, long long ls2, int O0,
+                                        int O1, int O2, const int* box, const double* knots, const double* basis, const double* cumlen, int N,
+                                        double centre1, double centre2, const void* patient_label, int label_dtype, long long ps0,
+                                        long long ps1, long long ps2, int D0, int D1, int D2, const int* region, int where, int vert_id,
+                                        double* ct_out, long long os0, long long os1, long long os2, uint8_t* label_out, long long qs0,
+                                        long long qs1, long long qs2, uint8_t* covered, long long vs0, long long vs1, long long vs2,
+                                        double* local_out, const double* spacing, void* stream) {
+    return rs_restore(3, crop_coef, HV_DT_F64, 0, 0, 0, crop_label, ls0, ls1, ls2, O0, O1, O2, box, knots, basis, cumlen, N, centre1, centre2,
+                      patient_label, label_dtype, ps0, ps1, ps2, D0, D1, D2, region, where, vert_id, ct_out, os0, os1, os2, label_out, qs0, qs1,
+                      qs2, covered, vs0, vs1, vs2, local_out, spacing, stream);
 }
 
 // the entry from before the spacing: voxel indices are millimetres (x * 1.0 is exact: the same bits)

@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstdlib>
 #include "hv_common.h"
+#include "spline_tap.h"                   // ss_window, hv_spline_sample
 
 #define SS_HDR 4                      // [0] ~key(min) (atomic max), [1] key(max), [2] bad-label flag, [3] unused
 #define SS_CNT SS_HDR                 // [4 + l] voxel count of label l
@@ -44,14 +45,6 @@ __device__ __forceinline__ double ss_ld_dt(const void* p, int dt, long long o) {
         case HV_DT_F32: return (double)((const float*)p)[o];
         default: return ((const double*)p)[o];
     }
-}
-
-// window(img, win_min, win_max) on one value (straighten_mask_3d.py:178-183): 255.0 * (v - min) / (max - min), clipped to [0, 255]
-__device__ __forceinline__ double ss_window(double v, double wmin, double wmax) {
-    double r = 255.0 * (v - wmin) / (wmax - wmin);
-    if (r < 0.0) r = 0.0;
-    if (r > 255.0) r = 255.0;
-    return r;
 }
 
 // memory-order walk of a [D0][D1][D2] volume with arbitrary strides: the host passes the axes sorted by stride (innermost first)
@@ -145,8 +138,9 @@ __global__ __launch_bounds__(256) void straighten_stats_label_kernel(const T* __
 struct SsSpacing { double s0, s1, s2; };      // millimetres per voxel along axes 0, 1, 2: a kernel argument, no device allocation
 
 // one lane per sample; workgroups are renumbered so that consecutive planes (which read the same voxels) run on one XCD
-// (the hardware hands workgroup i to XCD i % 8)
-template <typename T>
+// (the hardware hands workgroup i to XCD i % 8).  ORDER = 3: `ct` is the contiguous float64 coefficient volume hv_spline_prefilter left (the
+// window already applied), read as 4 x 4 x 4 cubic B-spline taps; coordinates, the outside rule, the label and the presence bits are shared.
+template <typename T, int ORDER>
 __global__ __launch_bounds__(256) void straighten_sample_kernel(const T* __restrict__ ct, long long cs0, long long cs1, long long cs2,
                                                                 const void* __restrict__ label, int ldt, long long ls0, long long ls1, long long ls2,
                                                                 int D0, int D1, int D2, const double* __restrict__ knots,
@@ -177,29 +171,33 @@ __global__ __launch_bounds__(256) void straighten_sample_kernel(const T* __restr
     double v = 0.0;
     int l = 0;
     if (in) {
-        long long i0[3], i1[3];
-        double w0[3], w1[3];
+        if constexpr (ORDER == 3) {
+            v = hv_spline_sample((const double*)ct, D0, D1, D2, c[0], c[1], c[2]);
+        } else {
+            long long i0[3], i1[3];
+            double w0[3], w1[3];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double f = floor(c[i]);
-            const double t = c[i] - f;
-            i0[i] = (long long)f;
-            i1[i] = i0[i] + 1 < D[i] ? i0[i] + 1 : i0[i];     // at c = D - 1 the upper weight is 0: not read
-            w0[i] = 1.0 - t;
-            w1[i] = t;
+            for (int i = 0; i < 3; ++i) {
+                const double f = floor(c[i]);
+                const double t = c[i] - f;
+                i0[i] = (long long)f;
+                i1[i] = i0[i] + 1 < D[i] ? i0[i] + 1 : i0[i];     // at c = D - 1 the upper weight is 0: not read
+                w0[i] = 1.0 - t;
+                w1[i] = t;
+            }
+            const long long ox[2] = {i0[0] * cs0, i1[0] * cs0}, oy[2] = {i0[1] * cs1, i1[1] * cs1}, oz[2] = {i0[2] * cs2, i1[2] * cs2};
+            // map_coordinates: sum over the 8 corners, last axis fastest, coefficient = value * w_x * w_y * w_z
+#pragma unroll
+            for (int hx = 0; hx < 2; ++hx)
+#pragma unroll
+                for (int hy = 0; hy < 2; ++hy)
+#pragma unroll
+                    for (int hz = 0; hz < 2; ++hz) {
+                        double u = ss_ld(ct, ox[hx] + oy[hy] + oz[hz]);
+                        if (win) u = ss_window(u, wmin, wmax);
+                        v += ((u * (hx ? w1[0] : w0[0])) * (hy ? w1[1] : w0[1])) * (hz ? w1[2] : w0[2]);
+                    }
         }
-        const long long ox[2] = {i0[0] * cs0, i1[0] * cs0}, oy[2] = {i0[1] * cs1, i1[1] * cs1}, oz[2] = {i0[2] * cs2, i1[2] * cs2};
-        // map_coordinates: sum over the 8 corners, last axis fastest, coefficient = value * w_x * w_y * w_z
-#pragma unroll
-        for (int hx = 0; hx < 2; ++hx)
-#pragma unroll
-            for (int hy = 0; hy < 2; ++hy)
-#pragma unroll
-                for (int hz = 0; hz < 2; ++hz) {
-                    double u = ss_ld(ct, ox[hx] + oy[hy] + oz[hz]);
-                    if (win) u = ss_window(u, wmin, wmax);
-                    v += ((u * (hx ? w1[0] : w0[0])) * (hy ? w1[1] : w0[1])) * (hz ? w1[2] : w0[2]);
-                }
         const long long n0 = (long long)floor(c[0] + 0.5), n1 = (long long)floor(c[1] + 0.5), n2 = (long long)floor(c[2] + 0.5);
         const double d = ss_ld_dt(label, ldt, n0 * ls0 + n1 * ls1 + n2 * ls2);
         l = d >= 0.0 && d <= 255.0 ? (int)d : 0;         // validated by the stats pass; the guard keeps the presence index in range
@@ -308,11 +306,11 @@ extern "C" int hv_straighten_stats(const void* ct, int ct_dtype, long long cs0, 
     return HV_OK;
 }
 
-extern "C" int hv_straighten_sample_sp(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label,
-                                       int label_dtype, long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots,
-                                       const double* basis, int N, int PA, int PB, int window, double win_min, double win_max,
-                                       double* straight_ct, uint8_t* straight_label, uint64_t* presence, size_t presence_bytes,
-                                       const double* spacing, void* stream) {
+// both sampling entries: order 1 reads the scan (ct_dtype, strides), order 3 the contiguous float64 coefficients of the whole scan
+static int ss_sample(int order, const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label, int label_dtype,
+                     long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots, const double* basis, int N, int PA,
+                     int PB, int window, double win_min, double win_max, double* straight_ct, uint8_t* straight_label, uint64_t* presence,
+                     size_t presence_bytes, const double* spacing, void* stream) {
     if (!spacing) return HV_ERR_ARG;
     for (int i = 0; i < 3; ++i)
         if (!(spacing[i] > 0.0) || !std::isfinite(spacing[i])) return HV_ERR_ARG;
@@ -327,17 +325,37 @@ extern "C" int hv_straighten_sample_sp(const void* ct, int ct_dtype, long long c
     if (hipMemsetAsync(presence, 0, hv_straighten_presence_bytes(PA), s) != hipSuccess) return -1000 - (int)hipGetLastError();
     const int nblk = hv_cdiv(total, 256);
     const int grid = hv_cdiv(nblk, 8) * 8;
-#define SS_SMP(T) hipLaunchKernelGGL(straighten_sample_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)ct, cs0, cs1, cs2, label, label_dtype, \
-                                     ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, window, win_min, win_max, straight_ct, straight_label, \
-                                     (u64*)presence, nblk, sp)
-    switch (ct_dtype) {
-        case HV_DT_I16: SS_SMP(int16_t); break;
-        case HV_DT_F32: SS_SMP(float); break;
-        default: SS_SMP(double); break;
+#define SS_SMP(T, ORDER) hipLaunchKernelGGL((straighten_sample_kernel<T, ORDER>), dim3(grid), dim3(256), 0, s, (const T*)ct, cs0, cs1, cs2, label, \
+                                            label_dtype, ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, window, win_min, win_max, straight_ct, \
+                                            straight_label, (u64*)presence, nblk, sp)
+    if (order == 3) SS_SMP(double, 3);
+    else switch (ct_dtype) {
+        case HV_DT_I16: SS_SMP(int16_t, 1); break;
+        case HV_DT_F32: SS_SMP(float, 1); break;
+        default: SS_SMP(double, 1); break;
     }
 #undef SS_SMP
     HV_LAUNCH_CHECK();
     return HV_OK;
+}
+
+extern "C" int hv_straighten_sample_sp(const void* ct, int ct_dtype, long long cs0, long long cs1, long long cs2, const void* label,
+                                       int label_dtype, long long ls0, long long ls1, long long ls2, int D0, int D1, int D2, const double* knots,
+                                       const double* basis, int N, int PA, int PB, int window, double win_min, double win_max,
+                                       double* straight_ct, uint8_t* straight_label, uint64_t* presence, size_t presence_bytes,
+                                       const double* spacing, void* stream) {
+    return ss_sample(1, ct, ct_dtype, cs0, cs1, cs2, label, label_dtype, ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, window, win_min,
+                     win_max, straight_ct, straight_label, presence, presence_bytes, spacing, stream);
+}
+
+// order 3: the CT is sampled cubically from `coef`, hv_spline_prefilter's output for the whole scan ([D0][D1][D2] contiguous, the window fused
+// in there); label, presence bits, coordinates and the outside rule are hv_straighten_sample_sp's
+extern "C" int hv_straighten_sample_spline(const double* coef, const void* label, int label_dtype, long long ls0, long long ls1, long long ls2,
+                                           int D0, int D1, int D2, const double* knots, const double* basis, int N, int PA, int PB,
+                                           double* straight_ct, uint8_t* straight_label, uint64_t* presence, size_t presence_bytes,
+                                           const double* spacing, void* stream) {
+    return ss_sample(3, coef, HV_DT_F64, 0, 0, 0, label, label_dtype, ls0, ls1, ls2, D0, D1, D2, knots, basis, N, PA, PB, 0, 0.0, 1.0,
+                     straight_ct, straight_label, presence, presence_bytes, spacing, stream);
 }
 
 // the entry from before the spacing: the scan is on a 1 mm grid (x / 1.0 is exact: the same bits)

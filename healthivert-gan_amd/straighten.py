@@ -14,6 +14,7 @@ requested vertebra (csrc/straighten.hip).
   depedicle(label_vol, out=None) -> uint8 volume            process_3d_array (straighten_mask_3d.py:189-219) on a crop or a batch of crops
   component_counts(label_vol) -> int32 [Z, 256]             4-connected components of every label value per slice
   single_component_range(label_vol, label, offset=10)       find_single_component_layers (:249-280) -> (z0, z1)
+  spline_coefficients(vol, window=None) -> float64 volume    scipy.ndimage.spline_filter(vol, 3, mode='mirror'): the prefilter of order=3
   restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebra') -> (ct_out, label_out[, covered][, local])
                                                             the way back: Interpolator.global_to_local (curve.py:104-150,223-239) for every
                                                             voxel of a vertebra's patient-space box (restore_box) and a resample of the
@@ -26,6 +27,12 @@ Scans with anisotropic voxels: straighten_patient, plan, curve_frame, global_to_
 spacing=(sx, sy, sz), millimetres per voxel, the `spacing` of the reference's Interpolator (curve.py:26-52,160-195), which process_mask3d
 leaves at 1.  The scan is read at its native spacing, the crops come out on the 1 mm grid the later stages assume, and restore_patient
 (which reads the spacing from the plan) writes back onto the scan's own grid.
+
+Cubic resampling: straighten_patient and restore_patient take order=1 (trilinear, the default and what process_mask3d asks for) or order=3,
+the cubic B-spline of interpolate_along(array, shape, order=3) (curve.py:77-102 -> scipy.ndimage.map_coordinates): the scan (each crop's
+filled part on the way back) is prefiltered once into float64 B-spline coefficients (csrc/spline.hip; spline_coefficients(vol) is that step
+alone) and the CT is sampled from 4 x 4 x 4 taps of them.  Labels stay order 0.  There is no clipping: a cubic sample of windowed [0, 255] data
+may leave that interval, as it does in scipy.  The coefficients cost 8 bytes per voxel of the scan (839 MB for 512 x 512 x 400).
 
 Volumes are [X, Y, Z] device tensors as nibabel hands them over (any strides; a Fortran-ordered array passes as it lies).  The CT may be
 int16, float32 or float64 and is windowed in double for every dtype.  Deviation: the reference reads CT files over 500 MB as float32
@@ -271,6 +278,35 @@ def _stats(ct, label, ctc, lc):
     return st, rec
 
 
+def check_order(order):
+    """The spline order of the CT resampling: 1 (trilinear) or 3 (cubic B-spline); anything else is a ValueError (orders 2, 4 and 5 of
+    scipy's map_coordinates are out of scope)."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in (1, 3):
+        raise ValueError('order: 1 (trilinear) or 3 (cubic B-spline), got %r' % (order,))
+    return int(order)
+
+
+def _prefilter(vol, dims, win, wmin, wmax):
+    """hv_spline_prefilter of the [dims] box whose first element is vol's (a view: its pointer and strides) -> float64 [dims], contiguous."""
+    coef = torch.empty(tuple(dims), dtype=torch.float64, device=vol.device)
+    _lib.get().call('hv_spline_prefilter', _lib.ptr(vol), _DT[vol.dtype], *_strides(vol), *(int(d) for d in dims), int(win),
+                    ctypes.c_double(wmin), ctypes.c_double(wmax), _lib.ptr(coef), _lib.stream())
+    return coef
+
+
+def spline_coefficients(vol, window=None):
+    """The cubic B-spline prefilter alone: scipy.ndimage.spline_filter(vol, 3, mode='mirror') in float64 for a [X, Y, Z] device tensor
+    (int16 / float32 / float64, any strides) -> contiguous float64 device tensor of the same shape (8 bytes per voxel).  window: None or
+    (win_min, win_max): every voxel goes through window() (straighten_mask_3d.py:178-183) as it is read, before the filter."""
+    _lib.require_gpu(vol)
+    if vol.dim() != 3 or min(vol.shape) <= 0:
+        raise ValueError('spline_coefficients: expected a non-empty [X, Y, Z] volume, got %s' % (tuple(vol.shape),))
+    _dtype_code(vol, _CT_DT, 'volume')
+    wmin, wmax = (0.0, 1.0) if window is None else (float(window[0]), float(window[1]))
+    with torch.cuda.device(vol.device):
+        return _prefilter(vol, vol.shape, window is not None, wmin, wmax)
+
+
 def vertebra_centroids(label):
     """The centroid list of location_json_local.py for one label volume (device tensor [X, Y, Z], integer values 0..255): labels ascending,
     the two small-label drops applied, {"label", "X", "Y", "Z"} = mean voxel index along axes 0, 1, 2 (bit-identical to numpy's)."""
@@ -437,7 +473,7 @@ _depedicle = depedicle
 
 
 def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 256, 64), return_plan=False, depedicle=False,
-                       spacing=(1.0, 1.0, 1.0)):
+                       spacing=(1.0, 1.0, 1.0), order=1):
     """process_mask3d(ct, label, json, vertebrae_ids, out, out_size) on device tensors (straighten_mask_3d.py:463-563, mask_2d and file I/O
     excepted).  ct: [X, Y, Z] int16 / float32 / float64; label: [X, Y, Z] integer values 0..255 in any integer or float dtype.  centroids:
     the list location_json_local.py writes, or None = computed on the device from the same stats pass.
@@ -445,8 +481,13 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
     process_3d_array call the reference keeps commented out in process_mask3d).
     spacing: millimetres per voxel of the scan along its three axes (a scalar: all three), the Interpolator's `spacing` (curve.py:26-52):
     the scan is read at its native spacing and the crops come out on the 1 mm grid the later stages assume; no resampled copy is made.
+    order: how the CT is resampled, interpolate_along's `order` (curve.py:77-102): 1 = trilinear (what process_mask3d passes), 3 = cubic
+    B-spline: the scan is prefiltered once, the window fused into that pass (8 bytes per voxel of the scan while the call runs), and sampled
+    cubically.  Labels are order 0 either way and come out bit-identical.  A cubic sample is not clipped: it may leave the window's [0, 255],
+    as in scipy.  With one centroid (a raw crop at integer offsets) order has no effect.  The plan records it as 'order'.
     -> {vert_id: (ct_vol float64, label_vol uint8)}, each [out_size] on the device, the orientation the reference saves."""
     spacing = check_spacing(spacing)          # before any GPU work
+    order = check_order(order)
     ctc, lc = _check(ct, label)
     L = _lib.get()
     dev = ct.device
@@ -473,9 +514,15 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
             slab = torch.empty(N, PA, PB, dtype=torch.uint8, device=dev)
             pbytes = L.size('hv_straighten_presence_bytes', PA)
             pres = torch.empty(pbytes // 8, dtype=torch.int64, device=dev)
-            L.call('hv_straighten_sample_sp', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z,
-                   _lib.ptr(d_knots), _lib.ptr(d_basis), N, PA, PB, win, wmin, wmax, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres),
-                   ctypes.c_size_t(pbytes), (ctypes.c_double * 3)(*spacing), _lib.stream())
+            if order == 3:
+                coef = _prefilter(ct, (X, Y, Z), win, *WINDOW)
+                L.call('hv_straighten_sample_spline', _lib.ptr(coef), _lib.ptr(label), lc, *_strides(label), X, Y, Z, _lib.ptr(d_knots),
+                       _lib.ptr(d_basis), N, PA, PB, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres), ctypes.c_size_t(pbytes),
+                       (ctypes.c_double * 3)(*spacing), _lib.stream())
+            else:
+                L.call('hv_straighten_sample_sp', _lib.ptr(ct), ctc, *_strides(ct), _lib.ptr(label), lc, *_strides(label), X, Y, Z,
+                       _lib.ptr(d_knots), _lib.ptr(d_basis), N, PA, PB, win, wmin, wmax, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres),
+                       ctypes.c_size_t(pbytes), (ctypes.c_double * 3)(*spacing), _lib.stream())
             L.call('hv_straighten_crop', _lib.ptr(sct), 5, *_strides(sct), _lib.ptr(slab), 0, *_strides(slab), PA, 0, wmin, wmax,
                    _lib.ptr(pres), _lib.ptr(d_boxes), V, O0, O1, O2, _lib.ptr(ct_out), _lib.ptr(lab_out), _lib.stream())
         else:   # one centroid: the windowed raw CT and the raw label are cropped at the raw position (:499-502)
@@ -486,7 +533,7 @@ def straighten_patient(ct, label, vertebrae_ids, centroids=None, out_size=(256, 
     out = {vid: (ct_out[i], lab_out[i]) for i, vid in enumerate(vertebrae_ids)}
     if return_plan:
         return out, {'centroids': centroids, 'knots': knots, 'basis': basis, 'local': local, 'boxes': boxes, 'window': bool(win),
-                     'spacing': spacing}
+                     'spacing': spacing, 'order': order}
     return out
 
 
@@ -539,7 +586,7 @@ def _plan_spacing(plan, spacing=None):
 
 
 def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebra', return_covered=False, return_local=False, out=None,
-                    regions=None, spacing=None):
+                    regions=None, spacing=None, order=None):
     """The way back from the straightened crops to the patient's scan: Interpolator.global_to_local (curve.py:104-150,223-239) for every
     voxel of each vertebra's patient-space box and a resample of the crop there, on the device (csrc/restore.hip), where the reference
     offers the transform one point at a time in Python.
@@ -553,6 +600,10 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
     where the label sample or the patient's own label is vert_id.  The crop's zero padding never reaches the patient.
     spacing: None = plan['spacing'], the spacing of the scan the plan was made for ((1, 1, 1) for a plan without the entry); a value that
     disagrees with the plan is a ValueError.  The outputs are on the scan's own grid: a box voxel enters the curve math in millimetres.
+    order: None = plan['order'] (1 for a plan without the entry); an explicit 1 or 3 overrides it.  3: the CT sample is the cubic B-spline of
+    the crop's filled part (map_coordinates order 3 on crop[start : start + len], mirrored at its own edges): one prefilter call per vertebra
+    before its restore launch, on the same stream; not clipped, so it may leave the crop's value range.  Labels, the covered mask and the
+    local coordinates do not depend on it.  With a single-centroid plan (an integer un-crop) it has no effect.
     -> (ct_out float64, label_out uint8[, covered uint8: 1 where written][, {vert_id: (box, local)}: the patient-space box
     [x0, y0, z0, nx, ny, nz] and the local coordinate of each of its voxels, float64 [nx, ny, nz, 3], NaN where there is none])."""
     if where not in RESTORE:
@@ -560,6 +611,7 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
     if where == 'vertebra' and label is None:
         raise ValueError("restore: where='vertebra' needs the patient's label volume")
     spacing = _plan_spacing(plan, spacing)
+    order = check_order(plan.get('order', 1) if order is None else order)
     crops = dict(crops)
     if not crops:
         raise ValueError('restore: no crop')
@@ -656,6 +708,16 @@ def restore_patient(plan, crops, shape=None, ct=None, label=None, where='vertebr
             loc = torch.empty(region[3], region[4], region[5], 3, dtype=torch.float64, device=dev)
             local[vid] = (region, loc)
         if min(region[3:]) <= 0:
+            continue
+        if order == 3 and knots is not None and min(box[3:6]) > 0:
+            sub = cvol[box[6]:box[6] + box[3], box[7]:box[7] + box[4], box[8]:box[8] + box[5]]
+            coef = _prefilter(sub, box[3:6], 0, 0.0, 1.0)
+            L.call('hv_restore_volume_spline', _lib.ptr(coef), _lib.ptr(lvol), *_strides(lvol), *cvol.shape, (ctypes.c_int * 9)(*box),
+                   _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), N, ctypes.c_double(PLANE[0] / 2), ctypes.c_double(PLANE[1] / 2),
+                   _lib.ptr(label), 0 if label is None else _DT[label.dtype], *(zero3 if label is None else _strides(label)), *shape,
+                   (ctypes.c_int * 6)(*region), RESTORE[where], vid, _lib.ptr(ct_out), *_strides(ct_out), _lib.ptr(lab_out),
+                   *_strides(lab_out), _lib.ptr(covered), *(zero3 if covered is None else _strides(covered)), _lib.ptr(loc),
+                   (ctypes.c_double * 3)(*spacing), _lib.stream())
             continue
         L.call('hv_restore_volume_sp', _lib.ptr(cvol), _DT[cvol.dtype], *_strides(cvol), _lib.ptr(lvol), *_strides(lvol), *cvol.shape,
                (ctypes.c_int * 9)(*box), _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), N, ctypes.c_double(PLANE[0] / 2),

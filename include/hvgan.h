@@ -809,6 +809,43 @@ int hv_restore_volume_sp(const void* crop_ct, int crop_dtype, long long cs0, lon
 int hv_curve_points(const double* points, long long M, const double* knots, const double* basis, const double* cumlen, int N, double centre1,
                     double centre2, const double* spacing, int direction, double* out, void* stream);
 
+/* ---- cubic B-spline resampling (order 3) for the straightening and the restore (reference straighten/straighten/curve.py:77-102:
+ * interpolate_along hands `order` to scipy.ndimage.map_coordinates, and map_coordinates(v, coords, order=3, mode='constant', cval=0) is a
+ * prefilter, spline_filter(v, 3, mode='mirror') in float64, followed by a 4 x 4 x 4-tap sample) ----
+ * hv_spline_prefilter: the float64 B-spline coefficients of a 3-D source [D0][D1][D2] (HV_DT_I16 / F32 / F64, element (i, j, k) at
+ *   src[i*s0 + j*s1 + k*s2], strides in elements: a sub-box of a larger array is its first element's pointer and the array's strides) into
+ *   coef, [D0][D1][D2] contiguous doubles.  `window`: every voxel is windowed (255 (v - win_min) / (win_max - win_min) clipped to [0, 255]) as
+ *   it is first read, the reference's order (window the volume, then interpolate).  Along each axis in turn (0, 1, 2), with z = sqrt(3) - 2,
+ *   every line c[0..n-1] is scaled by (1 - z)(1 - 1/z), then c[0] = (c[0] + z^(n-1) c[n-1] + sum_{i=1..n-2} (z^i + z^(2n-2-i)) c[i]) /
+ *   (1 - z^(2n-2)), c[i] += z c[i-1], c[n-1] = z / (z^2 - 1) (c[n-1] + z c[n-2]), c[i] = z (c[i+1] - c[i]); a line of length 1 is left as
+ *   it is.  For n > 32 the sum for c[0] stops after 32 terms (|z|^32 = 5e-19, below one rounding).  One lane per line, no atomics: the same
+ *   input gives the same bits on every run.  Up to three launches, no workspace beyond coef (8 bytes per voxel: 839 MB for a 512 x 512 x 400
+ *   scan).  HV_ERR_ARG: null pointer, non-positive size, another dtype, coef not 8-byte aligned; nothing is launched, nothing written.
+ * Sampling a coefficient volume at u (all three coordinates inside [0, n - 1]; outside it the sample is 0 as for order 1): i = floor(u),
+ *   t = u - i, taps i - 1 .. i + 2 with the cubic B-spline weights ((1-t)^3 / 6, (t^2 (t - 2) 3 + 4) / 6, ((1-t)^2 ((1-t) - 2) 3 + 4) / 6,
+ *   the rest to 1), tap indices outside the line mirrored (-1 -> 1, n -> n - 2).  There is NO clipping: a cubic sample of windowed [0, 255]
+ *   data may leave that interval, as it does in scipy.
+ * hv_straighten_sample_spline: hv_straighten_sample_sp with the CT sampled cubically from coef = hv_spline_prefilter of the whole scan (the
+ *   window fused in there).  Coordinates, the spacing division, the outside rule, the label, the presence bits and the output layout are the
+ *   order-1 kernel's (one kernel template): straight_label and presence are bit-identical to hv_straighten_sample_sp's.  HV_ERR_ARG /
+ *   HV_ERR_WORKSPACE as there.
+ * hv_restore_volume_spline: hv_restore_volume_sp with the CT sampled cubically from crop_coef = hv_spline_prefilter of the crop's filled
+ *   sub-box alone: source pointer at crop element (start0, start1, start2), sizes (len0, len1, len2) of the box row, the crop's strides; the
+ *   mirror is at the sub-box's own edges and the crop's zero padding is never read.  The sample lies at c - start.  The covered rule, the
+ *   label sample (from crop_label, [O0][O1][O2]), the write rules and local_out are unchanged.  knots == NULL is HV_ERR_ARG here: the
+ *   single-centroid un-crop copies voxels (a cubic sample at a lattice point is the voxel itself), use hv_restore_volume_sp. */
+int hv_spline_prefilter(const void* src, int dtype, long long s0, long long s1, long long s2, int D0, int D1, int D2, int window, double win_min,
+                        double win_max, double* coef, void* stream);
+int hv_straighten_sample_spline(const double* coef, const void* label, int label_dtype, long long ls0, long long ls1, long long ls2, int D0,
+                                int D1, int D2, const double* knots, const double* basis, int N, int PA, int PB, double* straight_ct,
+                                uint8_t* straight_label, uint64_t* presence, size_t presence_bytes, const double* spacing, void* stream);
+int hv_restore_volume_spline(const double* crop_coef, const uint8_t* crop_label, long long ls0, long long ls1, long long ls2, int O0, int O1,
+                             int O2, const int* box, const double* knots, const double* basis, const double* cumlen, int N, double centre1,
+                             double centre2, const void* patient_label, int label_dtype, long long ps0, long long ps1, long long ps2, int D0,
+                             int D1, int D2, const int* region, int where, int vert_id, double* ct_out, long long os0, long long os1,
+                             long long os2, uint8_t* label_out, long long qs0, long long qs1, long long qs2, uint8_t* covered, long long vs0,
+                             long long vs1, long long vs2, double* local_out, const double* spacing, void* stream);
+
 /* ---- generation-quality evaluation of a synthesized volume (reference evaluation/generation_eval_sagittal.py:11-37 calculate_iou /
  * calculate_dice / relative_volume_difference, :39-103 process_images; generation_eval_coronal.py the same with the slice axis 1; SURVEY.md
  * row 17).  Four [H][W][Z] volumes: element (h, w, z) of the CTs at base[h*cs0 + w*cs1 + z*cs2], of the labels

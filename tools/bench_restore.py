@@ -9,7 +9,12 @@ label, the reference's parameters (plane 128 x 128, out_size (256, 256, 64)), on
   cpu_ref_s_extrapolated                  restore_ref on the host for a sub-box of --cpu-voxels voxels, scaled to the whole box
                                           (EXTRAPOLATED: the per-point Python loop takes minutes per vertebra)
 
-    timeout -k 10 600 python tools/bench_restore.py [--reps 10] [--cpu-voxels 4000] [--no-cpu] [--spacing a,b,c]
+  --order 3 adds: prefilter_ms (hv_spline_prefilter of the crop's filled sub-box), restore3_ms (hv_restore_volume_spline alone),
+                  patient3_ms (restore_patient(order=3) end to end: the prefilter and the launch)
+  --baseline-lib PATH adds: restore_ms_baseline, hv_restore_volume_sp of another build of the library (the parent commit's) loaded beside this
+                  one, timed in the same process, and restore_ms_spread / restore_ms_baseline_spread (max - min over the repeats)
+
+    timeout -k 10 600 python tools/bench_restore.py [--reps 10] [--cpu-voxels 4000] [--no-cpu] [--spacing a,b,c] [--order 3] [--baseline-lib PATH]
 --spacing: millimetres per voxel of the same 512 x 512 x 400 voxel patient (default 1,1,1).
 """
 import argparse
@@ -28,7 +33,7 @@ import hvgan  # noqa: E402,F401
 from hvgan import lib as _lib, straighten as S, synth  # noqa: E402
 
 
-def _timed(fn, reps):
+def _times(fn, reps):
     ts = []
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -37,7 +42,11 @@ def _timed(fn, reps):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    return float(np.median(ts))
+    return ts
+
+
+def _timed(fn, reps):
+    return float(np.median(_times(fn, reps)))
 
 
 def main():
@@ -46,6 +55,8 @@ def main():
     ap.add_argument('--cpu-voxels', type=int, default=4000)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--spacing', default='1,1,1')
+    ap.add_argument('--order', type=int, default=1, choices=(1, 3))
+    ap.add_argument('--baseline-lib', default=None)
     args = ap.parse_args()
     spacing = S.check_spacing([float(v) for v in args.spacing.split(',')])
     shape = (512, 512, 400)
@@ -74,12 +85,18 @@ def main():
     c_box, c_region = (ctypes.c_int * 9)(*box), (ctypes.c_int * 6)(*region)
     st = lambda t: [ctypes.c_longlong(v) for v in t.stride()]      # noqa: E731
 
-    def launch():
-        L.call('hv_restore_volume_sp', _lib.ptr(cvol), S._DT[cvol.dtype], *st(cvol), _lib.ptr(lvol), *st(lvol), *cvol.shape, c_box,
-               _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), len(plan['knots']), ctypes.c_double(S.PLANE[0] / 2),
-               ctypes.c_double(S.PLANE[1] / 2), _lib.ptr(tlab), S._DT[tlab.dtype], *st(tlab), *shape, c_region, S.RESTORE['crop'], int(vid),
-               _lib.ptr(out[0]), *st(out[0]), _lib.ptr(out[1]), *st(out[1]), _lib.ptr(cov), *st(cov), None,
-               (ctypes.c_double * 3)(*spacing), _lib.stream())
+    def tail():
+        return (_lib.ptr(lvol), *st(lvol), *cvol.shape, c_box, _lib.ptr(d_knots), _lib.ptr(d_basis), _lib.ptr(d_cum), len(plan['knots']),
+                ctypes.c_double(S.PLANE[0] / 2), ctypes.c_double(S.PLANE[1] / 2), _lib.ptr(tlab), S._DT[tlab.dtype], *st(tlab), *shape, c_region,
+                S.RESTORE['crop'], int(vid), _lib.ptr(out[0]), *st(out[0]), _lib.ptr(out[1]), *st(out[1]), _lib.ptr(cov), *st(cov), None,
+                (ctypes.c_double * 3)(*spacing), _lib.stream())
+
+    def launch(cdll=None):
+        args_ = (_lib.ptr(cvol), S._DT[cvol.dtype], *st(cvol)) + tail()
+        if cdll is None:
+            L.call('hv_restore_volume_sp', *args_)
+        else:
+            assert cdll.hv_restore_volume_sp(*args_) == 0
 
     launch()
     torch.cuda.synchronize()
@@ -97,6 +114,29 @@ def main():
     copy_ms = _timed(copy, args.reps)
     res = {'spacing': list(spacing), 'knots': len(plan['knots']), 'box': region, 'box_voxels': nvox, 'covered': covered, 'restore_ms': round(restore_ms, 4),
            'voxels_per_s': round(nvox / (restore_ms * 1e-3), 1), 'patient_ms': round(patient_ms, 4), 'copy_ms': round(copy_ms, 4)}
+    if args.baseline_lib:
+        B = ctypes.CDLL(args.baseline_lib)
+        B.hv_restore_volume_sp.restype = ctypes.c_int
+        B.hv_restore_volume_sp.argtypes = L.protos['hv_restore_volume_sp'][1]
+        launch()
+        ref_ct = out[0].clone()
+        launch(B)
+        torch.cuda.synchronize()
+        assert torch.equal(out[0], ref_ct)
+        for _ in range(2):                  # interleaved: this build, the baseline, this build, the baseline
+            t_new, t_old = _times(launch, args.reps), _times(lambda: launch(B), args.reps)
+        res.update(restore_ms=round(float(np.median(t_new)), 4), restore_ms_spread=round(max(t_new) - min(t_new), 4),
+                   restore_ms_baseline=round(float(np.median(t_old)), 4), restore_ms_baseline_spread=round(max(t_old) - min(t_old), 4))
+    if args.order == 3:
+        sub = cvol[box[6]:box[6] + box[3], box[7]:box[7] + box[4], box[8]:box[8] + box[5]]
+        coef = torch.empty(box[3], box[4], box[5], dtype=torch.float64, device='cuda')
+        pre = lambda: L.call('hv_spline_prefilter', _lib.ptr(sub), S._DT[sub.dtype], *st(sub), box[3], box[4], box[5], 0, ctypes.c_double(0.0),  # noqa: E731
+                             ctypes.c_double(1.0), _lib.ptr(coef), _lib.stream())
+        res['sub_box'] = [int(v) for v in box[3:6]]
+        res['prefilter_ms'] = round(_timed(pre, args.reps), 4)
+        res['restore3_ms'] = round(_timed(lambda: L.call('hv_restore_volume_spline', _lib.ptr(coef), *tail()), args.reps), 4)
+        res['patient3_ms'] = round(_timed(lambda: S.restore_patient(plan, crops, label=tlab, where='crop', return_covered=True, out=out, order=3),
+                                          args.reps), 4)
     if not args.no_cpu:
         import restore_ref as R
         import spacing_ref as SR

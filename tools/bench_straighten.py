@@ -9,7 +9,14 @@ parameters (plane 128 x 128, out_size (256, 256, 64), every kept vertebra reques
   cpu_mirror_s                            the same patient on the host: centroids per label (np.where), window, map_coordinates x 2,
                                           split cleanup, crops
 
-    timeout -k 10 600 python tools/bench_straighten.py [--reps 10] [--no-cpu] [--spacing a,b,c]
+  --order 3 adds: prefilter_ms (hv_spline_prefilter of the whole scan, window fused, its up to three launches together; per axis:
+                  rocprofv3 --kernel-trace --stats lists spline_axis_kernel<true> (axis 0), <false> (axis 1) and spline_axis2_kernel),
+                  coef_MB / coef_copy_ms (a plain device copy of the coefficient volume's bytes), sample3_ms (hv_straighten_sample_spline),
+                  patient3_ms (straighten_patient(order=3) end to end)
+  --baseline-lib PATH adds: sample_ms_baseline, the order-1 sampler of another build of the library (the parent commit's) loaded beside
+                  this one, timed in the same process, and sample_ms_spread / sample_ms_baseline_spread (max - min over the repeats)
+
+    timeout -k 10 600 python tools/bench_straighten.py [--reps 10] [--no-cpu] [--spacing a,b,c] [--order 3] [--baseline-lib libhvgan_parent.so]
 --spacing: millimetres per voxel of the same 512 x 512 x 400 voxel patient (default 1,1,1); the host mirror is skipped at other spacings.
 """
 import argparse
@@ -33,7 +40,7 @@ def _ev():
     return torch.cuda.Event(enable_timing=True)
 
 
-def _timed(fn, reps):
+def _times(fn, reps):
     ts = []
     for _ in range(reps):
         a, b = _ev(), _ev()
@@ -42,7 +49,11 @@ def _timed(fn, reps):
         b.record()
         b.synchronize()
         ts.append(a.elapsed_time(b))
-    return float(np.median(ts))
+    return ts
+
+
+def _timed(fn, reps):
+    return float(np.median(_times(fn, reps)))
 
 
 def cpu_mirror(ct, label, ids, out_size=(256, 256, 64)):
@@ -85,6 +96,8 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--spacing', default='1,1,1')
+    ap.add_argument('--order', type=int, default=1, choices=(1, 3))
+    ap.add_argument('--baseline-lib', default=None)
     args = ap.parse_args()
     spacing = S.check_spacing([float(v) for v in args.spacing.split(',')])
     c_spacing = (ctypes.c_double * 3)(*spacing)
@@ -134,6 +147,37 @@ def main():
            'sample_ms': round(sample_ms, 4), 'samples_per_s': float('%.4g' % (N * 128 * 128 / sample_ms * 1e3)), 'crop_ms': round(crop_ms, 4),
            'crop_out_MB': round(V * 256 * 256 * 64 * 9 / 1e6, 1), 'patient_ms': round(patient_ms, 3), 'h2d_ct_ms': round(h2d_ct, 3),
            'h2d_label_ms': round(h2d_lab, 3)}
+    if args.baseline_lib:
+        B = ctypes.CDLL(args.baseline_lib)
+        B.hv_straighten_sample_sp.restype = ctypes.c_int
+        B.hv_straighten_sample_sp.argtypes = L.protos['hv_straighten_sample_sp'][1]
+        sct_b = torch.empty_like(sct)
+        base = lambda: B.hv_straighten_sample_sp(_lib.ptr(tct), 1, *st(tct), _lib.ptr(tlab), 0, *st(tlab), X, Y, Z, _lib.ptr(d_knots),  # noqa: E731
+                                                 _lib.ptr(d_basis), N, 128, 128, int(plan['window']), wmin, wmax, _lib.ptr(sct_b), _lib.ptr(slab),
+                                                 _lib.ptr(pres), ctypes.c_size_t(pbytes), c_spacing, _lib.stream())
+        assert base() == 0
+        sample()
+        torch.cuda.synchronize()
+        assert torch.equal(sct, sct_b)
+        for _ in range(2):                  # interleaved: this build, the baseline, this build, the baseline
+            t_new, t_old = _times(sample, args.reps), _times(base, args.reps)
+        res.update(sample_ms=round(float(np.median(t_new)), 4), sample_ms_spread=round(max(t_new) - min(t_new), 4),
+                   sample_ms_baseline=round(float(np.median(t_old)), 4), sample_ms_baseline_spread=round(max(t_old) - min(t_old), 4))
+    if args.order == 3:
+        win = int(plan['window'])
+        coef = torch.empty(X, Y, Z, dtype=torch.float64, device=dev)
+        pre = lambda: L.call('hv_spline_prefilter', _lib.ptr(tct), 1, *st(tct), X, Y, Z, win, wmin, wmax, _lib.ptr(coef), _lib.stream())  # noqa: E731
+        res['prefilter_ms'] = round(_timed(pre, args.reps), 4)
+        res['coef_MB'] = round(coef.numel() * 8 / 1e6, 1)
+        dst = torch.empty_like(coef)
+        res['coef_copy_ms'] = round(_timed(lambda: dst.copy_(coef), args.reps), 4)
+        del dst
+        smp3 = lambda: L.call('hv_straighten_sample_spline', _lib.ptr(coef), _lib.ptr(tlab), 0, *st(tlab), X, Y, Z, _lib.ptr(d_knots),  # noqa: E731
+                              _lib.ptr(d_basis), N, 128, 128, _lib.ptr(sct), _lib.ptr(slab), _lib.ptr(pres), ctypes.c_size_t(pbytes), c_spacing,
+                              _lib.stream())
+        res['sample3_ms'] = round(_timed(smp3, args.reps), 4)
+        del coef
+        res['patient3_ms'] = round(_timed(lambda: S.straighten_patient(tct, tlab, ids, spacing=spacing, order=3), args.reps), 3)
     if not args.no_cpu and spacing == (1.0, 1.0, 1.0):
         res['cpu_mirror_s'] = round(cpu_mirror(ct, label, ids), 3)
     res['device'] = torch.cuda.get_device_name(0)
