@@ -8,6 +8,9 @@ Same entry points as the reference modules, on device tensors (csrc/gen_eval.hip
   process_images_batch(originals, fakes, view) / evaluate_experiments(originals, experiments, view)    main()'s two loops (:124-162), every
       validation vertebra x every experiment against the same original, through hv_gen_eval_batch: one launch sequence and one readback,
       what depends on the original alone computed once per item, every pair's values the bits process_images gives for it
+Beyond the reference (section 8 row f9, csrc/edt.hip): distance_transform(volume, value, spacing) -- the exact Euclidean distance transform --
+and surface_distances / surface_distances_batch(ori_seg, fake_seg, label, spacing): Hausdorff distance, HD95 and average symmetric surface
+distance of the vertebra's two outlines, in the units of `spacing`
 Volumes are [H, W, Z] with any strides: CT float32 / float64, labels uint8 / float32 / float64 (other dtypes are converted), device tensors
 or numpy arrays (uploaded), e.g. the float64 arrays infer.process_volume returns.  `label` is the vertebra id the reference parses from the
 file name.  File I/O, the vertebra_data.json selection and the .txt report stay on the host.
@@ -345,3 +348,132 @@ def evaluate_experiments(originals, experiments, view='sagittal'):
     fakes = [[rows[k][i] for k in names] for i in range(len(originals))]
     out, _ = _batch_outputs(originals, fakes, view, False, None)
     return {k: average_outputs(out[:, e], 'evaluate_experiments (experiment %r, volume %%d)' % (k,)) for e, k in enumerate(names)}
+
+
+# ------------------------------------------------------------------------------------------------ distance transform, surface distances
+# The shape part of the evaluation beyond overlap (csrc/edt.hip through hv_edt / hv_surface_distance): the exact
+# Euclidean distance transform (scipy.ndimage.distance_transform_edt) and MedPy's boundary metrics -- Hausdorff distance, its 95th percentile,
+# average symmetric surface distance -- in the units of `spacing` (millimetres per voxel, straighten.check_spacing: a scalar or three floats).
+SURFACE_KEYS = ('hd', 'hd95', 'assd', 'asd_ab', 'asd_ba', 'n_a', 'n_b')
+_SURFACE_AT = {'n_a': 0, 'n_b': 1, 'max_ab': 2, 'max_ba': 3, 'asd_ab': 4, 'asd_ba': 5, 'hd': 6, 'hd95': 7, 'assd': 8}
+
+
+def _spacing3(spacing):
+    from .straighten import check_spacing
+    sp = check_spacing(spacing)
+    return sp, (ctypes.c_double * 3)(*sp)
+
+
+def _label_volume(v, device):
+    t = torch.as_tensor(v)
+    if t.dtype == torch.bool:
+        t = t.to(torch.uint8)
+    t = _prep(t, device, _LABEL_DT, torch.float64)
+    if t.dim() != 3:
+        raise ValueError('generation_eval: a 3-D volume expected, got shape %s' % (tuple(t.shape),))
+    return t
+
+
+def _check_box(box, shape):
+    if box is None:
+        return None
+    try:
+        vals = [int(v) for v in box]
+    except (TypeError, ValueError):
+        raise ValueError('box: (lo0, lo1, lo2, n0, n1, n2) expected, got %r' % (box,))
+    if len(vals) != 6 or any(vals[a] < 0 or vals[3 + a] < 1 or vals[a] + vals[3 + a] > shape[a] for a in range(3)):
+        raise ValueError('box: (lo0, lo1, lo2, n0, n1, n2) inside the volume %s expected, got %r' % (tuple(shape), box))
+    return (ctypes.c_int * 6)(*vals)
+
+
+def distance_transform(mask_or_volume, value=0, spacing=1.0, out=None, box=None, return_status=False):
+    """The exact Euclidean distance of every voxel to the nearest voxel equal to `value`, scipy.ndimage.distance_transform_edt(v != value,
+    sampling=spacing): for a mask and value 0 the distance to the background.  -> device float64 tensor of the volume's shape (`out`, if
+    given: contiguous float64 of that shape on the device).  box (lo0, lo1, lo2, n0, n1, n2) limits the voxels written and the voxels
+    considered (a fresh output is NaN outside it).  No voxel equal to `value`: every distance is +inf; return_status also returns the device
+    int32 word that says so (1), without a synchronisation."""
+    sp, csp = _spacing3(spacing)
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError('value: a number expected, got %r' % (value,))
+    meta = torch.as_tensor(mask_or_volume)
+    if meta.dim() != 3:
+        raise ValueError('generation_eval: a 3-D volume expected, got shape %s' % (tuple(meta.shape),))
+    cbox = _check_box(box, meta.shape)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != tuple(meta.shape)
+                            or not out.is_contiguous()):
+        raise ValueError('out: a contiguous float64 tensor of shape %s expected' % (tuple(meta.shape),))
+    dev = _device(mask_or_volume, out)
+    v = _label_volume(mask_or_volume, dev)
+    _lib.require_gpu(v, out)
+    L = _lib.get()
+    A0, A1, A2 = v.shape
+    if out is None:
+        out = torch.empty(A0, A1, A2, dtype=torch.float64, device=dev) if box is None else \
+            torch.full((A0, A1, A2), float('nan'), dtype=torch.float64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws, wsz = ops._ws(L.size('hv_edt_workspace_bytes', A0, A1, A2), dev, slot=3)
+    L.call('hv_edt', _lib.ptr(v), _DT[v.dtype], *[ctypes.c_longlong(s) for s in v.stride()], A0, A1, A2, ctypes.c_double(float(value)), csp,
+           cbox, _lib.ptr(out), _lib.ptr(status), _lib.ptr(ws), wsz, _lib.stream())
+    return (out, status) if return_status else out
+
+
+def _launch_surface(ori_seg, fake_seg, label, csp, restrict, out):
+    """Queue one hv_surface_distance on the current stream; `out` (16 doubles) is a device view written by it."""
+    L = _lib.get()
+    dev = out.device
+    a, b = _pair(ori_seg, fake_seg, dev, _LABEL_DT, torch.float64)
+    A0, A1, A2 = a.shape
+    ws, wsz = ops._ws(L.size('hv_surface_distance_workspace_bytes', A0, A1, A2), dev, slot=3)
+    L.call('hv_surface_distance', _lib.ptr(a), _lib.ptr(b), _DT[a.dtype], *[ctypes.c_longlong(s) for s in a.stride()], A0, A1, A2,
+           ctypes.c_double(float(label)), csp, 1 if restrict else 0, _lib.ptr(out), _lib.ptr(ws), wsz, _lib.stream())
+
+
+def _surface_dict(o, what):
+    if o[9] != 0 or o[10] != 0:
+        raise ValueError('%s: %s has no voxel of the label, the surface distances are undefined'
+                         % (what, ' and '.join(n for n, f in (('the original', o[9]), ('the synthesized volume', o[10])) if f != 0)))
+    res = {k: float(o[_SURFACE_AT[k]]) for k in SURFACE_KEYS}
+    res['n_a'], res['n_b'] = int(o[0]), int(o[1])
+    return res
+
+
+def _bool_mask(v):
+    t = torch.as_tensor(v)
+    return t.to(torch.uint8) if t.dtype == torch.bool else v
+
+
+def surface_distances(ori_seg, fake_seg, label=1, spacing=1.0, restrict=True, return_raw=False):
+    """Boundary metrics of vertebra `label` between two label volumes (A = ori_seg == label, B = fake_seg == label; surface = the voxels of a
+    set with a face neighbour outside it): -> {'hd': Hausdorff distance, 'hd95': 95th percentile of both directed distance lists joined
+    (numpy's linear rule), 'assd': average symmetric surface distance, 'asd_ab' / 'asd_ba': the directed means, 'n_a' / 'n_b': the surface
+    counts}, distances in the units of `spacing`.  One readback (16 doubles; return_raw returns them too).  restrict=False runs the two
+    distance transforms over the whole volume instead of the sets' bounding box: the same bits, more work.  Raises ValueError if either
+    set is empty."""
+    _, csp = _spacing3(spacing)
+    ori_seg, fake_seg = _bool_mask(ori_seg), _bool_mask(fake_seg)
+    dev = _device(ori_seg, fake_seg)
+    out = torch.empty(16, dtype=torch.float64, device=dev)
+    _launch_surface(ori_seg, fake_seg, label, csp, restrict, out)
+    o = out.cpu().numpy()
+    if return_raw:
+        return (_surface_dict(o, 'surface_distances') if o[9] == 0 and o[10] == 0 else None), o
+    return _surface_dict(o, 'surface_distances')
+
+
+def surface_distances_batch(pairs, spacing=1.0, restrict=True):
+    """surface_distances for an iterable of (ori_seg, fake_seg, label): every pair is queued on the device, then one readback.  `spacing`
+    holds for all pairs.  -> list of the dicts surface_distances returns, each the bits of the single
+    call.  Raises ValueError, naming the pair, if a set is empty."""
+    pairs = [tuple(p) for p in pairs]
+    for i, p in enumerate(pairs):
+        if len(p) != 3:
+            raise ValueError('surface_distances_batch: (ori_seg, fake_seg, label) expected, pair %d has %d entries' % (i, len(p)))
+    _, csp = _spacing3(spacing)
+    if not pairs:
+        return []
+    dev = _device(*[v for p in pairs for v in p[:2]])
+    outs = torch.empty(len(pairs), 16, dtype=torch.float64, device=dev)
+    for i, (a, b, label) in enumerate(pairs):
+        _launch_surface(_bool_mask(a), _bool_mask(b), label, csp, restrict, outs[i])
+    o = outs.cpu().numpy()
+    return [_surface_dict(o[i], 'surface_distances_batch (pair %d)' % i) for i in range(len(pairs))]

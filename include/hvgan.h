@@ -953,6 +953,35 @@ int hv_svm_predict(const double* X, int G, int N, int F, int K, const int* prese
                    const double* b, const int* info, int* pred, double* decision, int* votes, double* contrib, void* stream);
 int hv_svm_features(const double* records, int N, int first_view, int F, double* X, void* stream);
 
+/* ---- exact Euclidean distance transform and the surface-distance metrics on it (csrc/edt.hip).  The reference has
+ * no such metric: the transform is scipy.ndimage.distance_transform_edt, the metric definitions are MedPy's (metric.binary hd / hd95 / asd / assd).
+ * hv_edt: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order), dtype HV_DT_U8 / F32 / F64.  T = {vol ==
+ *   value}.  out (device, [A0][A1][A2] contiguous doubles): the distance of every voxel to the nearest voxel of T with the axes scaled by spacing[3]
+ *   (HOST pointer, copied into the kernel arguments), i.e. distance_transform_edt(vol != value, sampling=spacing).  One pass per axis over squared
+ *   distances: integers at unit spacing (int32 in the workspace while A0^2 + A1^2 + A2^2 < 2^31, else int64 in out's own slots), else the double sum
+ *   ((s0 d0)^2 + (s1 d1)^2) + (s2 d2)^2; one correctly rounded square root per voxel.  box (HOST, NULL = the whole volume): { lo0, lo1, lo2, n0, n1,
+ *   n2 } limits both the voxels written and the part of T considered; out is not touched outside it.  status (device int): 1 if T (inside the box)
+ *   is empty -- every voxel written is then +inf -- else 0.  workspace: 16-byte aligned, hv_edt_workspace_bytes(A0, A1, A2) bytes.
+ *   HV_ERR_ARG: a NULL pointer (box excepted), a non-positive size, an unknown dtype, a spacing that is not positive and finite, a box that is
+ *   empty or leaves the volume, out not 8-byte or workspace not 16-byte aligned, a workspace smaller than queried; HV_ERR_UNSUPPORTED: an A1 or A2
+ *   line above 64 KiB of carried values (16 384 at unit spacing, 8 192 otherwise), more than 2^30 voxels.  Nothing is launched or written then.
+ * hv_surface_distance: a, b label volumes of one shape, dtype and stride triple (rules as above); A = {a == value}, B = {b == value}.  A voxel of a
+ *   set is a surface voxel if one of its six face neighbours is not in the set, a neighbour outside the volume counting as such (X & ~binary_erosion(
+ *   X, generate_binary_structure(3, 1), border_value=0)).  out[16] (device): [0] n_a, [1] n_b the surface counts, [2] max_ab = max over p in S_A of
+ *   d(p, S_B), [3] max_ba, [4] asd_ab, [5] asd_ba the directed means, [6] hd = max([2], [3]), [7] hd95 = the 95th percentile (numpy's linear rule:
+ *   v = (n - 1) 0.95, lo / hi the order statistics floor(v) and floor(v) + 1, t = v - floor(v), lo + (hi - lo) t for t < 0.5, else hi - (hi - lo)
+ *   (1 - t)) of both directed lists joined, [8] assd = ([4] + [5]) / 2, [9] 1 if S_A is empty, [10] 1 if S_B is empty (then [2..8] are NaN),
+ *   [11..15] 0.  restricted 1: the two transforms run inside the bounding box of A | B, found on the device (every surface voxel lies inside it, so
+ *   the distances are exact); 0: over the whole volume; the 16 doubles are the same bits either way.  Sums are per-slice partials (axis 0) folded in
+ *   ascending order by one lane: the same bits on every run.  No host synchronisation; workspace 16-byte aligned,
+ *   hv_surface_distance_workspace_bytes bytes.  HV_ERR_ARG / HV_ERR_UNSUPPORTED as for hv_edt, and HV_ERR_ARG for restricted other than 0 / 1. */
+size_t hv_edt_workspace_bytes(int A0, int A1, int A2);
+int hv_edt(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, const double* spacing,
+           const int* box, double* out, int* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t hv_surface_distance_workspace_bytes(int A0, int A1, int A2);
+int hv_surface_distance(const void* a, const void* b, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value,
+                        const double* spacing, int restricted, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
