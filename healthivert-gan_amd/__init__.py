@@ -13,3 +13,4 @@ from . import engine, optim, ddp, step_runner, profiler, evaluation, eval_metric
 from . import models  # noqa: E402,F401  (drop-in mirror of the reference's `models` package)
 from . import straighten  # noqa: E402,F401  (stage 1: centroids, straightening, per-vertebra crops)
 from . import generation_eval  # noqa: E402,F401  (generation-quality evaluation of synthesized volumes)
+from . import components  # noqa: E402,F401  (3-D connected components, clean-up of synthesized labels)

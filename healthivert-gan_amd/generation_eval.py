@@ -10,7 +10,8 @@ Same entry points as the reference modules, on device tensors (csrc/gen_eval.hip
       what depends on the original alone computed once per item, every pair's values the bits process_images gives for it
 Beyond the reference (section 8 row f9, csrc/edt.hip): distance_transform(volume, value, spacing) -- the exact Euclidean distance transform --
 and surface_distances / surface_distances_batch(ori_seg, fake_seg, label, spacing): Hausdorff distance, HD95 and average symmetric surface
-distance of the vertebra's two outlines, in the units of `spacing`
+distance of the vertebra's two outlines, in the units of `spacing`; largest_component=True first reduces both sets to their largest 3-D
+component (components.py, csrc/ccl3d.hip; row f10), so that a stray island of a slice-wise synthesized label does not set the distances
 Volumes are [H, W, Z] with any strides: CT float32 / float64, labels uint8 / float32 / float64 (other dtypes are converted), device tensors
 or numpy arrays (uploaded), e.g. the float64 arrays infer.process_volume returns.  `label` is the vertebra id the reference parses from the
 file name.  File I/O, the vertebra_data.json selection and the .txt report stay on the host.
@@ -442,17 +443,38 @@ def _bool_mask(v):
     return t.to(torch.uint8) if t.dtype == torch.bool else v
 
 
-def surface_distances(ori_seg, fake_seg, label=1, spacing=1.0, restrict=True, return_raw=False):
+def _largest_components(ori_seg, fake_seg, label, connectivity, dev):
+    """Both volumes with every 3-D component of `label` but the largest one erased (components.clean_label; csrc/ccl3d.hip), queued on the
+    current stream: contiguous device volumes of one dtype, nothing read back."""
+    from . import components
+    a, b = _pair(ori_seg, fake_seg, dev, _LABEL_DT, torch.float64)
+    fill = 0 if float(label) != 0.0 else 1
+    tables = torch.empty(2, 8, dtype=torch.int32, device=dev)
+    return tuple(components._clean(v, label, connectivity, 0, True, False, None, fill, tables[i]) for i, v in enumerate((a, b)))
+
+
+def _check_largest(largest_component, connectivity):
+    if largest_component:
+        from . import components
+        components._check_connectivity(connectivity)
+
+
+def surface_distances(ori_seg, fake_seg, label=1, spacing=1.0, restrict=True, return_raw=False, largest_component=False, connectivity=1):
     """Boundary metrics of vertebra `label` between two label volumes (A = ori_seg == label, B = fake_seg == label; surface = the voxels of a
     set with a face neighbour outside it): -> {'hd': Hausdorff distance, 'hd95': 95th percentile of both directed distance lists joined
     (numpy's linear rule), 'assd': average symmetric surface distance, 'asd_ab' / 'asd_ba': the directed means, 'n_a' / 'n_b': the surface
     counts}, distances in the units of `spacing`.  One readback (16 doubles; return_raw returns them too).  restrict=False runs the two
-    distance transforms over the whole volume instead of the sets' bounding box: the same bits, more work.  Raises ValueError if either
-    set is empty."""
+    distance transforms over the whole volume instead of the sets' bounding box: the same bits, more work.  largest_component: both sets are
+    first reduced to their largest 3-D component (connectivity 1 / 2 / 3: 6, 18 or 26 neighbours; equal sizes: the first in raster order) on
+    the device, so that a stray island of a slice-wise synthesized label does not set the Hausdorff distance; no extra readback.  Raises
+    ValueError if either set is empty."""
     _, csp = _spacing3(spacing)
+    _check_largest(largest_component, connectivity)
     ori_seg, fake_seg = _bool_mask(ori_seg), _bool_mask(fake_seg)
     dev = _device(ori_seg, fake_seg)
     out = torch.empty(16, dtype=torch.float64, device=dev)
+    if largest_component:
+        ori_seg, fake_seg = _largest_components(ori_seg, fake_seg, label, connectivity, dev)
     _launch_surface(ori_seg, fake_seg, label, csp, restrict, out)
     o = out.cpu().numpy()
     if return_raw:
@@ -460,20 +482,24 @@ def surface_distances(ori_seg, fake_seg, label=1, spacing=1.0, restrict=True, re
     return _surface_dict(o, 'surface_distances')
 
 
-def surface_distances_batch(pairs, spacing=1.0, restrict=True):
-    """surface_distances for an iterable of (ori_seg, fake_seg, label): every pair is queued on the device, then one readback.  `spacing`
-    holds for all pairs.  -> list of the dicts surface_distances returns, each the bits of the single
+def surface_distances_batch(pairs, spacing=1.0, restrict=True, largest_component=False, connectivity=1):
+    """surface_distances for an iterable of (ori_seg, fake_seg, label): every pair is queued on the device, then one readback.  `spacing`,
+    largest_component and connectivity hold for all pairs.  -> list of the dicts surface_distances returns, each the bits of the single
     call.  Raises ValueError, naming the pair, if a set is empty."""
     pairs = [tuple(p) for p in pairs]
     for i, p in enumerate(pairs):
         if len(p) != 3:
             raise ValueError('surface_distances_batch: (ori_seg, fake_seg, label) expected, pair %d has %d entries' % (i, len(p)))
     _, csp = _spacing3(spacing)
+    _check_largest(largest_component, connectivity)
     if not pairs:
         return []
     dev = _device(*[v for p in pairs for v in p[:2]])
     outs = torch.empty(len(pairs), 16, dtype=torch.float64, device=dev)
     for i, (a, b, label) in enumerate(pairs):
-        _launch_surface(_bool_mask(a), _bool_mask(b), label, csp, restrict, outs[i])
+        a, b = _bool_mask(a), _bool_mask(b)
+        if largest_component:
+            a, b = _largest_components(a, b, label, connectivity, dev)
+        _launch_surface(a, b, label, csp, restrict, outs[i])
     o = outs.cpu().numpy()
     return [_surface_dict(o[i], 'surface_distances_batch (pair %d)' % i) for i in range(len(pairs))]

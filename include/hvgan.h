@@ -982,6 +982,41 @@ size_t hv_surface_distance_workspace_bytes(int A0, int A1, int A2);
 int hv_surface_distance(const void* a, const void* b, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value,
                         const double* spacing, int restricted, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- 3-D connected components of a volume, and the clean-up of a synthesized label volume on them (csrc/ccl3d.hip).
+ * The reference filters components per 2-D slice only (hv_slice_components, hv_depedicle); these are scipy.ndimage.label / binary_fill_holes.
+ * The volume is described as for hv_edt: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order), dtype
+ * HV_DT_U8 / F32 / F64.  Foreground: vol == value (mode HV_CCL_EQ) or vol != value (HV_CCL_NE; with value 0 scipy's label(vol)).  connectivity
+ * 1 / 2 / 3 = generate_binary_structure(3, c): 6, 18 or 26 neighbours.
+ * hv_label3d: labels (device, contiguous int32 [A0][A1][A2]): 0 = background, 1..n the components in ascending order of the smallest raster index
+ *   (i*A1 + j)*A2 + k of their voxels -- scipy.ndimage.label's numbering.  table (device int32 [4 + table_cap]): [0] n, [1] the label of the largest
+ *   component (equal sizes: the lowest label, np.argmax(np.bincount(labels.ravel())[1:]) + 1; 0 if n = 0), [2] its size, [3] status (bit 0: no
+ *   foreground voxel), [4 + i] the size of component i + 1 for i < min(n, table_cap) and 0 from n on.  [0..2] are exact whatever table_cap (>= 0) is.
+ *   Tiles of hv_label3d_tile's shape are labelled in LDS, their seams joined by lock-free unions in global memory, the roots ranked by a prefix
+ *   sum, the sizes counted by integer atomics: the same bytes on every run.  No host synchronisation.
+ * hv_clean_components: out (dtype of vol, strides os0..os2) = vol with the foreground voxels of dropped components set to `fill`; every other voxel
+ *   is copied unchanged.  A component is kept iff it has >= min_size voxels (min_size <= 1: no size rule; the reference's rule drops < min_size) and,
+ *   with keep_largest = 1, is the largest one ([1] above).  out may be vol itself with the same strides: the launch that writes out then does not
+ *   read vol.  table (device int32 [4]): [0..3] as above, of the labelling before the filter.
+ * hv_fill_holes: the voxels that are not foreground and from which no face of the volume is reached through 6-connected non-foreground voxels
+ *   become `fill` in out (scipy.ndimage.binary_fill_holes with the default structure); everything else is copied, out as above.  table (device
+ *   int32 [4]): [0] the number of holes (6-connected components filled), [2] the voxels filled, [1] and [3] 0.
+ * hv_label3d_tile (host only): dims[3] = the tile shape of the first pass.  hv_label3d_workspace_bytes: the workspace of all three entries, 16-byte
+ *   aligned: 4 bytes per voxel of parents, 4 per voxel + 4 of sizes, 4 per voxel of labels (used by the two clean-ups), 4 per 1 024 voxels of
+ *   block counts, each of the four rounded up to 16, + 16: 12 bytes per voxel in all.
+ * Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer, a non-positive size, an unknown dtype or mode, connectivity
+ *   outside 1..3, keep_largest other than 0 / 1, table_cap < 0, labels or table not 4-byte aligned, a workspace that is not 16-byte aligned or smaller
+ *   than queried, out == vol with other strides; HV_ERR_UNSUPPORTED: more than 2^30 voxels (raster indices are int32). */
+enum { HV_CCL_EQ = 0, HV_CCL_NE = 1 };
+size_t hv_label3d_workspace_bytes(int A0, int A1, int A2);
+int hv_label3d_tile(int* dims);
+int hv_label3d(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode,
+               int connectivity, int* labels, int* table, int table_cap, void* workspace, size_t workspace_bytes, void* stream);
+int hv_clean_components(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode,
+                        int connectivity, int min_size, int keep_largest, double fill, void* out, long long os0, long long os1, long long os2,
+                        int* table, void* workspace, size_t workspace_bytes, void* stream);
+int hv_fill_holes(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode, double fill,
+                  void* out, long long os0, long long os1, long long os2, int* table, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
