@@ -7,7 +7,8 @@ scipy.ndimage.label / binary_fill_holes bit for bit, on volumes that stay reside
   label(vol, value=None, connectivity=1)                  -> (labels int32, table) device tensors, no synchronisation
   component_sizes(vol, value=None, connectivity=1)        -> numpy int64 sizes of the n components (one readback)
   keep_largest_component / remove_small_components / fill_holes(vol, value, ...)        -> the cleaned device volume
-  clean_label(vol, value, ...)                            the filter, then optionally the hole fill, queued back to back
+  clean_label(vol, value, ...)                            the filter, then optionally the hole fill, queued back to back; closing_mm /
+                                                          opening_mm / spacing: morphology.open_label / close_label run first
   clean_labels(volumes, values, ...)                      the same for a list (the 13 crops of a patient), one readback of the tables
 Volumes are 3-D with any strides, uint8 / float32 / float64 (bool masks become uint8, other dtypes float64), device tensors or numpy arrays
 (uploaded).  connectivity 1 / 2 / 3 is generate_binary_structure(3, c): 6, 18 or 26 neighbours.  table: int32, [0] the number of components
@@ -159,31 +160,52 @@ def _prepare(vol, value, connectivity, out):
     return conn, val, dtype
 
 
-def _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table):
-    """clean_label's checks and launches; `table`: a device int32 [8] view (the filter's four words, then the hole fill's)."""
+def _check_morph(closing_mm, opening_mm, spacing):
+    """-> None when neither radius is given (no morphology code runs), else (opening radius or None, closing radius or None, spacing), checked."""
+    if closing_mm is None and opening_mm is None:
+        return None
+    from . import morphology as M
+    return (None if opening_mm is None else M._check_radius(opening_mm), None if closing_mm is None else M._check_radius(closing_mm),
+            M._check_spacing(spacing))
+
+
+def _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table, morph=None):
+    """clean_label's checks and launches; `table`: a device int32 [8] view (the filter's four words, then the hole fill's); `morph`: what
+    _check_morph returned."""
     conn, val, _ = _prepare(vol, value, connectivity, out)
     ms = _check_min_size(min_size)
     fl = _check_value(fill, 'fill')
     v = _upload(vol, table.device)
     out = _out_for(v, out)
+    if morph is not None:                        # the opening first (bridges), then the closing (gaps), then in place on `out`
+        from . import morphology as M
+        for op, radius in ((M.OPEN, morph[0]), (M.CLOSE, morph[1])):
+            if radius is not None:
+                v = M._label_op(op, v, val, radius, morph[2], fl, fl, out)
     _launch_clean(v, val, conn, ms, bool(keep_largest), fl, out, table[:4])
     if fill_holes:
         _launch_fill(out, val, val, out, table[4:])
     return out
 
 
-def clean_label(vol, value, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, out=None, fill=0, return_table=False):
+def clean_label(vol, value, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, out=None, fill=0, return_table=False,
+                closing_mm=None, opening_mm=None, spacing=(1, 1, 1)):
     """The 3-D clean-up of label `value` in a (synthesized) label volume: components of vol == value with fewer than min_size voxels are
     dropped (a component of exactly min_size voxels stays: the reference's rule for its 2-D filter), with keep_largest all but the largest
     one; their voxels become `fill`.  With fill_holes the cavities of what is left -- voxels from which no face of the volume is reached
     through face neighbours outside the label -- are then set to `value` (binary_fill_holes).  Every other voxel, other labels included, is
     copied.  -> the device volume (`out`: a device tensor of the volume's dtype and shape, `vol` itself for in place); return_table adds the
-    device int32 [4] table of the labelling before the filter.  Nothing is read back."""
+    device int32 [4] table of the labelling before the filter.  Nothing is read back.
+    opening_mm / closing_mm (radii in the units of `spacing`, the voxel size along the three axes): before all of this, vol == value is opened
+    and / or closed by that ball (morphology.open_label, then morphology.close_label, border_value 0, with `fill` as both the opening's fill
+    and the background the closing may grow into): the opening cuts thin bridges to a neighbour, the closing joins fragments that a gap
+    narrower than two radii separates from the body, so that keep_largest keeps them.  The table is then the labelling after them."""
     _prepare(vol, value, connectivity, out)
     _check_min_size(min_size)
     _check_value(fill, 'fill')
+    morph = _check_morph(closing_mm, opening_mm, spacing)
     table = torch.empty(8, dtype=torch.int32, device=_device(vol, out))
-    out = _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table)
+    out = _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table, morph)
     return (out, table[:4]) if return_table else out
 
 
@@ -209,9 +231,11 @@ def fill_holes(vol, value, out=None, return_table=False):
     return (out, table) if return_table else out
 
 
-def clean_labels(volumes, values, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, fill=0):
+def clean_labels(volumes, values, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, fill=0, closing_mm=None, opening_mm=None,
+                 spacing=(1, 1, 1)):
     """clean_label for a list of volumes and their labels (one value for all, or one per volume): every call is queued on the stream, then
-    the tables are read back once.  -> (the device volumes, each the bytes of the single call; numpy int32 [V][4] tables)."""
+    the tables are read back once.  -> (the device volumes, each the bytes of the single call; numpy int32 [V][4] tables).  closing_mm /
+    opening_mm / spacing as for clean_label, the same for every volume."""
     volumes = list(volumes)
     if isinstance(values, (int, float, np.integer, np.floating)) and not isinstance(values, bool):
         values = [values] * len(volumes)
@@ -222,9 +246,10 @@ def clean_labels(volumes, values, connectivity=1, min_size=0, keep_largest=True,
         _prepare(v, val, connectivity, None)
     _check_min_size(min_size)
     _check_value(fill, 'fill')
+    morph = _check_morph(closing_mm, opening_mm, spacing)
     if not volumes:
         return [], np.zeros((0, 4), dtype=np.int32)
     tables = torch.empty(len(volumes), 8, dtype=torch.int32, device=_device(*volumes))
-    outs = [_clean(v, val, connectivity, min_size, keep_largest, fill_holes, None, fill, tables[i])
+    outs = [_clean(v, val, connectivity, min_size, keep_largest, fill_holes, None, fill, tables[i], morph)
             for i, (v, val) in enumerate(zip(volumes, values))]
     return outs, tables.cpu().numpy()[:, :4]

@@ -1017,6 +1017,46 @@ int hv_clean_components(const void* vol, int dtype, long long s0, long long s1, 
 int hv_fill_holes(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode, double fill,
                   void* out, long long os0, long long os1, long long os2, int* table, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- 3-D binary morphology of a volume, and a mask written back into a label volume (csrc/morph.hip).  The reference
+ * only dilates 2-D masks (skimage dilation(seg, square(2)) in its cv2 mask scripts); these are scipy.ndimage.binary_dilation / binary_erosion /
+ * binary_opening / binary_closing, bit for bit.  The volume is described as for hv_label3d: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 +
+ * k*s2] (strides in elements, any order), dtype HV_DT_U8 / F32 / F64, foreground vol == value (HV_CCL_EQ) or vol != value (HV_CCL_NE).  out: a
+ * uint8 mask of 0 / 1, element (i, j, k) at out[i*os0 + j*os1 + k*os2]; it must not overlap vol.  op: HV_MORPH_DILATE / ERODE / OPEN (erosion then
+ * dilation) / CLOSE (dilation then erosion); border_value 0 / 1 is what the voxels outside the volume hold, in both halves of a compound op.
+ * hv_morph_ball: the structuring element is the set of integer offsets o with ((s0 o0)^2 + (s1 o1)^2) + (s2 o2)^2 <= radius * radius, float64 in
+ *   this order (hv_edt's ordered sum), s = spacing[3] (HOST pointer); radius 0 is the identity.  One pass per axis; no distance is formed: the
+ *   passes carry the step count to the nearest member along axis 0 and the remaining reach along axis 2 (uint8 while both stay <= 254 steps, else
+ *   uint16), every line scan is bounded by the largest step count d with (s_a d)^2 <= radius^2, the erosion is the dilation of the complement.
+ * hv_morph_struct: the structuring element is generate_binary_structure(3, connectivity) (7 / 19 / 27 cells), applied `iterations` times; OPEN /
+ *   CLOSE run `iterations` times the first half, then `iterations` times the second (scipy's iterations=).  One launch per iteration: a 3 x 3 x 3
+ *   stencil over a tile of hv_morph_tile's shape with a one-voxel halo in LDS.  iterations < 1 (scipy: until nothing changes) is refused.
+ * hv_morph_merge: out (dtype of vol, strides os0..os2) = vol with a mask (uint8, strides ms0..ms2, set = non-zero) written back.  HV_MORPH_GROW
+ *   (after a dilation / closing): a voxel whose mask is set and whose value is `background` becomes `value`; HV_MORPH_SHRINK (after an erosion /
+ *   opening): a voxel that holds `value` and whose mask is 0 becomes `fill`.  Every other voxel is copied bit for bit, so other labels are never
+ *   overwritten.  out may be vol itself with the same strides.
+ * hv_morph_tile (host only): dims[3] = the stencil's tile shape.  hv_morph_workspace_bytes (host only; spacing NULL = {1, 1, 1}): the workspace of
+ *   hv_morph_ball at that radius -- one count per voxel (1 or 2 bytes) and one byte per voxel of intermediate mask, each rounded up to 16; with
+ *   radius 0 (2 bytes per voxel) it is what hv_morph_struct needs.  0 for arguments hv_morph_ball refuses.
+ * No host synchronisation, no atomics; the same bytes on every run, whatever the workspace held.  Refusals, before any launch and with nothing
+ * written -- HV_ERR_ARG: a NULL pointer, a non-positive size, an unknown dtype, mode, op or rule, border_value other than 0 / 1, a radius that is
+ *   negative, not finite or whose square is not finite, a spacing that is not positive and finite, iterations < 1, connectivity outside 1..3, a
+ *   workspace that is not 16-byte aligned or smaller than queried, out == vol with other strides (merge); HV_ERR_UNSUPPORTED: more than 2^30
+ *   voxels; hv_morph_ball only: A1 or A2 above 32 768 (a line of 16-bit counts must fit 64 KiB of LDS), a reach above 65 534 steps along axis 0
+ *   or 2 (radius / spacing, capped by the extent). */
+enum { HV_MORPH_DILATE = 0, HV_MORPH_ERODE = 1, HV_MORPH_OPEN = 2, HV_MORPH_CLOSE = 3 };
+enum { HV_MORPH_GROW = 0, HV_MORPH_SHRINK = 1 };
+size_t hv_morph_workspace_bytes(int A0, int A1, int A2, double radius, const double* spacing);
+int hv_morph_tile(int* dims);
+int hv_morph_ball(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode, int op,
+                  double radius, const double* spacing, int border_value, void* out, long long os0, long long os1, long long os2, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int hv_morph_struct(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value, int mode, int op,
+                    int connectivity, int iterations, int border_value, void* out, long long os0, long long os1, long long os2, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int hv_morph_merge(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const void* mask, long long ms0,
+                   long long ms1, long long ms2, int rule, double value, double background, double fill, void* out, long long os0, long long os1,
+                   long long os2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
