@@ -1057,6 +1057,41 @@ int hv_morph_merge(const void* vol, int dtype, long long s0, long long s1, long 
                    long long ms1, long long ms2, int rule, double value, double background, double fill, void* out, long long os0, long long os1,
                    long long os2, void* stream);
 
+/* ---- per-label intensity statistics and order statistics of volumes (csrc/labelstats.hip).  The reference has no
+ * counterpart: the definitions are scipy.ndimage.sum_labels / minimum / maximum / center_of_mass / find_objects and np.percentile (linear).
+ * hv_label_stats: vol holds V intensity volumes [V][A0][A1][A2], element (v; i, j, k) at vol[v*sv + i*s0 + j*s1 + k*s2] (strides in elements, any
+ *   order), vol_dtype HV_DT_U8 / I16 / F32 / F64.  label: the same logical shape with its own strides, any HV_DT_* code, values integers in [0, 255]
+ *   as for hv_straighten_stats; a voxel whose label is not such a value sets HV_LS_BAD_LABEL in every record of its volume and is counted nowhere.
+ *   mask (may be NULL): uint8 with its own strides; a voxel counts only where mask != 0.  labels[S] (HOST, 1 <= S <= HV_LS_MAX_LABELS, distinct
+ *   values in [0, 255], 0 allowed) and q[Q] (HOST, 0 <= Q <= HV_LS_MAX_Q percentiles in [0, 100]; may be NULL for Q = 0) are copied into the kernel
+ *   arguments.  out (device, 8-byte aligned): [V][S][HV_LS_REC] doubles, per (volume, listed label):
+ *     [HV_LS_COUNT] the voxel count n; [HV_LS_SUM], [HV_LS_SUMSQ] the sums of v and of v*v -- for U8 / I16 the EXACT int64 sums, stored as the
+ *     int64's bit pattern in the double's slot (2^30 voxels x 32768^2 = 2^60 keeps the squares inside int64); for F32 / F64 doubles, the sum of
+ *     (double)v and of fl((double)v * (double)v) in an order fixed by the shape (16^3 tiles in raster order; the strides do not enter);
+ *     [HV_LS_MIN], [HV_LS_MAX] (+inf / -inf for n = 0); [HV_LS_COORD + a] the sum of index a over the voxels, an exact integer while n * (A_a - 1)
+ *     <= 2^53 (every volume with A_a <= 2^23); [HV_LS_LO + a], [HV_LS_HI + a] the inclusive bounding box (n = 0: lo = A_a, hi = -1);
+ *     [HV_LS_STATUS] the OR of HV_LS_BAD_LABEL, HV_LS_NONFINITE (a NaN or +-inf met inside this label: it is still counted, summed and ranked by
+ *     its key, so the floating fields are meaningless), HV_LS_EMPTY (n = 0); [HV_LS_STATUS + 1] 0; [HV_LS_ORDER + 2t], [HV_LS_ORDER + 2t + 1] for
+ *     t < Q the order statistics x[lo], x[hi] of the label's values with vi = (n - 1) * (q[t] / 100) in float64 (numpy's virtual index), lo =
+ *     floor(vi), hi = lo + 1, and lo = hi = n - 1 once vi >= n - 1; NaN for n = 0.  The fields from HV_LS_ORDER + 2Q on are NOT written.
+ *   Order statistics come from a radix select over an order-preserving key (16 bits for U8 / I16, 32 for F32, 64 for F64: 2 / 4 / 8 passes over
+ *   the volumes, none for Q = 0); -0.0 sorts below +0.0.  Only integer atomics; floating sums have a fixed order: the same bytes on every run,
+ *   for any strides, single or stacked, whatever the workspace held.  No host synchronisation.  workspace: 16-byte aligned,
+ *   hv_label_stats_workspace_bytes(V, A0, A1, A2, S, Q) bytes (0 for sizes the entry refuses).
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (mask excepted; q for Q = 0), a non-positive size, an
+ *   unknown dtype, S outside 1..HV_LS_MAX_LABELS, Q outside 0..HV_LS_MAX_Q, a label value outside [0, 255] or listed twice, a q outside [0, 100]
+ *   or not finite, out not 8-byte aligned, a workspace that is not 16-byte aligned or smaller than queried; HV_ERR_UNSUPPORTED: more than 2^30
+ *   voxels per volume, V > 65535. */
+enum { HV_LS_REC = 32, HV_LS_MAX_LABELS = 64, HV_LS_MAX_Q = 8 };
+enum { HV_LS_COUNT = 0, HV_LS_SUM = 1, HV_LS_SUMSQ = 2, HV_LS_MIN = 3, HV_LS_MAX = 4, HV_LS_COORD = 5, HV_LS_LO = 8, HV_LS_HI = 11, HV_LS_STATUS = 14,
+       HV_LS_ORDER = 16 };
+enum { HV_LS_BAD_LABEL = 1, HV_LS_NONFINITE = 2, HV_LS_EMPTY = 4 };
+size_t hv_label_stats_workspace_bytes(int V, int A0, int A1, int A2, int S, int Q);
+int hv_label_stats(const void* vol, int vol_dtype, long long sv, long long s0, long long s1, long long s2, const void* label, int label_dtype,
+                   long long lsv, long long ls0, long long ls1, long long ls2, const void* mask, long long msv, long long ms0, long long ms1,
+                   long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const double* q, int Q, double* out, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
