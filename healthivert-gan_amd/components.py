@@ -8,7 +8,8 @@ scipy.ndimage.label / binary_fill_holes bit for bit, on volumes that stay reside
   component_sizes(vol, value=None, connectivity=1)        -> numpy int64 sizes of the n components (one readback)
   keep_largest_component / remove_small_components / fill_holes(vol, value, ...)        -> the cleaned device volume
   clean_label(vol, value, ...)                            the filter, then optionally the hole fill, queued back to back; closing_mm /
-                                                          opening_mm / spacing: morphology.open_label / close_label run first
+                                                          opening_mm / spacing: morphology.open_label / close_label run first; smooth_mm:
+                                                          then filters.smooth_label
   clean_labels(volumes, values, ...)                      the same for a list (the 13 crops of a patient), one readback of the tables
 Volumes are 3-D with any strides, uint8 / float32 / float64 (bool masks become uint8, other dtypes float64), device tensors or numpy arrays
 (uploaded).  connectivity 1 / 2 / 3 is generate_binary_structure(3, c): 6, 18 or 26 neighbours.  table: int32, [0] the number of components
@@ -160,13 +161,20 @@ def _prepare(vol, value, connectivity, out):
     return conn, val, dtype
 
 
-def _check_morph(closing_mm, opening_mm, spacing):
-    """-> None when neither radius is given (no morphology code runs), else (opening radius or None, closing radius or None, spacing), checked."""
-    if closing_mm is None and opening_mm is None:
+def _check_morph(closing_mm, opening_mm, spacing, smooth_mm=None):
+    """-> None when none of the three is given (no morphology or filter code runs), else (opening radius or None, closing radius or None,
+    spacing, the Gaussian weights per axis of smooth_mm or None), checked."""
+    if closing_mm is None and opening_mm is None and smooth_mm is None:
         return None
     from . import morphology as M
+    smooth = None
+    if smooth_mm is not None:
+        from . import filters as F
+        if isinstance(smooth_mm, bool) or not isinstance(smooth_mm, (int, float, np.integer, np.floating)) or not float(smooth_mm) >= 0.0:
+            raise ValueError('smooth_mm: a non-negative number expected, got %r' % (smooth_mm,))
+        smooth = F._gaussian_axes(float(smooth_mm), 0, 4.0, None, M._check_spacing(spacing))
     return (None if opening_mm is None else M._check_radius(opening_mm), None if closing_mm is None else M._check_radius(closing_mm),
-            M._check_spacing(spacing))
+            M._check_spacing(spacing), smooth)
 
 
 def _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table, morph=None):
@@ -182,6 +190,9 @@ def _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fi
         for op, radius in ((M.OPEN, morph[0]), (M.CLOSE, morph[1])):
             if radius is not None:
                 v = M._label_op(op, v, val, radius, morph[2], fl, fl, out)
+        if morph[3] is not None:                 # then the staircase along the slice axis is rounded
+            from . import filters as F
+            v = F._smooth_op(v, val, morph[3], 0.5, fl, fl, out)
     _launch_clean(v, val, conn, ms, bool(keep_largest), fl, out, table[:4])
     if fill_holes:
         _launch_fill(out, val, val, out, table[4:])
@@ -189,7 +200,7 @@ def _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fi
 
 
 def clean_label(vol, value, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, out=None, fill=0, return_table=False,
-                closing_mm=None, opening_mm=None, spacing=(1, 1, 1)):
+                closing_mm=None, opening_mm=None, spacing=(1, 1, 1), smooth_mm=None):
     """The 3-D clean-up of label `value` in a (synthesized) label volume: components of vol == value with fewer than min_size voxels are
     dropped (a component of exactly min_size voxels stays: the reference's rule for its 2-D filter), with keep_largest all but the largest
     one; their voxels become `fill`.  With fill_holes the cavities of what is left -- voxels from which no face of the volume is reached
@@ -199,11 +210,14 @@ def clean_label(vol, value, connectivity=1, min_size=0, keep_largest=True, fill_
     opening_mm / closing_mm (radii in the units of `spacing`, the voxel size along the three axes): before all of this, vol == value is opened
     and / or closed by that ball (morphology.open_label, then morphology.close_label, border_value 0, with `fill` as both the opening's fill
     and the background the closing may grow into): the opening cuts thin bridges to a neighbour, the closing joins fragments that a gap
-    narrower than two radii separates from the body, so that keep_largest keeps them.  The table is then the labelling after them."""
+    narrower than two radii separates from the body, so that keep_largest keeps them.  The table is then the labelling after them.
+    smooth_mm (the sigma of a Gaussian in the units of `spacing`): after the opening / closing and before the component rules the label is
+    smoothed (filters.smooth_label(..., sigma=smooth_mm, spacing=spacing, threshold=0.5, background=fill, fill=fill)), which rounds the
+    staircase the slice-wise generator leaves along the slice axis.  Without it no filter code runs."""
     _prepare(vol, value, connectivity, out)
     _check_min_size(min_size)
     _check_value(fill, 'fill')
-    morph = _check_morph(closing_mm, opening_mm, spacing)
+    morph = _check_morph(closing_mm, opening_mm, spacing, smooth_mm)
     table = torch.empty(8, dtype=torch.int32, device=_device(vol, out))
     out = _clean(vol, value, connectivity, min_size, keep_largest, fill_holes, out, fill, table, morph)
     return (out, table[:4]) if return_table else out
@@ -232,10 +246,10 @@ def fill_holes(vol, value, out=None, return_table=False):
 
 
 def clean_labels(volumes, values, connectivity=1, min_size=0, keep_largest=True, fill_holes=False, fill=0, closing_mm=None, opening_mm=None,
-                 spacing=(1, 1, 1)):
+                 spacing=(1, 1, 1), smooth_mm=None):
     """clean_label for a list of volumes and their labels (one value for all, or one per volume): every call is queued on the stream, then
     the tables are read back once.  -> (the device volumes, each the bytes of the single call; numpy int32 [V][4] tables).  closing_mm /
-    opening_mm / spacing as for clean_label, the same for every volume."""
+    opening_mm / spacing / smooth_mm as for clean_label, the same for every volume."""
     volumes = list(volumes)
     if isinstance(values, (int, float, np.integer, np.floating)) and not isinstance(values, bool):
         values = [values] * len(volumes)
@@ -246,7 +260,7 @@ def clean_labels(volumes, values, connectivity=1, min_size=0, keep_largest=True,
         _prepare(v, val, connectivity, None)
     _check_min_size(min_size)
     _check_value(fill, 'fill')
-    morph = _check_morph(closing_mm, opening_mm, spacing)
+    morph = _check_morph(closing_mm, opening_mm, spacing, smooth_mm)
     if not volumes:
         return [], np.zeros((0, 4), dtype=np.int32)
     tables = torch.empty(len(volumes), 8, dtype=torch.int32, device=_device(*volumes))

@@ -1092,6 +1092,53 @@ int hv_label_stats(const void* vol, int vol_dtype, long long sv, long long s0, l
                    long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const double* q, int Q, double* out, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- separable linear filtering of a volume, and the weighted composite of two volumes (csrc/filter3d.hip).  The
+ * reference filters nothing in 3-D; the definitions are scipy.ndimage.correlate1d / gaussian_filter1d / gaussian_filter (odd-length weights,
+ * origin 0) applied to the float64 copy of the input, bit for bit on finite results, NaN where scipy has NaN.
+ * hv_separable_filter: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order; a sub-box of a larger
+ *   array is its first element's pointer with the array's strides), dtype HV_DT_U8 / I16 / F32 / F64.  in_mode HV_FILT_IN_VALUE: the voxel as a
+ *   double; HV_FILT_IN_EQ: the indicator vol == value as 0.0 / 1.0 (a label's mask is never materialised).  axes: three hv_filter_axis in HOST
+ *   memory, one per axis, copied into the kernel arguments of that axis' launch.  radius < 0 skips the axis (scipy skips sigma <= 1e-15); else
+ *   w[0 .. 2 radius] are the correlation weights, centre at w[radius], radius <= HV_FILT_MAX_RADIUS, and form says how they are summed -- +1
+ *   symmetric, -1 antisymmetric, 0 general; scipy picks +1 iff every |w[r+i] - w[r-i]| <= DBL_EPSILON, else -1 iff every |w[r+i] + w[r-i]| <=
+ *   DBL_EPSILON, and the caller hands that choice over.  With x the line extended by the boundary mode, c the output's place in it, r the radius:
+ *     +1: t = x[c] w[r]; for i = -r .. -1: t += (x[c+i] + x[c-i]) w[i+r]        -1: the same with (x[c+i] - x[c-i])
+ *      0: t = x[c+r] w[2r]; for i = 0 .. 2r-1: t += x[c-r+i] w[i]               (NI_Correlate1D starts the general sum with the last tap)
+ *   all float64, no fma, axes in the order 0, 1, 2, each pass on the doubles of the pass before.  mode: HV_FILT_REFLECT (d c b a | a b c d | d c b
+ *   a), CONSTANT (cval; with HV_FILT_IN_EQ cval is in the indicator's domain), NEAREST, MIRROR (d c b | a b c d | c b a) or WRAP, scipy's modes of
+ *   those names for 1-D filters; the patterns repeat, so a radius above the extent and an extent of 1 are legal in every mode.
+ *   out, element (i, j, k) at out[i*os0 + j*os1 + k*os2]: out_dtype HV_DT_F64 the filtered doubles (8-byte aligned); HV_DT_U8 the mask t >=
+ *   threshold as 0 / 1, formed in the last pass so that its doubles are never stored.  With all three axes skipped out is the converted (or
+ *   thresholded) input.  The address ranges of out and vol must not intersect.
+ *   workspace: 16-byte aligned, hv_filter_workspace_bytes(A0, A1, A2, axes) bytes (host only; 0 for arguments the entry refuses): 16 bytes for
+ *   at most one filtered axis, else one C-ordered double volume (rounded up to 16 bytes) per pass after the first.  A float64 out uses one of
+ *   them (the passes alternate between out and the workspace); a uint8 out after three passes needs both, and the query does not know out_dtype.
+ *   hv_filter_tile (host only): dims[3] = the outputs per workgroup along each axis when that axis is filtered; the halo of `radius` elements on
+ *   either side is resolved through the boundary map while the tile is staged in LDS, so a line's length is not limited.
+ * hv_blend_lerp: out[i][j][k] = ((1 - w) * a) + (w * b) in float64, in this order.  a, b: HV_DT_I16 / F32 / F64, w: HV_DT_F64, or HV_DT_U8 as
+ *   a mask (non-zero = 1.0); every operand has its own strides.  out: doubles, 8-byte aligned; it may be a itself (float64, the same strides)
+ *   and must not intersect b, w, or a in any other way.
+ * No atomics, no host synchronisation, no scratch; the same bytes on every run, whatever the workspace held; nothing outside the described
+ * boxes is read or written.  Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer, a non-positive size, an
+ *   unknown dtype, in_mode, boundary mode or form, a weight or cval that is not finite, out_dtype other than F64 / U8, a float64 out that is not
+ *   8-byte aligned, a workspace that is not 16-byte aligned or smaller than queried, out intersecting an input; HV_ERR_UNSUPPORTED: a radius above
+ *   HV_FILT_MAX_RADIUS, more than 2^30 voxels. */
+enum { HV_FILT_MAX_RADIUS = 64, HV_FILT_MAX_TAPS = 129 };   /* HV_FILT_MAX_TAPS = 2 * HV_FILT_MAX_RADIUS + 1 */
+enum { HV_FILT_IN_VALUE = 0, HV_FILT_IN_EQ = 1 };
+enum { HV_FILT_REFLECT = 0, HV_FILT_CONSTANT = 1, HV_FILT_NEAREST = 2, HV_FILT_MIRROR = 3, HV_FILT_WRAP = 4 };
+typedef struct {
+    int radius, form;
+    double w[HV_FILT_MAX_TAPS];
+} hv_filter_axis;
+size_t hv_filter_workspace_bytes(int A0, int A1, int A2, const hv_filter_axis* axes);
+int hv_filter_tile(int* dims);
+int hv_separable_filter(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, int in_mode, double value,
+                        const hv_filter_axis* axes, int mode, double cval, void* out, int out_dtype, double threshold, long long os0,
+                        long long os1, long long os2, void* workspace, size_t workspace_bytes, void* stream);
+int hv_blend_lerp(const void* a, int a_dtype, long long as0, long long as1, long long as2, const void* b, int b_dtype, long long bs0,
+                  long long bs1, long long bs2, const void* w, int w_dtype, long long ws0, long long ws1, long long ws2, int A0, int A1, int A2,
+                  double* out, long long os0, long long os1, long long os2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
