@@ -24,6 +24,7 @@
 // scratch; every double of the workspace that is read was written by an earlier launch of the same call.
 #include <cmath>
 #include "hv_common.h"
+#include "boundary_map.h"
 
 #pragma clang fp contract(off)
 
@@ -59,31 +60,7 @@ __device__ __forceinline__ void fi_store(const FiPass& P, long long o, double t)
     if (P.out_kind == FI_OUT_THR) ((uint8_t*)P.dst)[o] = (uint8_t)(t >= P.threshold ? 1 : 0);
     else ((double*)P.dst)[o] = t;
 }
-// the index in [0, n) that position p of the extended line reads; -1: cval
-__device__ __forceinline__ int fi_map(int p, int n, int mode) {
-    if (p >= 0 && p < n) return p;
-    switch (mode) {
-        case HV_FILT_CONSTANT: return -1;
-        case HV_FILT_NEAREST: return p < 0 ? 0 : n - 1;
-        case HV_FILT_WRAP: {
-            const int m = p % n;
-            return m < 0 ? m + n : m;
-        }
-        case HV_FILT_REFLECT: {
-            const long long n2 = 2LL * n;
-            long long m = p % n2;
-            if (m < 0) m += n2;
-            return (int)(m < n ? m : n2 - 1 - m);
-        }
-        default: {                                // HV_FILT_MIRROR
-            if (n == 1) return 0;
-            const long long n2 = 2LL * n - 2;
-            long long m = p % n2;
-            if (m < 0) m += n2;
-            return (int)(m < n ? m : n2 - m);
-        }
-    }
-}
+// (fi_map, the index in [0, n) that position p of the extended line reads, -1 for cval: boundary_map.h)
 // the sum of one output: x points at the output's own element of the staged line, consecutive elements of the line `st` doubles apart
 __device__ __forceinline__ double fi_sum(const double* x, int st, const hv_filter_axis& W) {
     const int r = W.radius;

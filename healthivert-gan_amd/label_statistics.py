@@ -4,7 +4,8 @@ What intensities does a (synthesized) vertebra have, per vertebra, and how do th
 definitions are scipy.ndimage.sum_labels / mean / variance / minimum / maximum / center_of_mass / find_objects and np.percentile (linear), on
 volumes that stay resident; one readback of 256 bytes per (volume, label):
   label_statistics(vol, label, labels=None, percentiles=(), mask=None, spacing=(1, 1, 1))         -> dict of arrays [V][S] ([S] for one volume)
-  vertebra_density(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), percentiles=(5, 50, 95))  one vertebra's cancellous core
+  vertebra_density(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), percentiles=(5, 50, 95), median_size=None)
+                                                                                                   one vertebra's cancellous core
   density_comparison(ct_original, ct_synth, label_original, label_synth, vert_id, neighbours=(), erode_mm=0.0, spacing=(1, 1, 1))
 vol: a device tensor [A0][A1][A2] or a stacked [V][A0][A1][A2], any strides, uint8 / int16 / float32 / float64.  label: the same shape, its own
 strides, uint8 / int16 / int32 / int64 / float32 / float64 holding integers in [0, 255].  mask: uint8 or bool of the same shape, a voxel counts
@@ -257,15 +258,20 @@ def _one(res, v, s):
     return {k: (res[k][v][s] if k != 'labels' else int(res[k][s])) for k in res}
 
 
-def vertebra_density(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), percentiles=(5, 50, 95)):
+def vertebra_density(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), percentiles=(5, 50, 95), median_size=None):
     """The statistics of one vertebra's cancellous core: label_statistics of `ct` inside label == vert_id, under the mask
     morphology.binary_erosion(label == vert_id, ball(erode_mm, spacing), border_value=0) (erode_mm = 0: no morphology runs, no mask).
+    median_size (an integer or one per axis): the statistics are those of rank_filters.median_filter(ct, size=median_size), the usual pre-step
+    against salt-and-pepper noise (None: no filter runs).
     -> the dict of label_statistics for that one label (scalars; percentiles [Q])."""
     sp = _check_spacing(spacing)
     r = _check_erode(erode_mm)
     vid = _check_labels([vert_id])[0]
     _check_3d(ct, 'ct', _VOL_DT)
     _check_3d(label, 'label', _LABEL_DT, ct.shape)
+    if median_size is not None:
+        from . import rank_filters
+        ct = rank_filters.median_filter(ct, size=median_size)
     mask = None
     if r > 0.0:
         mask = _core_mask(label, [vid], r, sp, torch.empty(tuple(label.shape), dtype=torch.uint8, device=label.device))

@@ -22,7 +22,7 @@ ERRORS = {-1: 'HV_ERR_ARG (invalid argument)', -2: 'HV_ERR_UNSUPPORTED (shape no
 
 _BASE = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'long long': ctypes.c_longlong,
-    'size_t': ctypes.c_size_t, 'void': None, 'char': ctypes.c_char,
+    'size_t': ctypes.c_size_t, 'void': None, 'char': ctypes.c_char, 'unsigned long long': ctypes.c_ulonglong,
 }
 
 
@@ -59,7 +59,7 @@ def parse_header(path=HEADER):
             decl = decl.strip()
             if not decl:
                 continue
-            m = re.match(r'((?:const\s+)?(?:long long|size_t|int|float|double|\w+)\s*\**)\s*(.*)', decl)
+            m = re.match(r'((?:const\s+)?(?:unsigned long long|long long|size_t|int|float|double|\w+)\s*\**)\s*(.*)', decl)
             tname, names = m.group(1), m.group(2)
             for nm in names.split(','):
                 nm = nm.strip()
@@ -87,7 +87,7 @@ def parse_header(path=HEADER):
 
 
 _CTYPES_NAME = {ctypes.c_int: 'ctypes.c_int', ctypes.c_float: 'ctypes.c_float', ctypes.c_double: 'ctypes.c_double',
-                ctypes.c_longlong: 'ctypes.c_longlong', ctypes.c_size_t: 'ctypes.c_size_t', ctypes.c_void_p: 'ctypes.c_void_p',
+                ctypes.c_longlong: 'ctypes.c_longlong', ctypes.c_ulonglong: 'ctypes.c_ulonglong', ctypes.c_size_t: 'ctypes.c_size_t', ctypes.c_void_p: 'ctypes.c_void_p',
                 ctypes.c_char_p: 'ctypes.c_char_p', ctypes.c_char: 'ctypes.c_char'}
 
 

@@ -1139,6 +1139,31 @@ int hv_blend_lerp(const void* a, int a_dtype, long long as0, long long as1, long
                   long long bs1, long long bs2, const void* w, int w_dtype, long long ws0, long long ws1, long long ws2, int A0, int A1, int A2,
                   double* out, long long os0, long long os1, long long os2, void* stream);
 
+/* ---- 3-D rank filters (csrc/rankfilt.hip): scipy.ndimage.rank_filter with a footprint of at most 9 x 9 x 9 cells,
+ * which is what median_filter, percentile_filter, minimum_filter / maximum_filter and the flat grey-scale morphology are built from.
+ * hv_rank_filter: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order; a sub-box of a larger array
+ *   passes as it lies), dtype HV_DT_U8 / I16 / F32 / F64; out has the same dtype and its own strides, and its bytes must not intersect the bytes
+ *   vol spans.  fp (HOST memory, copied into the kernel arguments): the footprint as a set of integer offsets o with |o_a| <= 4 -- bit
+ *   ((o0 + 4) * 9 + (o1 + 4)) * 9 + (o2 + 4) of `bits` (bit b is bit b % 64 of bits[b / 64]) is set for each member, n is their number.
+ *   out[p] = the rank-th smallest (0-based) of { ext(vol)[p + o] : o in the footprint }, ext the boundary extension of hv_separable_filter
+ *   (mode: the HV_FILT_* codes; the patterns repeat, so an extent of 1 and a reach above the extent are legal).  The comparison is on
+ *   order-preserving integer keys of the element's own width: for floats the sign-flipped bits, so -0.0 sorts just below +0.0 and NaNs sort at
+ *   the two ends by their sign bit; the voxel written is one of the window's own voxels or cval, bit for bit.  A window without NaN is not
+ *   affected by NaNs elsewhere; for a window with a NaN the answer is the key order's (scipy's depends on its selection algorithm).
+ *   hv_rank_tile (host only): dims[3] = the outputs per workgroup along each axis, whatever the strides.
+ * No atomics, no workspace, no host synchronisation, no scratch; the same bytes on every run.  Refusals, before any launch and with nothing
+ *   written -- HV_ERR_ARG: a NULL pointer, a non-positive size, an unknown dtype or mode, n < 1, n other than the number of set bits, a bit set
+ *   above index 728, rank outside [0, n), a cval that is not finite or not exactly representable in dtype (scipy compares such a cval as a
+ *   double and truncates it on output: not offered), out intersecting vol; HV_ERR_UNSUPPORTED: more than 2^30 voxels. */
+enum { HV_RANK_REACH = 4, HV_RANK_WORDS = 12 };             /* offsets -4 .. 4 per axis: 729 bits in 12 words */
+typedef struct {
+    int n;
+    unsigned long long bits[HV_RANK_WORDS];
+} hv_rank_footprint;
+int hv_rank_tile(int* dims);
+int hv_rank_filter(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const hv_rank_footprint* fp,
+                   int rank, int mode, double cval, void* out, long long os0, long long os1, long long os2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
