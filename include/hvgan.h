@@ -1164,6 +1164,38 @@ int hv_rank_tile(int* dims);
 int hv_rank_filter(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const hv_rank_footprint* fp,
                    int rank, int mode, double cval, void* out, long long os0, long long os1, long long os2, void* stream);
 
+/* ---- 3-D affine resampling (csrc/resample.hip): scipy.ndimage.affine_transform, zoom and shift of a volume at spline
+ * order 0, 1 or 3, mode constant (and nearest at order 0), scipy's bytes.
+ * hv_resample: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order; a sub-box of a larger array
+ *   passes as it lies), dtype HV_DT_U8 / I16 / F32 / F64.  For order 3 vol is the float64 coefficient volume hv_spline_prefilter leaves (window
+ *   off), so dtype is HV_DT_F64 there.  out [O0][O1][O2] with its own dtype (any of the four) and strides; its bytes must not intersect the bytes
+ *   vol spans.  desc (HOST memory, copied into the kernel arguments; no host-to-device copy): for output index o and input axis h, in float64
+ *   without fused multiply-add,
+ *     form HV_RESAMPLE_MATRIX:    u_h = ((o0 matrix[3h] + o1 matrix[3h+1]) + o2 matrix[3h+2]) + offset[h]   (summed from 0.0, the offset last)
+ *     form HV_RESAMPLE_ZOOMSHIFT: u_h = (o_h + shift[h]) * zoom[h]                                          (scipy's zoom_shift)
+ *   mode (the HV_FILT_* codes) HV_FILT_CONSTANT: u_h < 0 or u_h > A_h - 1 on any axis gives cval; HV_FILT_NEAREST (order 0 only): u_h is clamped
+ *   to [0, A_h - 1].  order 0: the voxel at floor(u + 0.5); order 1: taps floor(u), floor(u) + 1 with the weights w0 = 1 - y, 1 - w0; order 3:
+ *   the four taps and weights of the spline sampler above.  Tap indices beyond the ends are mirrored about the end points.  The sum runs over
+ *   the taps with the last axis fastest, each term ((c w0) w1) w2, added from 0.0.  Output: float64 as it is; float32 rounded once; int16
+ *   t > 0 ? t + 0.5 : t - 0.5, clamped, truncated; uint8 t > 0 ? t + 0.5 : 0, clamped, truncated.
+ *   hv_resample_tile (host only): dims[3] = the outputs per workgroup along each axis, whatever the strides.
+ * One launch, no atomics, no workspace, no host synchronisation, no scratch; the same bytes on every run; nothing outside the two boxes is read
+ *   or written.  Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer, a non-positive extent, an unknown dtype,
+ *   form, order (other than 0, 1, 3) or mode, a matrix, offset, zoom, shift or cval that is not finite (every field is checked, whatever the
+ *   form), a cval that is not a value of an integer out_dtype, order 3 on anything but float64, a pointer not aligned to its element, out
+ *   intersecting vol; HV_ERR_UNSUPPORTED: modes reflect / mirror / wrap, nearest at order 1 (scipy's edge rule there is not a clamp of the
+ *   coordinate) or 3 (scipy pre-pads by 12 voxels), more than 2^30 voxels on either side. */
+enum { HV_RESAMPLE_MATRIX = 0, HV_RESAMPLE_ZOOMSHIFT = 1 };
+typedef struct {
+    int form;
+    double matrix[9], offset[3], zoom[3], shift[3];
+    int order, mode;
+    double cval;
+} hv_resample_desc;
+int hv_resample_tile(int* dims);
+int hv_resample(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, void* out, int out_dtype,
+                long long os0, long long os1, long long os2, int O0, int O1, int O2, const hv_resample_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
