@@ -1092,6 +1092,37 @@ int hv_label_stats(const void* vol, int vol_dtype, long long sv, long long s0, l
                    long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const double* q, int Q, double* out, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- per-label 3-D grey-level co-occurrence matrices of volumes (csrc/texture.hip).  The reference has no
+ * counterpart: the definition is Haralick's (1973), skimage.feature.graycomatrix carried to three dimensions and restricted to a label.
+ * hv_glcm: vol, vol_dtype and strides, label, label_dtype and strides, mask and strides, V, A0..A2 and labels[S] exactly as for hv_label_stats
+ *   (vol HV_DT_U8 / I16 / F32 / F64; a label value that is no integer in [0, 255] sets HV_LS_BAD_LABEL for its whole volume and has no slot).
+ *   The SLOT of a voxel p is the s with label(p) == labels[s] if mask is NULL or mask(p) != 0; otherwise it has none.  Its LEVEL: x = (double)v;
+ *   a non-finite x takes the voxel out of every pair and ORs HV_LS_NONFINITE into info[v][s][0] of the slot it would have had; otherwise
+ *   t = (x - lo) / width, those two IEEE float64 operations (no contraction, no reciprocal), and the level is 0 if t < 0, G - 1 if t >= G, else
+ *   (int)t.  offsets (HOST, [D][3] ints, 1 <= D <= HV_GLCM_MAX_OFFSETS, every component in [-HV_GLCM_MAX_REACH, HV_GLCM_MAX_REACH], no offset
+ *   twice; (0, 0, 0) allowed: the slot's level histogram on the diagonal) are copied into the kernel arguments.  G in 2..HV_GLCM_MAX_LEVELS.
+ *   out (device, 8-byte aligned): [V][S][D][G][G] int64.  For every offset d and every voxel p with p + d inside the volume and
+ *   slot(p) == slot(p + d) == s: out[v][s][d][level(p)][level(p + d)] += 1, and with HV_GLCM_SYMMETRIC in flags also
+ *   out[v][s][d][level(p + d)][level(p)] += 1 (P + P^T, the diagonal doubled, as graycomatrix(symmetric=True)).  No boundary modes: a pair that
+ *   leaves the volume is not counted.  info (device, 8-byte aligned): [V][S][HV_GLCM_INFO] int64 -- [0] the OR of HV_LS_BAD_LABEL,
+ *   HV_LS_NONFINITE, HV_LS_EMPTY (no finite voxel in the slot); [1] the number of finite voxels of the slot; [2] how many of them were clamped
+ *   from below (t < 0); [3] how many from above (t >= G).
+ *   The entry zeroes out and info itself on the stream.  Only integer atomics: the same bytes on every run, for any strides, single or stacked,
+ *   whatever out, info and the workspace held.  No host synchronisation.  workspace: 16-byte aligned, hv_glcm_workspace_bytes(V, A0, A1, A2,
+ *   S, D, G) bytes (0 for sizes the entry refuses).
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (mask excepted), a non-positive size, an unknown dtype, S
+ *   outside 1..HV_LS_MAX_LABELS, D outside 1..HV_GLCM_MAX_OFFSETS, G outside 2..HV_GLCM_MAX_LEVELS, a label value outside [0, 255] or listed
+ *   twice, an offset component beyond HV_GLCM_MAX_REACH, an offset listed twice, lo not finite, width not finite or not > 0, unknown flag bits,
+ *   out or info not 8-byte aligned, a workspace that is not 16-byte aligned or smaller than queried; HV_ERR_UNSUPPORTED: more than 2^30 voxels
+ *   per volume, V > 65535. */
+enum { HV_GLCM_MAX_LEVELS = 64, HV_GLCM_MAX_OFFSETS = 26, HV_GLCM_MAX_REACH = 4, HV_GLCM_INFO = 4 };
+enum { HV_GLCM_SYMMETRIC = 1 };
+size_t hv_glcm_workspace_bytes(int V, int A0, int A1, int A2, int S, int D, int G);
+int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s0, long long s1, long long s2, const void* label, int label_dtype,
+            long long lsv, long long ls0, long long ls1, long long ls2, const void* mask, long long msv, long long ms0, long long ms1,
+            long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const int* offsets, int D, double lo, double width, int G,
+            int flags, long long* out, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- separable linear filtering of a volume, and the weighted composite of two volumes (csrc/filter3d.hip).  The
  * reference filters nothing in 3-D; the definitions are scipy.ndimage.correlate1d / gaussian_filter1d / gaussian_filter (odd-length weights,
  * origin 0) applied to the float64 copy of the input, bit for bit on finite results, NaN where scipy has NaN.
