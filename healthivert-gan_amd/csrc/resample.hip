@@ -18,12 +18,7 @@
 // part, and the one code path keeps the two forms' arithmetic identical.  The descriptor travels in the kernel arguments.  No atomics, no
 // workspace, no LDS, no scratch, no workgroup waits for another; every index is formed from a coordinate already tested (or clamped) to lie
 // in [0, A - 1] -- a NaN coordinate fails the test and counts as outside -- so nothing outside the source box is read.
-#include <cmath>
-#include "hv_common.h"
-#include "spline_tap.h"
-
-#define RS_THREADS 256
-#define RS_T 8                          // outputs per workgroup along each axis
+#include "resample_core.h"
 
 struct RsP {
     const void* src; void* dst;
@@ -34,58 +29,6 @@ struct RsP {
     int dst_dt;
     hv_resample_desc D;
 };
-
-template <typename T>
-__device__ __forceinline__ double rs_ld(const T* p, long long o) { return (double)p[o]; }
-
-// the coordinate along one axis against the outside rule: false = outside (constant mode); nearest clamps
-__device__ __forceinline__ bool rs_inside(double& u, int n, int mode) {
-    const double hi = (double)(n - 1);
-    if (mode == HV_FILT_NEAREST) {
-        u = u >= 0.0 ? (u <= hi ? u : hi) : 0.0;
-        return true;
-    }
-    return u >= 0.0 && u <= hi;         // false for a NaN
-}
-
-template <int ORDER>
-__device__ __forceinline__ void rs_taps(double u, int n, long long s, long long (&o)[ORDER + 1], double (&w)[ORDER + 1]) {
-    if constexpr (ORDER == 0) {
-        o[0] = (long long)floor(u + 0.5) * s;
-        w[0] = 1.0;
-    } else if constexpr (ORDER == 1) {
-        const double f = floor(u);
-        w[0] = 1.0 - (u - f);
-        w[1] = 1.0 - w[0];
-        const long long i = (long long)f;
-        o[0] = i * s;                   // 0 <= i <= n - 1
-        o[1] = hv_spline_mirror(i + 1, n) * s;
-    } else {
-        hv_spline_taps(u, n, s, o, w);
-    }
-}
-
-__device__ __forceinline__ void rs_store(void* dst, int dt, long long off, double t) {
-    switch (dt) {
-        case HV_DT_F64: ((double*)dst)[off] = t; break;
-        case HV_DT_F32: ((float*)dst)[off] = (float)t; break;
-        case HV_DT_I16: {
-            t = t > 0.0 ? t + 0.5 : t - 0.5;
-            t = t > 32767.0 ? 32767.0 : t;
-            t = t < -32768.0 ? -32768.0 : t;
-            ((int16_t*)dst)[off] = (int16_t)(int)t;
-            break;
-        }
-        default: {
-            t = t > 0.0 ? t + 0.5 : 0.0;
-            t = t > 255.0 ? 255.0 : t;
-            ((uint8_t*)dst)[off] = (uint8_t)(int)t;
-            break;
-        }
-    }
-}
-
-__device__ __forceinline__ int rs_pick(int role, int gL, int gM, int gO) { return role == 0 ? gL : role == 1 ? gM : gO; }
 
 // grid: the tiles, the one along L fastest
 template <typename T, int ORDER>
@@ -140,20 +83,6 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(RsP P) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline long long rs_abs(long long v) { return v < 0 ? -v : v; }
-static inline bool rs_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_DT_I16 || dt == HV_DT_F32 || dt == HV_DT_F64; }
-static inline size_t rs_elem(int dt) { return dt == HV_DT_U8 ? 1 : dt == HV_DT_I16 ? 2 : dt == HV_DT_F32 ? 4 : 8; }
-// the bytes [lo, hi) a strided box touches, relative to its base pointer
-static void rs_span(const int* A, const long long* s, size_t elem, long long* lo, long long* hi) {
-    long long mn = 0, mx = 0;
-    for (int a = 0; a < 3; ++a) {
-        const long long e = (long long)(A[a] - 1) * s[a];
-        if (e < 0) mn += e; else mx += e;
-    }
-    *lo = mn * (long long)elem;
-    *hi = (mx + 1) * (long long)elem;
-}
-
 template <typename T>
 static void rs_launch(int order, dim3 grid, hipStream_t st, const RsP& P) {
     if (order == 0) hipLaunchKernelGGL((resample_kernel<T, 0>), grid, dim3(RS_THREADS), 0, st, P);
@@ -172,52 +101,20 @@ extern "C" int hv_resample_tile(int* dims) {
 extern "C" int hv_resample(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, void* out,
                            int out_dtype, long long os0, long long os1, long long os2, int O0, int O1, int O2, const hv_resample_desc* desc,
                            void* stream) {
-    if (!vol || !out || !desc || A0 <= 0 || A1 <= 0 || A2 <= 0 || O0 <= 0 || O1 <= 0 || O2 <= 0 || !rs_dtype_ok(dtype) ||
-        !rs_dtype_ok(out_dtype))
-        return HV_ERR_ARG;
+    if (!desc) return HV_ERR_ARG;
     const hv_resample_desc& D = *desc;
-    if ((D.form != HV_RESAMPLE_MATRIX && D.form != HV_RESAMPLE_ZOOMSHIFT) || (D.order != 0 && D.order != 1 && D.order != 3) ||
-        D.mode < HV_FILT_REFLECT || D.mode > HV_FILT_WRAP)
-        return HV_ERR_ARG;
-    bool finite = std::isfinite(D.cval);
-    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(D.matrix[i]);
-    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(D.offset[i]) && std::isfinite(D.zoom[i]) && std::isfinite(D.shift[i]);
-    if (!finite) return HV_ERR_ARG;
-    if (out_dtype == HV_DT_U8 || out_dtype == HV_DT_I16) {
-        const double lo = out_dtype == HV_DT_U8 ? 0.0 : -32768.0, hi = out_dtype == HV_DT_U8 ? 255.0 : 32767.0;
-        if (D.cval < lo || D.cval > hi || D.cval != std::floor(D.cval)) return HV_ERR_ARG;
-    }
-    if (D.order == 3 && dtype != HV_DT_F64) return HV_ERR_ARG;             // order 3 samples coefficients, and those are doubles
-    if (((uintptr_t)vol & (rs_elem(dtype) - 1)) || ((uintptr_t)out & (rs_elem(out_dtype) - 1))) return HV_ERR_ARG;
-    // the modes not built: mirror / reflect / wrap; nearest above order 0 (order 1: scipy's edge rule is not a clamp; order 3: its 12-voxel
-    // pre-padding)
-    if (D.mode != HV_FILT_CONSTANT && !(D.mode == HV_FILT_NEAREST && D.order == 0)) return HV_ERR_UNSUPPORTED;
-    if ((long long)A0 * A1 * A2 > (1LL << 30) || (long long)O0 * O1 * O2 > (1LL << 30)) return HV_ERR_UNSUPPORTED;
     const int A[3] = {A0, A1, A2}, O[3] = {O0, O1, O2};
     const long long ss[3] = {s0, s1, s2}, os[3] = {os0, os1, os2};
-    long long vlo, vhi, olo, ohi;
-    rs_span(A, ss, rs_elem(dtype), &vlo, &vhi);
-    rs_span(O, os, rs_elem(out_dtype), &olo, &ohi);
-    if ((intptr_t)vol + vlo < (intptr_t)out + ohi && (intptr_t)out + olo < (intptr_t)vol + vhi) return HV_ERR_ARG;
+    int rc = rs_check_args(vol, dtype, A, out, out_dtype, O, D.order, D.mode, D.cval);
+    if (rc != HV_OK) return rc;
+    if (!rs_desc_ok(D)) return HV_ERR_ARG;
+    rc = rs_check_support(vol, dtype, A, ss, out, out_dtype, O, os, D.order, D.mode);
+    if (rc != HV_OK) return rc;
     // the roles: L the output axis whose unit step moves least far in the source (an axis of extent 1 comes last), then M, then O
     double img[3];
-    for (int j = 0; j < 3; ++j) {
-        if (D.form == HV_RESAMPLE_MATRIX) {
-            img[j] = 0.0;
-            for (int h = 0; h < 3; ++h) img[j] += std::fabs(D.matrix[3 * h + j]) * (double)rs_abs(ss[h]);
-        } else {
-            img[j] = std::fabs(D.zoom[j]) * (double)rs_abs(ss[j]);
-        }
-    }
-    int ord[3] = {0, 1, 2};
-    auto before = [&](int a, int b) {
-        if ((O[a] > 1) != (O[b] > 1)) return O[a] > 1;
-        if (img[a] != img[b]) return img[a] < img[b];
-        return a > b;
-    };
-    for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2 - i; ++j)
-            if (before(ord[j + 1], ord[j])) { const int t = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = t; }
+    rs_image(D, ss, img);
+    int ord[3];
+    rs_roles(O, img, ord);
     RsP P;
     P.src = vol; P.dst = out;
     P.s0 = s0; P.s1 = s1; P.s2 = s2; P.d0 = os0; P.d1 = os1; P.d2 = os2;

@@ -1227,6 +1227,43 @@ int hv_resample_tile(int* dims);
 int hv_resample(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, void* out, int out_dtype,
                 long long os0, long long os1, long long os2, int O0, int O1, int O2, const hv_resample_desc* desc, void* stream);
 
+/* ---- deformable 3-D resampling (csrc/warp.hip): a volume sampled at coordinates the caller supplies
+ * (scipy.ndimage.map_coordinates, or a dense displacement field) or at an affine lattice deformed by a coarse control grid.  vol, out, order,
+ * mode and cval are hv_resample's, and from the coordinate u on everything is hv_resample's rule: outside test (a NaN coordinate fails it and
+ * gives cval in mode constant; the nearest form clamps it to 0, as scipy does), taps, weights, mirrored indices, term order, output conversion.
+ * hv_map_coordinates: coords holds three planes over the output lattice, component h of output (i, j, k) at coords[h*cp + i*c0 + j*c1 + k*c2]
+ *   (strides in elements, any order: a [3][O0][O1][O2] array, a permuted view of one, an [O0][O1][O2][3] array and a sub-box all pass as they
+ *   lie), coord_dtype HV_DT_F32 (widened exactly) or HV_DT_F64.  coord_kind HV_COORDS_ABSOLUTE: u_h = c_h(o); HV_COORDS_DISPLACEMENT:
+ *   u_h = (double)o_h + c_h(o), a displacement field in source voxels.
+ * hv_warp_grid: grid [3][G0][G1][G2], float64, component h at (a, b, c) at grid[h*gp + a*g0 + b*g1 + c*g2]: the displacement along source axis
+ *   h in source voxels at that control point.  desc (HOST memory, copied into the kernel arguments): base is the lattice, order, mode and cval
+ *   as for hv_resample.  For output index o, in float64 without fused multiply-add, in this order:
+ *     q_a = (o_a + gshift[a]) * gzoom[a], then clamped to [0, G_a - 1] as q >= 0 ? (q <= hi ? q : hi) : 0
+ *     d_h = the sampler's sum on grid[h] at q at order gorder: 1 the taps floor(q), floor(q) + 1 with the weights 1 - y, 1 - (1 - y); 3 the
+ *           four taps and weights of the spline sampler applied to the control values themselves, with no prefilter (the approximating cubic
+ *           B-spline of free-form deformation).  Tap indices mirrored about the ends, last axis fastest, each term ((g w0) w1) w2, from 0.0
+ *     u_h = base_h(o) + d_h, base_h hv_resample's expression for base.form
+ *   hv_map_coordinates_tile / hv_warp_grid_tile (host only): dims[3] = the outputs per workgroup along each axis, whatever the strides.
+ * One launch per call, no atomics, no workspace, no host synchronisation, no scratch; the same bytes on every run and for any strides; nothing
+ *   outside the stated boxes is read or written.  Refusals, before any launch and with nothing written -- hv_resample's own list, and
+ *   HV_ERR_ARG: a NULL coords / grid, a coord_dtype other than F32 / F64, an unknown coord_kind, coords or grid not aligned to its element,
+ *   out intersecting coords or grid, a gorder other than 1 or 3, a non-positive grid extent, a gzoom or gshift that is not finite;
+ *   HV_ERR_UNSUPPORTED: more than 2^30 control points. */
+enum { HV_COORDS_ABSOLUTE = 0, HV_COORDS_DISPLACEMENT = 1 };
+typedef struct {
+    hv_resample_desc base;
+    double gzoom[3], gshift[3];
+    int gorder;
+} hv_warp_desc;
+int hv_map_coordinates_tile(int* dims);
+int hv_warp_grid_tile(int* dims);
+int hv_map_coordinates(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const void* coords,
+                       int coord_dtype, long long cp, long long c0, long long c1, long long c2, int coord_kind, void* out, int out_dtype,
+                       long long os0, long long os1, long long os2, int O0, int O1, int O2, int order, int mode, double cval, void* stream);
+int hv_warp_grid(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const double* grid, long long gp,
+                 long long g0, long long g1, long long g2, int G0, int G1, int G2, void* out, int out_dtype, long long os0, long long os1,
+                 long long os2, int O0, int O1, int O2, const hv_warp_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
