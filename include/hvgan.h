@@ -1264,6 +1264,41 @@ int hv_warp_grid(const void* vol, int dtype, long long s0, long long s1, long lo
                  long long g0, long long g1, long long g2, int G0, int G1, int G2, void* out, int out_dtype, long long os0, long long os1,
                  long long os2, int O0, int O1, int O2, const hv_warp_desc* desc, void* stream);
 
+/* ---- joint intensity histograms of a fixed and a moving volume under a list of affine poses (csrc/similarity.hip):
+ * what mutual information, its normalised form and the entropy correlation coefficient are computed from.  The reference has no counterpart.
+ * hv_joint_hist: fixed [O0][O1][O2], element (i, j, k) at fixed[i*fs0 + j*fs1 + k*fs2]; moving [A0][A1][A2] likewise; both HV_DT_U8 / I16 /
+ *   F32 / F64, strides in elements, any order (a sub-box passes as it lies).  At order 3 moving is the float64 coefficient volume of
+ *   hv_spline_prefilter, as for hv_resample.  mask (may be NULL): uint8 over the fixed lattice with its own strides.  poses (HOST, [K][12]
+ *   doubles: matrix[9] then offset[3], 1 <= K <= HV_JH_MAX_POSES) are copied into the kernel arguments; no host-to-device copy.
+ *   For every fixed voxel o and every pose k, in this order:
+ *     1. mask != NULL and mask(o) == 0: the voxel is in no pair; info[k][2] += 1.
+ *     2. x = (double)fixed(o) not finite: in no pair; info[k][3] += 1.
+ *     3. u_h = ((o0 m[3h] + o1 m[3h+1]) + o2 m[3h+2]) + off[h], summed from 0.0, float64 without fma: hv_resample's HV_RESAMPLE_MATRIX form.
+ *     4. u_h < 0 or u_h > A_h - 1 on any axis (a NaN counts as outside): the pair is not counted; info[k][4] += 1.  No cval is invented: only
+ *        the overlap is measured.
+ *     5. y = hv_resample's float64 sum at `order` 0 / 1 / 3 (taps, weights, mirrored indices, last axis fastest, ((c w0) w1) w2 from 0.0), with
+ *        no output conversion.  y not finite: not counted; info[k][3] += 1.
+ *     6. levels by hv_glcm's rule: t = (x - flo) / fwidth, two IEEE operations; lf = 0 if t < 0, Gf - 1 if t >= Gf, else (int)t; lm the same
+ *        from y, mlo, mwidth, Gm.  out[k][lf][lm] += 1.
+ *   out (device, 8-byte aligned): [K][Gf][Gm] int64.  info (device, 8-byte aligned): [K][HV_JH_INFO] int64 -- [0] HV_LS_NONFINITE if [3] > 0,
+ *   ORed with HV_LS_EMPTY if [1] == 0; [1] counted pairs; [2] masked out; [3] non-finite (fixed or sampled); [4] outside; [5], [6] the counted
+ *   pairs whose fixed level was clamped from below / from above; [7] the counted pairs whose moving level was clamped from below or above.
+ *   For every k: [1] + [2] + [3] + [4] == O0 * O1 * O2 and the sum of out[k] == [1].
+ *   The entry zeroes out and info itself on the stream.  Only integer atomics: the same bytes on every run, for any strides, whatever the
+ *   buffers held.  No host synchronisation.  workspace: hv_joint_hist_workspace_bytes bytes, which is 0 -- the tables live in LDS -- so NULL
+ *   is accepted; a pointer that is given must be 16-byte aligned.
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (mask and workspace excepted), a non-positive extent,
+ *   an unknown dtype, order other than 0 / 1 / 3, order 3 on a moving volume that is not float64, K outside 1..HV_JH_MAX_POSES, Gf or Gm
+ *   outside 2..HV_JH_MAX_LEVELS, a pose entry, flo or mlo that is not finite, a width that is not finite or not > 0, fixed or moving not
+ *   aligned to its element, out or info not 8-byte aligned, out or info intersecting fixed, moving, mask or each other, a misaligned
+ *   workspace; HV_ERR_UNSUPPORTED: more than 2^30 voxels on either side. */
+enum { HV_JH_MAX_LEVELS = 64, HV_JH_MAX_POSES = 16, HV_JH_INFO = 8 };
+size_t hv_joint_hist_workspace_bytes(int O0, int O1, int O2, int K, int Gf, int Gm);
+int hv_joint_hist(const void* fixed, int fixed_dtype, long long fs0, long long fs1, long long fs2, int O0, int O1, int O2, const void* moving,
+                  int moving_dtype, long long ms0, long long ms1, long long ms2, int A0, int A1, int A2, const void* mask, long long ks0,
+                  long long ks1, long long ks2, const double* poses, int K, int order, double flo, double fwidth, int Gf, double mlo,
+                  double mwidth, int Gm, long long* out, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
