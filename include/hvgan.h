@@ -1299,6 +1299,34 @@ int hv_joint_hist(const void* fixed, int fixed_dtype, long long fs0, long long f
                   long long ks1, long long ks2, const double* poses, int K, int order, double flo, double fwidth, int Gf, double mlo,
                   double mwidth, int Gm, long long* out, long long* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-label 3-D shape records: the 2 x 2 x 2 cell-configuration histogram (Minkowski measures), coordinate moments and directional extents
+ * (csrc/shape.hip).  The reference has no counterpart.
+ * hv_shape: label, label_dtype and strides, mask and strides, V, A0..A2 and labels[S] exactly as for hv_label_stats and hv_glcm (a label value
+ *   that is no integer in [0, 255] sets HV_LS_BAD_LABEL for its whole volume and has no slot).  The slot of voxel p is the s with
+ *   label(p) == labels[s], provided mask is NULL or mask(p) != 0; otherwise, and outside the volume, the voxel has no slot.
+ *   out (device, 8-byte aligned): [V][S][HV_SHAPE_REC] int64, per (volume, listed label):
+ *     [0 .. 255] the configuration histogram over the cells c = (i, j, k), i in [-1, A0 - 1], j in [-1, A1 - 1], k in [-1, A2 - 1] -- the
+ *       (A0 + 1)(A1 + 1)(A2 + 1) cells of the lattice padded by one background layer.  For slot s, code = the sum of bit (4 d0 + 2 d1 + d2) over
+ *       d in {0, 1}^3 with slot(c + d) == s; out[v][s][code] += 1 for code != 0, and out[v][s][0] is the cell count minus the rest, so every
+ *       histogram sums to the cell count.  A cell whose corners hold several listed labels counts once in each of those slots, with that
+ *       slot's code.
+ *     [HV_SHAPE_COUNT] n, the voxel count; [HV_SHAPE_SUM + a] the sum of p_a; [HV_SHAPE_SUM2 + 0 .. 5] the sums of p_a p_b in the order 00, 01,
+ *       02, 11, 12, 22 -- all exact int64.
+ *     [HV_SHAPE_EXTENT + 2t], [HV_SHAPE_EXTENT + 2t + 1], t < 13: the minimum and the maximum of the integer dot product d_t . p over the
+ *       slot's voxels, d_t the t-th of the 13 offsets (a, b, c) > (0, 0, 0) in lexicographic order; n = 0: INT64_MAX and INT64_MIN.
+ *     [HV_SHAPE_STATUS] the OR of HV_LS_BAD_LABEL and HV_LS_EMPTY (n = 0); the words after it are 0.
+ *   The entry initialises out itself on the stream.  Only integer atomics: the same bytes on every run, for any strides, single or stacked,
+ *   whatever out and the workspace held.  No host synchronisation.  workspace: 16-byte aligned, hv_shape_workspace_bytes(V, A0, A1, A2, S) bytes.
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (mask excepted), a non-positive size, an unknown dtype,
+ *   S outside 1..HV_LS_MAX_LABELS, a label value outside [0, 255] or listed twice, out not 8-byte aligned, a misaligned or too small workspace;
+ *   HV_ERR_UNSUPPORTED: more than 2^30 voxels per volume, V > 65535, or A0 A1 A2 max(A_a - 1)^2 >= 2^62 (the second moments would leave int64).
+ *   hv_shape_workspace_bytes returns 0 for all of these. */
+enum { HV_SHAPE_REC = 320, HV_SHAPE_COUNT = 256, HV_SHAPE_SUM = 257, HV_SHAPE_SUM2 = 260, HV_SHAPE_EXTENT = 266, HV_SHAPE_STATUS = 292 };
+size_t hv_shape_workspace_bytes(int V, int A0, int A1, int A2, int S);
+int hv_shape(const void* label, int label_dtype, long long lsv, long long ls0, long long ls1, long long ls2, const void* mask, long long msv,
+             long long ms0, long long ms1, long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, long long* out,
+             void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
