@@ -1327,6 +1327,49 @@ int hv_shape(const void* label, int label_dtype, long long lsv, long long ls0, l
              long long ms0, long long ms1, long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, long long* out,
              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- parallel-beam projections of a volume under a list of affine poses (csrc/projection.hip): what a radiograph
+ * (line integral), a minimum / maximum intensity projection, a thickness map and an areal density are computed from.  The reference has no
+ * counterpart.  A projection is hv_resample's HV_RESAMPLE_MATRIX lattice (p0, p1, t), reduced over t without ever being written.
+ * hv_project: vol [A0][A1][A2], element (i, j, k) at vol[i*s0 + j*s1 + k*s2] (strides in elements, any order; a sub-box passes as it lies),
+ *   dtype HV_DT_U8 / I16 / F32 / F64; at order 3 vol is the float64 coefficient volume of hv_spline_prefilter, as for hv_resample.  label (may be
+ *   NULL): the same logical shape with its own strides ls0..ls2, any HV_DT_* code, with label_value.  poses (HOST, [K][12] doubles: matrix[9]
+ *   then offset[3], 1 <= K <= HV_PROJ_MAX_POSES) are copied into the kernel arguments; no host-to-device copy.  Detector P0 x P1, T steps.
+ *   For every pose k, pixel (p0, p1) and step t = 0 .. T - 1, in float64 without fused multiply-add, in this order:
+ *     1. u_h = ((p0 m[3h] + p1 m[3h+1]) + t m[3h+2]) + off[h], summed from 0.0, the offset last: hv_resample's expression.
+ *     2. u_h < 0 or u_h > A_h - 1 on any axis (a NaN counts as outside): info[k][2] += 1.  Nothing is padded: only the part of a ray inside
+ *        the volume is measured.
+ *     3. label != NULL and (double)label(q) != label_value, q_h = floor(u_h + 0.5): info[k][3] += 1.
+ *     4. y = hv_resample's float64 sum at `order` 0 / 1 / 3 (taps, weights, mirrored indices, last axis fastest, ((c w0) w1) w2 from 0.0), with
+ *        no output conversion.  y not finite: info[k][4] += 1.
+ *     5. otherwise the sample is counted: info[k][1] += 1.
+ *   Per pixel, over the counted samples:
+ *     sum: the steps are cut into chunks of HV_PROJ_CHUNK consecutive t; a chunk's sum is taken sequentially from +0.0 in increasing t; the
+ *       chunk sums are added sequentially from +0.0 in increasing chunk order, every chunk, the empty ones included.  This order is the
+ *       definition, not an implementation note: the result is the same bytes on every run and equals a restatement in that order.
+ *     min, max: by value, from +inf / -inf; the stored word is m + 0.0, so a zero extreme is always +0.0.
+ *     count, first, last: the number of counted steps, the smallest and the largest counted t.
+ *     No counted step: sum +0.0, min +inf, max -inf, count 0, first T, last -1.
+ *   acc (device, 8-byte aligned): [K][3][P0][P1] float64 -- sum, min, max.  idx (device, 4-byte aligned): [K][3][P0][P1] int32 -- count, first,
+ *   last.  info (device, 8-byte aligned): [K][HV_PROJ_INFO] int64 -- [0] HV_LS_NONFINITE if [4] > 0, ORed with HV_LS_EMPTY if [1] == 0; [1]
+ *   counted; [2] outside; [3] rejected by the label; [4] non-finite; [5 .. 7] 0.  For every k: [1] + [2] + [3] + [4] == P0 * P1 * T and the sum
+ *   of count == [1].
+ *   hv_project_tile (host only): dims[5] = HV_PROJ_CHUNK; the pixels per workgroup and the lanes per ray R when the ray runs along adjacent
+ *   lanes; the same two when a detector axis does (each for a ray of at least R chunks; a shorter ray takes the power of two of lanes that
+ *   covers its chunks and the workgroup 256 / R pixels).
+ *   The entry zeroes info itself on the stream; every word of acc and idx is written.  Only integer atomics: the same bytes on every run,
+ *   for any strides, whatever the buffers held.  No host synchronisation, no scratch.  workspace: hv_project_workspace_bytes bytes, which is 0
+ *   -- the running words live in registers and LDS -- so NULL is accepted; a pointer that is given must be 16-byte aligned.
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (label and workspace excepted), a non-positive extent,
+ *   K or T, K > HV_PROJ_MAX_POSES, an unknown dtype or order, order 3 on anything but float64, a pose entry or label_value that is not finite (with or
+ *   without a label), with a label an unknown label_dtype, a pointer not aligned to its element, an output intersecting an input or another
+ *   output; HV_ERR_UNSUPPORTED: more than 2^30 voxels, P0 * P1 * T > 2^30. */
+enum { HV_PROJ_CHUNK = 16, HV_PROJ_MAX_POSES = 16, HV_PROJ_INFO = 8 };
+int hv_project_tile(int* dims);
+size_t hv_project_workspace_bytes(int A0, int A1, int A2, int K, int P0, int P1, int T);
+int hv_project(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, const void* label,
+               int label_dtype, long long ls0, long long ls1, long long ls2, double label_value, const double* poses, int K, int P0, int P1,
+               int T, int order, double* acc, int* idx, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
