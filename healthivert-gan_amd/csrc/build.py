@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-SOURCES = ['conv_igemm.hip', 'conv_halo.hip', 'conv_halo2.hip', 'conv_lf.hip', 'conv_g4.hip', 'conv_thin.hip', 'conv_px.hip', 'conv_s2t.hip', 'wgrad_halo.hip', 'wgrad_tr.hip', 'conv_narrow.hip', 'conv_head.hip', 'prep.hip', 'norm.hip', 'pointwise.hip', 'attention.hip', 'attention_gram.hip', 'bgemm.hip', 'rhlv.hip', 'assemble.hip', 'infer_prep.hip', 'eval_metrics.hip', 'straighten.hip', 'gen_eval.hip', 'depedicle.hip', 'svm_grade.hip', 'restore.hip', 'spline.hip', 'edt.hip', 'ccl3d.hip', 'morph.hip', 'labelstats.hip', 'filter3d.hip', 'rankfilt.hip', 'resample.hip', 'texture.hip', 'warp.hip', 'similarity.hip', 'shape.hip', 'projection.hip']
+SOURCES = ['conv_igemm.hip', 'conv_halo.hip', 'conv_halo2.hip', 'conv_lf.hip', 'conv_g4.hip', 'conv_thin.hip', 'conv_px.hip', 'conv_s2t.hip', 'wgrad_halo.hip', 'wgrad_tr.hip', 'conv_narrow.hip', 'conv_head.hip', 'prep.hip', 'norm.hip', 'pointwise.hip', 'attention.hip', 'attention_gram.hip', 'bgemm.hip', 'rhlv.hip', 'assemble.hip', 'infer_prep.hip', 'eval_metrics.hip', 'straighten.hip', 'gen_eval.hip', 'depedicle.hip', 'svm_grade.hip', 'restore.hip', 'spline.hip', 'edt.hip', 'ccl3d.hip', 'morph.hip', 'labelstats.hip', 'filter3d.hip', 'rankfilt.hip', 'resample.hip', 'texture.hip', 'texture_runs.hip', 'warp.hip', 'similarity.hip', 'shape.hip', 'projection.hip']
 FLAGS = os.environ.get('HV_EXTRA_FLAGS', '').split() + ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wno-unused-result', '-Wno-inline-asm', '-Rpass-analysis=kernel-resource-usage']
 OUT = os.path.join(PKG, 'libhvgan.so')
 
@@ -49,7 +49,7 @@ def _resources(remarks):
 def build(force=False, verbose=True):
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(HERE, 'hv_common.h'), os.path.join(HERE, 'conv_halo.h'), os.path.join(HERE, 'spline_tap.h'), os.path.join(HERE, 'boundary_map.h'), os.path.join(HERE, 'resample_core.h'), os.path.join(ROOT, 'include', 'hvgan.h')]
+    deps = [os.path.join(HERE, 'hv_common.h'), os.path.join(HERE, 'conv_halo.h'), os.path.join(HERE, 'spline_tap.h'), os.path.join(HERE, 'boundary_map.h'), os.path.join(HERE, 'resample_core.h'), os.path.join(HERE, 'texture_code.h'), os.path.join(ROOT, 'include', 'hvgan.h')]
     jobs = []
     for s in SOURCES:
         src, obj = os.path.join(HERE, s), os.path.join(objdir, s.replace('.hip', '.o'))

@@ -17,17 +17,13 @@
 // Only integer atomics, so the result does not depend on the order of anything; every word of out, info and the workspace that is read was
 // written by an earlier launch of the same call.  No host synchronisation: the grids come from the shape.
 #include <cmath>
-#include "hv_common.h"
+#include "texture_code.h"                     // GL_NONE, the staged code of a voxel that is in no pair; else (slot << 6) | level
 
 #define GL_THREADS 256
 #define GL_T 16                               // tile edge
 #define GL_MAX_PART 1024                      // workgroups per volume at most
-#define GL_NONE 0xFFFFu                       // staged code of a voxel that is in no pair; else (slot << 6) | level
 #define GL_LDS_BYTES 65536                    // dynamic LDS a launch may ask for without an attribute
 
-typedef unsigned long long u64;
-
-struct GlVol { const void* p; int dt; long long sv, s0, s1, s2; };
 struct GlArgs {
     GlVol vol, lab, msk;                      // msk.p == NULL: no mask
     int V, A0, A1, A2, S, D, G, symmetric;
@@ -42,45 +38,12 @@ struct GlArgs {
     unsigned char slot[256];
 };
 
-__device__ __forceinline__ double gl_ld_dt(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
-
-// the slot of voxel (v; i, j, k): 0xFF if masked out, not listed or not a label (then bad = 1); hv_label_stats' rule
-__device__ __forceinline__ int gl_slot(const GlArgs& a, int v, int i, int j, int k, int& bad) {
-    if (a.msk.p && ((const uint8_t*)a.msk.p)[v * a.msk.sv + i * a.msk.s0 + j * a.msk.s1 + k * a.msk.s2] == 0) return 0xFF;
-    const double d = gl_ld_dt(a.lab.p, a.lab.dt, v * a.lab.sv + i * a.lab.s0 + j * a.lab.s1 + k * a.lab.s2);
-    if (!(d >= 0.0 && d <= 255.0 && d == floor(d))) { bad = 1; return 0xFF; }   // NaN fails the first test
-    return a.slot[(int)d];
-}
-
-__device__ __forceinline__ bool gl_finite(double x) { return ((u64)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-
 __global__ __launch_bounds__(GL_THREADS) void glcm_init_kernel(u64* __restrict__ out, long long nout, u64* __restrict__ info, long long ninfo,
                                                                u64* __restrict__ vbad, int V) {
     const long long g = (long long)blockIdx.x * GL_THREADS + threadIdx.x, step = (long long)gridDim.x * GL_THREADS;
     for (long long e = g; e < nout; e += step) out[e] = 0ull;
     for (long long e = g; e < ninfo; e += step) info[e] = 0ull;
     for (long long e = g; e < V; e += step) vbad[e] = 0ull;
-}
-
-// a thread's run of one slot while staging: finite voxels, clamped from below, clamped from above, non-finite met
-struct GlRun { int slot; unsigned n, low, high, flag; };
-
-__device__ __forceinline__ void gl_run_flush(const GlRun& r, unsigned* s_info) {
-    if (r.slot == 0xFF) return;
-    unsigned* w = s_info + r.slot * HV_GLCM_INFO;
-    if (r.flag) atomicOr(&w[0], r.flag);
-    if (r.n) atomicAdd(&w[1], r.n);
-    if (r.low) atomicAdd(&w[2], r.low);
-    if (r.high) atomicAdd(&w[3], r.high);
 }
 
 // the tables of slot s and offsets [c0, c0 + nd) added to out, and zeroed
@@ -280,14 +243,10 @@ extern "C" int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s
     a.msk.p = mask; a.msk.dt = HV_DT_U8; a.msk.sv = msv; a.msk.s0 = ms0; a.msk.s1 = ms1; a.msk.s2 = ms2;
     a.V = V; a.A0 = A0; a.A1 = A1; a.A2 = A2; a.S = S; a.D = D; a.G = G; a.symmetric = (flags & HV_GLCM_SYMMETRIC) ? 1 : 0;
     a.lo = lo; a.width = width;
-    // the logical axes by ascending |stride| of vol, an extent-1 axis last; ties keep the higher axis inside (C order: 2, 1, 0)
     const long long str[3] = {s0, s1, s2};
     const int dims[3] = {A0, A1, A2};
-    int ord[3] = {2, 1, 0};
-    auto weight = [&](int ax) { return dims[ax] == 1 ? (long long)1 << 62 : (str[ax] < 0 ? -str[ax] : str[ax]); };
-    for (int x = 0; x < 2; ++x)
-        for (int y = 0; y < 2 - x; ++y)
-            if (weight(ord[y + 1]) < weight(ord[y])) { const int t = ord[y]; ord[y] = ord[y + 1]; ord[y + 1] = t; }
+    int ord[3];
+    gl_axis_order(str, dims, ord);
     a.ax_in = ord[0]; a.ax_mid = ord[1]; a.ax_out = ord[2];
     const int n0 = hv_cdiv(A0, GL_T);
     a.n1 = hv_cdiv(A1, GL_T); a.n2 = hv_cdiv(A2, GL_T);

@@ -1123,6 +1123,45 @@ int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s0, long lon
             long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const int* offsets, int D, double lo, double width, int G,
             int flags, long long* out, long long* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-label 3-D grey-level run-length matrices, dependence matrices and neighbourhood grey-tone sums of volumes (csrc/texture_runs.hip;
+ * DESIGN.md section 8 row f21).  The reference has no counterpart: the definitions are Galloway's (1975) for run lengths, Sun and Wee's (1983)
+ * for dependence and Amadasun and King's (1989) for the neighbourhood grey-tone difference, in the forms the pyradiomics documentation gives,
+ * in three dimensions and restricted to a label.
+ * Both entries: vol, vol_dtype and strides, label, label_dtype and strides, mask and strides, V, A0..A2, labels[S], lo, width and G exactly as
+ *   for hv_glcm, and so are the SLOT and the LEVEL of a voxel, HV_LS_NONFINITE, HV_LS_BAD_LABEL and info[v][s][0..3].  Two voxels are ALIKE if
+ *   both lie inside the volume, both have a slot, the same one, and both have the same level (a non-finite voxel has no slot here).
+ *   Both zero their outputs and info themselves on the stream.  Only integer atomics: the same bytes on every run, for any strides, single or
+ *   stacked, whatever the outputs, info and the workspace held.  No host synchronisation.  workspace: 16-byte aligned, the queried bytes (the
+ *   per-volume bad-label words and one 16-bit code per voxel; 0 for sizes the entry refuses).
+ * hv_glrlm: offsets (HOST, [D][3] ints, 1 <= D <= HV_GLRLM_MAX_OFFSETS, every component in {-1, 0, 1}, no offset (0, 0, 0), none listed twice and
+ *   none beside its negative: d and -d give the same runs) are copied into the kernel arguments.  R >= 1: the run-length bins.  A RUN along d is
+ *   a maximal sequence p, p + d, ..., p + (L - 1) d of voxels that have a slot and are pairwise alike: p - d is not alike p, p + L d is not
+ *   alike p.  out (device, 8-byte aligned): [V][S][D][G][R] int64; for every run out[v][s][d][level][min(L, R) - 1] += 1.  info (device, 8-byte
+ *   aligned): [V][S][HV_GLRLM_INFO] int64 -- [0..3] as hv_glcm's; [4 + d] the number of runs along offset d with L > R (counted in the last
+ *   bin), 0 for d >= D.
+ * hv_gldm: the neighbourhood of a voxel p is the 26 offsets at Chebyshev distance 1; alpha in 0..G - 1.  For every voxel p with slot s and
+ *   level i: N(p) the neighbours inside the volume with slot s, n = |N(p)|, A the sum of their levels, k how many of them have
+ *   |level - i| <= alpha.  dep (device, 8-byte aligned): [V][S][G][27] int64, dep[v][s][i][k] += 1 (column k + 1 of the pyradiomics matrix).
+ *   ngt (device, 8-byte aligned): [V][S][G][27][2] int64, ngt[v][s][i][n][0] += 1 and ngt[v][s][i][n][1] += |i n - A|: NGTDM's n_i is the sum
+ *   over n >= 1 of [..][0] and its s_i the sum over n >= 1 of [..][1] / n, exact and independent of any summation order.  info (device, 8-byte
+ *   aligned): [V][S][HV_GLCM_INFO] int64 as hv_glcm's.
+ *   Refusals, before any launch and with nothing written -- HV_ERR_ARG: a NULL pointer (mask excepted), a non-positive size, an unknown dtype, S
+ *   outside 1..HV_LS_MAX_LABELS, G outside 2..HV_GLCM_MAX_LEVELS, a label value outside [0, 255] or listed twice, lo not finite, width not finite
+ *   or not > 0, an output or info not 8-byte aligned, a workspace that is not 16-byte aligned or smaller than queried; hv_glrlm: D outside
+ *   1..HV_GLRLM_MAX_OFFSETS, an offset component outside {-1, 0, 1}, a zero offset, an offset listed twice or beside its negative, R < 1;
+ *   hv_gldm: alpha outside 0..G - 1; HV_ERR_UNSUPPORTED: more than 2^30 voxels per volume, V > 65535. */
+enum { HV_GLRLM_MAX_OFFSETS = 13, HV_GLRLM_INFO = 17, HV_GLDM_NEIGHBOURS = 27 };
+size_t hv_glrlm_workspace_bytes(int V, int A0, int A1, int A2, int S, int D, int G, int R);
+int hv_glrlm(const void* vol, int vol_dtype, long long sv, long long s0, long long s1, long long s2, const void* label, int label_dtype,
+             long long lsv, long long ls0, long long ls1, long long ls2, const void* mask, long long msv, long long ms0, long long ms1,
+             long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, const int* offsets, int D, double lo, double width, int G,
+             int R, long long* out, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+size_t hv_gldm_workspace_bytes(int V, int A0, int A1, int A2, int S, int G);
+int hv_gldm(const void* vol, int vol_dtype, long long sv, long long s0, long long s1, long long s2, const void* label, int label_dtype,
+            long long lsv, long long ls0, long long ls1, long long ls2, const void* mask, long long msv, long long ms0, long long ms1,
+            long long ms2, int V, int A0, int A1, int A2, const int* labels, int S, double lo, double width, int G, int alpha, long long* dep,
+            long long* ngt, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- separable linear filtering of a volume, and the weighted composite of two volumes (csrc/filter3d.hip).  The
  * reference filters nothing in 3-D; the definitions are scipy.ndimage.correlate1d / gaussian_filter1d / gaussian_filter (odd-length weights,
  * origin 0) applied to the float64 copy of the input, bit for bit on finite results, NaN where scipy has NaN.
