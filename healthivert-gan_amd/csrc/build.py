@@ -5,6 +5,7 @@
 Objects are rebuilt only when their source (or a header) is newer.  The .so lands next to the
 package (healthivert-gan_amd/libhvgan.so) so it travels with the tree to the GPU box.
 """
+import glob
 import json
 import os
 import re
@@ -49,7 +50,7 @@ def _resources(remarks):
 def build(force=False, verbose=True):
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
-    deps = [os.path.join(HERE, 'hv_common.h'), os.path.join(HERE, 'conv_halo.h'), os.path.join(HERE, 'spline_tap.h'), os.path.join(HERE, 'boundary_map.h'), os.path.join(HERE, 'resample_core.h'), os.path.join(HERE, 'texture_code.h'), os.path.join(ROOT, 'include', 'hvgan.h')]
+    deps = sorted(glob.glob(os.path.join(HERE, '*.h'))) + [os.path.join(ROOT, 'include', 'hvgan.h')]
     jobs = []
     for s in SOURCES:
         src, obj = os.path.join(HERE, s), os.path.join(objdir, s.replace('.hip', '.o'))

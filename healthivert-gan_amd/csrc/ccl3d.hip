@@ -26,7 +26,7 @@
 // No workgroup ever waits for another one: the phases are separated by kernel boundaries only.  Only integer atomics: the results are a pure
 // function of the input, bit for bit the same on every run.  No host synchronisation, no scratch; raster indices are int32 (<= 2^30 voxels),
 // element offsets into the volume 64-bit.
-#include "hv_common.h"
+#include "volume_access.h"                  // hv_up16
 
 #define CC_T0 4
 #define CC_T1 8
@@ -367,7 +367,6 @@ __global__ __launch_bounds__(CC_THREADS) void ccl_fill_kernel(CcSrc S, CcGeo G, 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t cc_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool cc_dims_ok(int A0, int A1, int A2) { return A0 > 0 && A1 > 0 && A2 > 0; }
 static inline bool cc_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_DT_F32 || dt == HV_DT_F64; }
 struct CcWs { size_t parent, sizes, labels, bcount, info, total; };
@@ -375,10 +374,10 @@ static CcWs cc_layout(int A0, int A1, int A2) {
     const size_t N = (size_t)A0 * A1 * A2;
     CcWs W;
     size_t o = 0;
-    W.parent = o; o += cc_up16(N * 4);
-    W.sizes = o; o += cc_up16((N + 1) * 4);
-    W.labels = o; o += cc_up16(N * 4);
-    W.bcount = o; o += cc_up16((size_t)hv_cdiv((long long)N, CC_BLOCK) * 4);
+    W.parent = o; o += hv_up16(N * 4);
+    W.sizes = o; o += hv_up16((N + 1) * 4);
+    W.labels = o; o += hv_up16(N * 4);
+    W.bcount = o; o += hv_up16((size_t)hv_cdiv((long long)N, CC_BLOCK) * 4);
     W.info = o; o += 16;
     W.total = o;
     return W;

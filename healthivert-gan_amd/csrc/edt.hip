@@ -23,7 +23,7 @@
 // percentile by an 8 x 8-bit radix select on the doubles' bit patterns, integer LDS atomics only).  Every floating-point sum has a fixed order.
 #include <climits>
 #include <cmath>
-#include "hv_common.h"
+#include "volume_access.h"                  // hv_up16
 
 #define ED_KT 32                      // columns (unit-stride neighbours) per tile of the axis-1 pass
 #define ED_LINES 32                   // lines per workgroup of the axis-2 pass
@@ -172,7 +172,6 @@ __global__ __launch_bounds__(ED_THREADS) void edt_axis2_kernel(EdGeo G, const T*
     }
 }
 
-static inline size_t ed_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool ed_dims_ok(int A0, int A1, int A2) { return A0 > 0 && A1 > 0 && A2 > 0; }
 static inline bool ed_spacing_ok(const double* sp) {
     if (!sp) return false;
@@ -224,7 +223,7 @@ static int ed_run(const EdSrc& S, const EdGeo& G, const int* n, int carrier, con
 
 extern "C" size_t hv_edt_workspace_bytes(int A0, int A1, int A2) {
     if (!ed_dims_ok(A0, A1, A2)) return 0;
-    return ed_up16((size_t)A0 * A1 * A2 * 4);
+    return hv_up16((size_t)A0 * A1 * A2 * 4);
 }
 
 extern "C" int hv_edt(const void* vol, int dtype, long long s0, long long s1, long long s2, int A0, int A1, int A2, double value,
@@ -259,15 +258,15 @@ static SdWs sd_layout(int A0, int A1, int A2) {
     const size_t N = (size_t)A0 * A1 * A2;
     SdWs W;
     size_t o = 0;
-    W.da = o; o += ed_up16(N * 8);
-    W.db = o; o += ed_up16(N * 8);
-    W.list = o; o += ed_up16(N * 8);
-    W.ws32 = o; o += ed_up16(N * 4);
-    W.mask = o; o += ed_up16(N);
-    W.rec = o; o += ed_up16((size_t)A0 * SD_REC * 4);
-    W.off = o; o += ed_up16((size_t)A0 * 2 * 4);
-    W.psum = o; o += ed_up16((size_t)A0 * 2 * 8);
-    W.pmax = o; o += ed_up16((size_t)A0 * 2 * 8);
+    W.da = o; o += hv_up16(N * 8);
+    W.db = o; o += hv_up16(N * 8);
+    W.list = o; o += hv_up16(N * 8);
+    W.ws32 = o; o += hv_up16(N * 4);
+    W.mask = o; o += hv_up16(N);
+    W.rec = o; o += hv_up16((size_t)A0 * SD_REC * 4);
+    W.off = o; o += hv_up16((size_t)A0 * 2 * 4);
+    W.psum = o; o += hv_up16((size_t)A0 * 2 * 8);
+    W.pmax = o; o += hv_up16((size_t)A0 * 2 * 8);
     W.small = o; o += 64;             // box[6], totals[2], EDT status[2]
     W.total = o;
     return W;

@@ -23,7 +23,7 @@
 // A line is tiled by FI_T outputs, so its length is not limited by LDS.  No workgroup waits for another, no atomics, no host synchronisation, no
 // scratch; every double of the workspace that is read was written by an earlier launch of the same call.
 #include <cmath>
-#include "hv_common.h"
+#include "volume_access.h"                  // hv_up16
 #include "boundary_map.h"
 
 #pragma clang fp contract(off)
@@ -149,7 +149,6 @@ __global__ __launch_bounds__(FI_THREADS) void blend_lerp_kernel(FiBlend B, long 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t fi_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool fi_dims_ok(int A0, int A1, int A2) { return A0 > 0 && A1 > 0 && A2 > 0; }
 static inline bool fi_in_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_DT_I16 || dt == HV_DT_F32 || dt == HV_DT_F64; }
 static inline size_t fi_elem(int dt) { return dt == HV_DT_U8 ? 1 : dt == HV_DT_I16 ? 2 : dt == HV_DT_F32 ? 4 : 8; }
@@ -197,7 +196,7 @@ extern "C" int hv_filter_tile(int* dims) {
 extern "C" size_t hv_filter_workspace_bytes(int A0, int A1, int A2, const hv_filter_axis* axes) {
     int passes = 0;
     if (!fi_dims_ok(A0, A1, A2) || (long long)A0 * A1 * A2 > (1LL << 30) || fi_axes_check(axes, &passes) != HV_OK) return 0;
-    const size_t vol = fi_up16((size_t)A0 * A1 * A2 * sizeof(double));
+    const size_t vol = hv_up16((size_t)A0 * A1 * A2 * sizeof(double));
     return passes <= 1 ? 16 : (size_t)(passes - 1) * vol;       // a uint8 out keeps both volumes between three passes; a float64 out needs one
 }
 
@@ -256,7 +255,7 @@ extern "C" int hv_separable_filter(const void* vol, int dtype, long long s0, lon
         I.radius = 0; I.form = 1; I.w[0] = 1.0;
         return fi_launch(vol, dtype, in_mode == HV_FILT_IN_EQ, value, ss, out, kind, threshold, os, A, 2, I, mode, cval, st);
     }
-    double* wsv[2] = {(double*)workspace, (double*)((char*)workspace + fi_up16((size_t)A0 * A1 * A2 * sizeof(double)))};
+    double* wsv[2] = {(double*)workspace, (double*)((char*)workspace + hv_up16((size_t)A0 * A1 * A2 * sizeof(double)))};
     const void* src = vol;
     const long long* sst = ss;
     int sdt = dtype, seq = in_mode == HV_FILT_IN_EQ, done = 0;

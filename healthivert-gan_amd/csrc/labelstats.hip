@@ -24,7 +24,7 @@
 // Only integer atomics; every workspace word that is read was written by an earlier launch of the same call.  No workgroup waits for another: the
 // phases are kernel boundaries.  No host synchronisation: ranks come from the device counts, grids from the shape.
 #include <cmath>
-#include "hv_common.h"
+#include "volume_access.h"
 
 #define LS_THREADS 256
 #define LS_T 16                               // tile edge
@@ -35,33 +35,19 @@
 #define LS_ACC 16                             // u64 words per (volume, slot) accumulator
 #define LS_MAX_PART 1024                      // workgroups (= partial sums) per volume at most
 #define LS_PAIRS 32                           // (slot, target) pairs whose bins share one workgroup's LDS
-#define LS_NONE 0xFF
-
-typedef unsigned long long u64;
+#define LS_NONE HV_NO_SLOT
 
 // accumulator words
 enum { LA_CNT = 0, LA_SV = 1, LA_SVV = 2, LA_MIN = 3, LA_MAX = 4, LA_C0 = 5, LA_LO0 = 8, LA_HI0 = 11, LA_FLAG = 14 };
 
-struct LsVol { const void* p; int dt; long long sv, s0, s1, s2; };
 struct LsArgs {
-    LsVol vol, lab, msk;                      // msk.p == NULL: no mask
+    HvVol vol, lab, msk;                      // msk.p == NULL: no mask
     int V, A0, A1, A2, S, Q;
     int ax_in, ax_mid, ax_out;                // logical axes by ascending stride of vol
     int n0, n1, n2, ntiles, tpb, P;           // tiles per axis, tiles, tiles per workgroup, workgroups per volume
     unsigned char slot[256];
     double q[HV_LS_MAX_Q];
 };
-
-__device__ __forceinline__ double ls_ld_dt(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
 
 // the order-preserving unsigned key of a value, its width in bits, the way back, and what the sums add
 template <typename T> struct LsKey;
@@ -100,14 +86,6 @@ template <> struct LsKey<double> {
         return ((u64)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
     }
 };
-
-// the slot of voxel (v; i, j, k): LS_NONE if masked out, not listed or not a label (then bad = 1)
-__device__ __forceinline__ int ls_slot(const LsArgs& a, int v, int i, int j, int k, int& bad) {
-    if (a.msk.p && ((const uint8_t*)a.msk.p)[v * a.msk.sv + i * a.msk.s0 + j * a.msk.s1 + k * a.msk.s2] == 0) return LS_NONE;
-    const double d = ls_ld_dt(a.lab.p, a.lab.dt, v * a.lab.sv + i * a.lab.s0 + j * a.lab.s1 + k * a.lab.s2);
-    if (!(d >= 0.0 && d <= 255.0 && d == floor(d))) { bad = 1; return LS_NONE; }   // NaN fails the first test
-    return a.slot[(int)d];
-}
 
 // identity of accumulator word f: minima start at ~0, everything else at 0 (the box's upper corner is kept as hi + 1)
 __device__ __forceinline__ u64 ls_identity(int f) { return (f == LA_MIN || (f >= LA_LO0 && f < LA_HI0)) ? ~0ull : 0ull; }
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(LS_THREADS) void ls_moments_kernel(LsArgs a, u64* _
             int s = LS_NONE;
             T x = (T)0;
             if (i < a.A0 && j < a.A1 && k < a.A2) {
-                s = ls_slot(a, v, i, j, k, bad);
+                s = hv_slot(a, v, i, j, k, bad);
                 if (s != LS_NONE) x = ((const T*)a.vol.p)[v * a.vol.sv + i * a.vol.s0 + j * a.vol.s1 + k * a.vol.s2];
             }
             if (K::FLT) {
@@ -296,7 +274,7 @@ __global__ __launch_bounds__(LS_THREADS) void ls_hist_kernel(LsArgs a, int pass,
         const int u = (int)(e % n_in), m = (int)((e / n_in) % n_mid), o = (int)(e / (n_in * n_mid));
         const int i = a.ax_in == 0 ? u : (a.ax_mid == 0 ? m : o), j = a.ax_in == 1 ? u : (a.ax_mid == 1 ? m : o),
                   k = a.ax_in == 2 ? u : (a.ax_mid == 2 ? m : o);
-        const int s = ls_slot(a, v, i, j, k, bad);
+        const int s = hv_slot(a, v, i, j, k, bad);
         if (s == LS_NONE || s < s_first || s > s_last) continue;
         const u64 key = K::key(((const T*)a.vol.p)[v * a.vol.sv + i * a.vol.s0 + j * a.vol.s1 + k * a.vol.s2]);
         const u64 high = pass == 0 ? 0ull : key >> sh;
@@ -368,7 +346,6 @@ __global__ __launch_bounds__(64) void ls_final_kernel(LsArgs a, const u64* __res
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t ls_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 struct LsWs { size_t acc, vbad, part, sel, hist, total; long long nacc, nhist; int P, tpb, ntiles, n0, n1, n2; };
 static LsWs ls_layout(int V, int A0, int A1, int A2, int S, int Q) {
     LsWs W;
@@ -380,11 +357,11 @@ static LsWs ls_layout(int V, int A0, int A1, int A2, int S, int Q) {
     W.nacc = (long long)V * S * LS_ACC;
     W.nhist = (long long)V * S * 2 * Q * 256;
     W.acc = 0;
-    W.vbad = W.acc + ls_up16((size_t)W.nacc * 8);
-    W.part = W.vbad + ls_up16((size_t)V * 8);
-    W.sel = W.part + ls_up16((size_t)V * W.P * S * 2 * 8);
-    W.hist = W.sel + ls_up16((size_t)V * S * 2 * Q * sizeof(LsSel));
-    W.total = W.hist + ls_up16((size_t)W.nhist * 4);
+    W.vbad = W.acc + hv_up16((size_t)W.nacc * 8);
+    W.part = W.vbad + hv_up16((size_t)V * 8);
+    W.sel = W.part + hv_up16((size_t)V * W.P * S * 2 * 8);
+    W.hist = W.sel + hv_up16((size_t)V * S * 2 * Q * sizeof(LsSel));
+    W.total = W.hist + hv_up16((size_t)W.nhist * 4);
     return W;
 }
 static inline bool ls_sizes_ok(int V, int A0, int A1, int A2, int S, int Q) {
@@ -394,7 +371,7 @@ static inline bool ls_vol_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_D
 static inline bool ls_label_dtype_ok(int dt) { return dt >= HV_DT_U8 && dt <= HV_DT_F64; }
 
 extern "C" size_t hv_label_stats_workspace_bytes(int V, int A0, int A1, int A2, int S, int Q) {
-    if (!ls_sizes_ok(V, A0, A1, A2, S, Q) || (long long)A0 * A1 * A2 > (1LL << 30) || V > 65535) return 0;
+    if (!ls_sizes_ok(V, A0, A1, A2, S, Q) || hv_too_large(V, A0, A1, A2)) return 0;
     return ls_layout(V, A0, A1, A2, S, Q).total;
 }
 
@@ -409,7 +386,7 @@ static int ls_run(const LsArgs& a, const LsWs& W, char* ws, double* out, hipStre
     const long long ninit = W.nacc > W.nhist ? W.nacc : W.nhist;
     hipLaunchKernelGGL(ls_init_kernel, dim3(min(hv_cdiv(ninit, LS_THREADS), 1024)), dim3(LS_THREADS), 0, st, acc, W.nacc, vbad, a.V, hist, W.nhist);
     HV_LAUNCH_CHECK();
-    const size_t lds = (size_t)a.S * LS_ACC * 8 + (K::FLT ? (size_t)4 * a.S * 2 * 8 + (size_t)LS_CELLS * 8 + ls_up16(LS_CELLS) : 0);
+    const size_t lds = (size_t)a.S * LS_ACC * 8 + (K::FLT ? (size_t)4 * a.S * 2 * 8 + (size_t)LS_CELLS * 8 + hv_up16(LS_CELLS) : 0);
     hipLaunchKernelGGL(ls_moments_kernel<T>, dim3(a.P, a.V), dim3(LS_THREADS), lds, st, a, acc, vbad, part);
     HV_LAUNCH_CHECK();
     const int nvs = a.V * a.S;
@@ -439,11 +416,7 @@ extern "C" int hv_label_stats(const void* vol, int vol_dtype, long long sv, long
         !ls_label_dtype_ok(label_dtype) || ((uintptr_t)workspace & 15) || ((uintptr_t)out & 7))
         return HV_ERR_ARG;
     LsArgs a;
-    for (int i = 0; i < 256; ++i) a.slot[i] = LS_NONE;
-    for (int s = 0; s < S; ++s) {
-        if (labels[s] < 0 || labels[s] > 255 || a.slot[labels[s]] != LS_NONE) return HV_ERR_ARG;
-        a.slot[labels[s]] = (unsigned char)s;
-    }
+    if (!hv_slot_table(a.slot, labels, S)) return HV_ERR_ARG;
     for (int t = 0; t < HV_LS_MAX_Q; ++t) {
         a.q[t] = 0.0;
         if (t < Q) {
@@ -451,22 +424,14 @@ extern "C" int hv_label_stats(const void* vol, int vol_dtype, long long sv, long
             a.q[t] = q[t];
         }
     }
-    if ((long long)A0 * A1 * A2 > (1LL << 30) || V > 65535) return HV_ERR_UNSUPPORTED;
+    if (hv_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
     const LsWs W = ls_layout(V, A0, A1, A2, S, Q);
     if (workspace_bytes < W.total) return HV_ERR_ARG;
-    a.vol.p = vol; a.vol.dt = vol_dtype; a.vol.sv = sv; a.vol.s0 = s0; a.vol.s1 = s1; a.vol.s2 = s2;
-    a.lab.p = label; a.lab.dt = label_dtype; a.lab.sv = lsv; a.lab.s0 = ls0; a.lab.s1 = ls1; a.lab.s2 = ls2;
-    a.msk.p = mask; a.msk.dt = HV_DT_U8; a.msk.sv = msv; a.msk.s0 = ms0; a.msk.s1 = ms1; a.msk.s2 = ms2;
+    a.vol = hv_vol(vol, vol_dtype, sv, s0, s1, s2);
+    a.lab = hv_vol(label, label_dtype, lsv, ls0, ls1, ls2);
+    a.msk = hv_vol(mask, HV_DT_U8, msv, ms0, ms1, ms2);
     a.V = V; a.A0 = A0; a.A1 = A1; a.A2 = A2; a.S = S; a.Q = Q;
-    // the logical axes by ascending |stride| of vol, an extent-1 axis last; ties keep the higher axis inside (C order: 2, 1, 0)
-    const long long str[3] = {s0, s1, s2};
-    const int dims[3] = {A0, A1, A2};
-    int ord[3] = {2, 1, 0};
-    auto weight = [&](int ax) { return dims[ax] == 1 ? (long long)1 << 62 : (str[ax] < 0 ? -str[ax] : str[ax]); };
-    for (int x = 0; x < 2; ++x)
-        for (int y = 0; y < 2 - x; ++y)
-            if (weight(ord[y + 1]) < weight(ord[y])) { const int t = ord[y]; ord[y] = ord[y + 1]; ord[y + 1] = t; }
-    a.ax_in = ord[0]; a.ax_mid = ord[1]; a.ax_out = ord[2];
+    hv_axis_order(a.vol, A0, A1, A2, a.ax_in, a.ax_mid, a.ax_out);
     a.n0 = W.n0; a.n1 = W.n1; a.n2 = W.n2; a.ntiles = W.ntiles; a.tpb = W.tpb; a.P = W.P;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

@@ -31,7 +31,7 @@
 // No workgroup waits for another (phases are kernel boundaries), no host synchronisation, no scratch; every byte of the workspace that is read
 // was written by an earlier launch of the same call: the result does not depend on what the workspace held.
 #include <cmath>
-#include "hv_common.h"
+#include "volume_access.h"                  // hv_up16
 
 #define MO_THREADS 256
 #define MO_KT 32                      // columns (unit-stride neighbours) per tile of the axis-1 pass
@@ -222,7 +222,6 @@ __global__ __launch_bounds__(MO_THREADS) void morph_merge_kernel(MoSrc S, MoOut 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t mo_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool mo_dims_ok(int A0, int A1, int A2) { return A0 > 0 && A1 > 0 && A2 > 0; }
 static inline bool mo_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_DT_F32 || dt == HV_DT_F64; }
 static inline bool mo_spacing_ok(const double* sp) {
@@ -257,8 +256,8 @@ static MoWs mo_layout(int A0, int A1, int A2, int cw) {
     const size_t N = (size_t)A0 * A1 * A2;
     MoWs W;
     W.a = 0;
-    W.m = mo_up16(N * cw);
-    W.total = W.m + mo_up16(N);
+    W.m = hv_up16(N * cw);
+    W.total = W.m + hv_up16(N);
     return W;
 }
 static const double mo_unit[3] = {1.0, 1.0, 1.0};

@@ -32,12 +32,11 @@
 // index is formed from a coordinate already tested to lie in [0, A - 1], every label index from floor(u + 0.5) of such coordinates, every
 // output index from a pixel index below the detector's extents.
 #include "resample_core.h"
+#include "volume_access.h"                    // hv_ld_dt, hv_finite
 
 #define PJ_THREADS RS_THREADS
 #define PJ_PX_RAY 16                          // pixels per workgroup at the most lanes per ray when t runs along adjacent lanes
 #define PJ_PX_DET 64                          // ... when a detector axis does
-
-typedef unsigned long long u64;
 
 struct PjP {
     const void* vol; const void* lab;
@@ -53,19 +52,6 @@ struct PjP {
     double lval;
     double pose[HV_PROJ_MAX_POSES][12];       // matrix[9], offset[3]
 };
-
-__device__ __forceinline__ double pj_ld_label(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
-
-__device__ __forceinline__ bool pj_finite(double x) { return ((u64)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 
 // the sum over the taps at (u0, u1, u2), each already inside [0, A - 1]: resample_kernel's tap loop restated
 template <typename T, int ORDER>
@@ -140,13 +126,13 @@ __global__ __launch_bounds__(PJ_THREADS) void project_kernel(PjP P, double* __re
                 }
                 if (P.lab) {
                     const long long q = (long long)floor(u0 + 0.5) * P.l0 + (long long)floor(u1 + 0.5) * P.l1 + (long long)floor(u2 + 0.5) * P.l2;
-                    if (pj_ld_label(P.lab, P.ldt, q) != P.lval) {
+                    if (hv_ld_dt(P.lab, P.ldt, q) != P.lval) {
                         ++n_lab;
                         continue;
                     }
                 }
                 const double y = pj_sample<T, ORDER>(vol, u0, u1, u2, P.A0, P.A1, P.A2, P.s0, P.s1, P.s2);
-                if (!pj_finite(y)) {
+                if (!hv_finite(y)) {
                     ++n_nf;
                     continue;
                 }

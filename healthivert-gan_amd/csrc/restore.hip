@@ -16,7 +16,7 @@
 //   restore_uncrop_kernel   the single-centroid branch (the crop was cut from the raw volume): the plain un-crop of the box.
 // Everything in doubles in the reference's operation order (-ffp-contract=off); element offsets are 64-bit.
 #include <cmath>
-#include "hv_common.h"
+#include "volume_access.h"                                 // hv_ld_dt
 #include "spline_tap.h"                                    // hv_spline_sample
 
 #define RS_THREADS 512
@@ -41,24 +41,13 @@ __device__ __forceinline__ double rs_ld_ct(const void* p, int dt, long long o) {
     return dt == HV_DT_F32 ? (double)((const float*)p)[o] : ((const double*)p)[o];
 }
 
-__device__ __forceinline__ double rs_ld_label(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
-
 __device__ __forceinline__ int rs_sign(double v) { return (v > 0.0) - (v < 0.0); }   // np.sign: sign(0) = 0
 
 // the write rule and the three stores of one voxel
 __device__ __forceinline__ void rs_write(const RsArgs& A, long long px, long long py, long long pz, double v, int l) {
     if (A.where == HV_RESTORE_VERTEBRA) {
         bool own = l == A.vert_id;
-        if (!own) own = rs_ld_label(A.plab, A.pdt, px * A.ps0 + py * A.ps1 + pz * A.ps2) == (double)A.vert_id;
+        if (!own) own = hv_ld_dt(A.plab, A.pdt, px * A.ps0 + py * A.ps1 + pz * A.ps2) == (double)A.vert_id;
         if (!own) return;
     }
     A.out_ct[px * A.os0 + py * A.os1 + pz * A.os2] = v;

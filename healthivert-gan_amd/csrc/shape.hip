@@ -18,7 +18,7 @@
 // Only integer atomics, so the result does not depend on the order of anything; every word of out and the workspace that is read was written by
 // an earlier launch of the same call.  No host synchronisation: the grids come from the shape.
 #include <climits>
-#include "hv_common.h"
+#include "volume_access.h"
 
 #define SH_THREADS 256
 #define SH_T 16                               // tile edge in cells
@@ -31,11 +31,8 @@
 #define SH_DIRS 13
 #define SH_FULL 0x1FFFFu
 
-typedef unsigned long long u64;
-
-struct ShVol { const void* p; int dt; long long sv, s0, s1, s2; };
 struct ShArgs {
-    ShVol lab, msk;                           // msk.p == NULL: no mask
+    HvVol lab, msk;                           // msk.p == NULL: no mask
     int V, A0, A1, A2, S;
     int ax_in, ax_mid, ax_out;                // logical axes by ascending stride of label
     int n1, n2, ntiles, tpb;                  // tiles along axes 1 and 2, tiles, tiles per workgroup
@@ -46,25 +43,6 @@ struct ShArgs {
 // texture.directions(1): the 13 offsets (a, b, c) > (0, 0, 0) in lexicographic order
 __device__ static const signed char sh_dir[SH_DIRS][3] = {{0, 0, 1}, {0, 1, -1}, {0, 1, 0}, {0, 1, 1}, {1, -1, -1}, {1, -1, 0}, {1, -1, 1},
                                                           {1, 0, -1}, {1, 0, 0}, {1, 0, 1}, {1, 1, -1}, {1, 1, 0}, {1, 1, 1}};
-
-__device__ __forceinline__ double sh_ld_dt(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
-
-// the slot of voxel (v; i, j, k) inside the volume: 0xFF if masked out, not listed or not a label (then bad = 1); hv_label_stats' rule
-__device__ __forceinline__ int sh_slot(const ShArgs& a, int v, int i, int j, int k, int& bad) {
-    if (a.msk.p && ((const uint8_t*)a.msk.p)[v * a.msk.sv + i * a.msk.s0 + j * a.msk.s1 + k * a.msk.s2] == 0) return 0xFF;
-    const double d = sh_ld_dt(a.lab.p, a.lab.dt, v * a.lab.sv + i * a.lab.s0 + j * a.lab.s1 + k * a.lab.s2);
-    if (!(d >= 0.0 && d <= 255.0 && d == floor(d))) { bad = 1; return 0xFF; }   // NaN fails the first test
-    return a.slot[(int)d];
-}
 
 __global__ __launch_bounds__(SH_THREADS) void shape_init_kernel(long long* __restrict__ out, long long nout, u64* __restrict__ vbad, int V) {
     const long long g = (long long)blockIdx.x * SH_THREADS + threadIdx.x, step = (long long)gridDim.x * SH_THREADS;
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(SH_THREADS) void shape_count_kernel(ShArgs a, long 
                 const int i = i0 + di, j = j0 + dj, k = k0 + dk;
                 int s = 0xFF;
                 if (i >= 0 && i < a.A0 && j >= 0 && j < a.A1 && k >= 0 && k < a.A2) {
-                    s = sh_slot(a, v, i, j, k, bad);
+                    s = hv_slot(a, v, i, j, k, bad);
                     if (s != 0xFF && !(s_present[s >> 5] >> (s & 31) & 1u)) atomicOr(&s_present[s >> 5], 1u << (s & 31));
                 }
                 st[(di * SH_E + dj) * SH_P2 + dk] = (unsigned char)s;
@@ -260,21 +238,19 @@ __global__ __launch_bounds__(64) void shape_final_kernel(int S, long long cells,
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t sh_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool sh_sizes_ok(int V, int A0, int A1, int A2, int S) {
     return V > 0 && A0 > 0 && A1 > 0 && A2 > 0 && S >= 1 && S <= HV_LS_MAX_LABELS;
 }
 static inline bool sh_supported(int V, int A0, int A1, int A2) {
-    if ((long long)A0 * A1 > (1LL << 30) || V > 65535) return false; // every factor < 2^31: the product of two fits, checked before the third
+    if (hv_too_large(V, A0, A1, A2)) return false;
     const long long vox = (long long)A0 * A1 * A2;
-    if (vox > (1LL << 30)) return false;
     const long long m = (A0 > A1 ? (A0 > A2 ? A0 : A2) : (A1 > A2 ? A1 : A2)) - 1;
     return (unsigned __int128)vox * (unsigned __int128)m * (unsigned __int128)m < ((unsigned __int128)1 << 62);   // sum p_a p_b stays inside int64
 }
 
 extern "C" size_t hv_shape_workspace_bytes(int V, int A0, int A1, int A2, int S) {
     if (!sh_sizes_ok(V, A0, A1, A2, S) || !sh_supported(V, A0, A1, A2)) return 0;
-    return sh_up16((size_t)V * 8);                                   // the per-volume bad-label words
+    return hv_up16((size_t)V * 8);                                   // the per-volume bad-label words
 }
 
 extern "C" int hv_shape(const void* label, int label_dtype, long long lsv, long long ls0, long long ls1, long long ls2, const void* mask,
@@ -284,25 +260,13 @@ extern "C" int hv_shape(const void* label, int label_dtype, long long lsv, long 
         ((uintptr_t)workspace & 15) || ((uintptr_t)out & 7))
         return HV_ERR_ARG;
     ShArgs a;
-    for (int i = 0; i < 256; ++i) a.slot[i] = 0xFF;
-    for (int s = 0; s < S; ++s) {
-        if (labels[s] < 0 || labels[s] > 255 || a.slot[labels[s]] != 0xFF) return HV_ERR_ARG;
-        a.slot[labels[s]] = (unsigned char)s;
-    }
+    if (!hv_slot_table(a.slot, labels, S)) return HV_ERR_ARG;
     if (!sh_supported(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
-    if (workspace_bytes < sh_up16((size_t)V * 8)) return HV_ERR_ARG;
-    a.lab.p = label; a.lab.dt = label_dtype; a.lab.sv = lsv; a.lab.s0 = ls0; a.lab.s1 = ls1; a.lab.s2 = ls2;
-    a.msk.p = mask; a.msk.dt = HV_DT_U8; a.msk.sv = msv; a.msk.s0 = ms0; a.msk.s1 = ms1; a.msk.s2 = ms2;
+    if (workspace_bytes < hv_up16((size_t)V * 8)) return HV_ERR_ARG;
+    a.lab = hv_vol(label, label_dtype, lsv, ls0, ls1, ls2);
+    a.msk = hv_vol(mask, HV_DT_U8, msv, ms0, ms1, ms2);
     a.V = V; a.A0 = A0; a.A1 = A1; a.A2 = A2; a.S = S;
-    // the logical axes by ascending |stride| of label, an extent-1 axis last; ties keep the higher axis inside (C order: 2, 1, 0)
-    const long long str[3] = {ls0, ls1, ls2};
-    const int dims[3] = {A0, A1, A2};
-    int ord[3] = {2, 1, 0};
-    auto weight = [&](int ax) { return dims[ax] == 1 ? (long long)1 << 62 : (str[ax] < 0 ? -str[ax] : str[ax]); };
-    for (int x = 0; x < 2; ++x)
-        for (int y = 0; y < 2 - x; ++y)
-            if (weight(ord[y + 1]) < weight(ord[y])) { const int t = ord[y]; ord[y] = ord[y + 1]; ord[y + 1] = t; }
-    a.ax_in = ord[0]; a.ax_mid = ord[1]; a.ax_out = ord[2];
+    hv_axis_order(a.lab, A0, A1, A2, a.ax_in, a.ax_mid, a.ax_out);
     const int n0 = hv_cdiv((long long)A0 + 1, SH_T);                 // cells -1 .. A - 1 per axis
     a.n1 = hv_cdiv((long long)A1 + 1, SH_T); a.n2 = hv_cdiv((long long)A2 + 1, SH_T);
     const long long nt = (long long)n0 * a.n1 * a.n2;               // <= 2^30 voxels: at most 2^26 + 1 tiles

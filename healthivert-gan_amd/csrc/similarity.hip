@@ -24,12 +24,11 @@
 // written by an earlier launch of the same call.  No host synchronisation, no workspace.  Every moving index is formed from a coordinate already
 // tested to lie in [0, A - 1], every fixed and mask index from a voxel index below the extents, every table index from clamped levels.
 #include "resample_core.h"
+#include "volume_access.h"                    // hv_finite
 
 #define JH_THREADS RS_THREADS
 #define JH_MAX_PART 1024                      // workgroups at most
 #define JH_LDS_BYTES 65536                    // dynamic LDS a launch may ask for without an attribute
-
-typedef unsigned long long u64;
 
 struct JhP {
     const void* fix; const void* mov; const unsigned char* msk;
@@ -52,8 +51,6 @@ __device__ __forceinline__ double jh_ld_dt(const void* p, int dt, long long o) {
         default: return ((const double*)p)[o];
     }
 }
-
-__device__ __forceinline__ bool jh_finite(double x) { return ((u64)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 
 // the sum over the taps at (u0, u1, u2), each already inside [0, A - 1]: resample_kernel's tap loop restated (see warp.hip's wp_sample)
 template <typename T, int ORDER>
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhP P, u64* __re
                     masked = P.msk && P.msk[i0 * P.k0 + i1 * P.k1 + i2 * P.k2] == 0;
                     if (!masked) {
                         const double x = jh_ld_dt(P.fix, P.fdt, i0 * P.f0 + i1 * P.f1 + i2 * P.f2);
-                        if (jh_finite(x)) {
+                        if (hv_finite(x)) {
                             const double t = (x - P.flo) / P.fwidth;
                             flow = t < 0.0;
                             fhigh = t >= (double)P.Gf;
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(JH_THREADS) void joint_hist_kernel(JhP P, u64* __re
                     int bin = 0;
                     if (valid && in) {
                         const double y = jh_sample<T, ORDER>(mov, u0, u1, u2, P.A0, P.A1, P.A2, P.s0, P.s1, P.s2);
-                        if (jh_finite(y)) {
+                        if (hv_finite(y)) {
                             const double t = (y - P.mlo) / P.mwidth;
                             const bool low = t < 0.0, high = t >= (double)P.Gm;
                             mcl = low || high;

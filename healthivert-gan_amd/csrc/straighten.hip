@@ -16,15 +16,13 @@
 #include <climits>
 #include <cmath>
 #include <cstdlib>
-#include "hv_common.h"
+#include "volume_access.h"                 // hv_ld_dt
 #include "spline_tap.h"                   // ss_window, hv_spline_sample
 
 #define SS_HDR 4                      // [0] ~key(min) (atomic max), [1] key(max), [2] bad-label flag, [3] unused
 #define SS_CNT SS_HDR                 // [4 + l] voxel count of label l
 #define SS_SUM (SS_CNT + 256)         // [260 + 3 l + axis] index sums
 #define SS_PRES (SS_SUM + 3 * 256)    // [1028 + l * Rw + w] presence words of the raw geometry
-
-typedef unsigned long long u64;
 
 __host__ __device__ static inline int ss_rows_words(int rows) { return (rows - rows / 2 + 63) / 64; }
 
@@ -35,17 +33,6 @@ __device__ __forceinline__ u64 ss_key(double v) {
 }
 
 template <typename T> __device__ __forceinline__ double ss_ld(const T* p, long long o) { return (double)p[o]; }
-
-__device__ __forceinline__ double ss_ld_dt(const void* p, int dt, long long o) {
-    switch (dt) {
-        case HV_DT_U8: return (double)((const uint8_t*)p)[o];
-        case HV_DT_I16: return (double)((const int16_t*)p)[o];
-        case HV_DT_I32: return (double)((const int32_t*)p)[o];
-        case HV_DT_I64: return (double)((const long long*)p)[o];
-        case HV_DT_F32: return (double)((const float*)p)[o];
-        default: return ((const double*)p)[o];
-    }
-}
 
 // memory-order walk of a [D0][D1][D2] volume with arbitrary strides: the host passes the axes sorted by stride (innermost first)
 struct SsWalk { long long n_in, n_mid, n_out, s_in, s_mid, s_out; int ax_in, ax_mid, ax_out; };
@@ -199,7 +186,7 @@ __global__ __launch_bounds__(256) void straighten_sample_kernel(const T* __restr
                     }
         }
         const long long n0 = (long long)floor(c[0] + 0.5), n1 = (long long)floor(c[1] + 0.5), n2 = (long long)floor(c[2] + 0.5);
-        const double d = ss_ld_dt(label, ldt, n0 * ls0 + n1 * ls1 + n2 * ls2);
+        const double d = hv_ld_dt(label, ldt, n0 * ls0 + n1 * ls1 + n2 * ls2);
         l = d >= 0.0 && d <= 255.0 ? (int)d : 0;         // validated by the stats pass; the guard keeps the presence index in range
     }
     sct[e] = v;
@@ -239,9 +226,9 @@ __global__ __launch_bounds__(256) void straighten_crop_kernel(const void* __rest
     int l = 0;
     if (si >= 0 && si < bx[3] && sj >= 0 && sj < bx[4] && sk >= 0 && sk < bx[5]) {
         const long long x = bx[0] + si, y = bx[1] + sj, z = bx[2] + sk;
-        c = ss_ld_dt(ct, cdt, x * cs0 + y * cs1 + z * cs2);
+        c = hv_ld_dt(ct, cdt, x * cs0 + y * cs1 + z * cs2);
         if (win) c = ss_window(c, wmin, wmax);
-        const double d = ss_ld_dt(label, ldt, x * ls0 + y * ls1 + z * ls2);
+        const double d = hv_ld_dt(label, ldt, x * ls0 + y * ls1 + z * ls2);
         l = d >= 0.0 && d <= 255.0 ? (int)d : 0;
         if (y >= cut[l]) l = 0;
     }

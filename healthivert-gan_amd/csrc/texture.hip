@@ -25,7 +25,7 @@
 #define GL_LDS_BYTES 65536                    // dynamic LDS a launch may ask for without an attribute
 
 struct GlArgs {
-    GlVol vol, lab, msk;                      // msk.p == NULL: no mask
+    HvVol vol, lab, msk;                      // msk.p == NULL: no mask
     int V, A0, A1, A2, S, D, G, symmetric;
     double lo, width;
     int ax_in, ax_mid, ax_out;                // logical axes by ascending stride of vol
@@ -99,14 +99,14 @@ __global__ __launch_bounds__(GL_THREADS) void glcm_count_kernel(GlArgs a, u64* _
                     const bool centre = di >= a.r0 && di < a.r0 + GL_T && dj >= a.r1 && dj < a.r1 + GL_T && dk >= a.r2 && dk < a.r2 + GL_T;
                     const bool own = centre && c0 == 0;
                     int nobad = 0;
-                    const int s = gl_slot(a, v, i, j, k, own ? bad : nobad);
+                    const int s = hv_slot(a, v, i, j, k, own ? bad : nobad);
                     if (own && s != run.slot) {
                         gl_run_flush(run, s_info);
                         run.slot = s; run.n = run.low = run.high = run.flag = 0u;
                     }
                     if (s != 0xFF) {
                         const double x = (double)((const T*)a.vol.p)[v * a.vol.sv + i * a.vol.s0 + j * a.vol.s1 + k * a.vol.s2];
-                        if (gl_finite(x)) {
+                        if (hv_finite(x)) {
                             const double t = (x - a.lo) / a.width;
                             const int lev = t < 0.0 ? 0 : (t >= (double)G ? G - 1 : (int)t);
                             code = (unsigned)(s << 6 | lev);
@@ -184,7 +184,6 @@ __global__ __launch_bounds__(64) void glcm_final_kernel(int V, int S, const u64*
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t gl_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool gl_sizes_ok(int V, int A0, int A1, int A2, int S, int D, int G) {
     return V > 0 && A0 > 0 && A1 > 0 && A2 > 0 && S >= 1 && S <= HV_LS_MAX_LABELS && D >= 1 && D <= HV_GLCM_MAX_OFFSETS && G >= 2 &&
            G <= HV_GLCM_MAX_LEVELS;
@@ -193,8 +192,8 @@ static inline bool gl_vol_dtype_ok(int dt) { return dt == HV_DT_U8 || dt == HV_D
 static inline bool gl_label_dtype_ok(int dt) { return dt >= HV_DT_U8 && dt <= HV_DT_F64; }
 
 extern "C" size_t hv_glcm_workspace_bytes(int V, int A0, int A1, int A2, int S, int D, int G) {
-    if (!gl_sizes_ok(V, A0, A1, A2, S, D, G) || (long long)A0 * A1 * A2 > (1LL << 30) || V > 65535) return 0;
-    return gl_up16((size_t)V * 8);                                   // the per-volume bad-label words
+    if (!gl_sizes_ok(V, A0, A1, A2, S, D, G) || hv_too_large(V, A0, A1, A2)) return 0;
+    return hv_up16((size_t)V * 8);                                   // the per-volume bad-label words
 }
 
 template <typename T>
@@ -218,11 +217,7 @@ extern "C" int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s
         (flags & ~HV_GLCM_SYMMETRIC) || ((uintptr_t)workspace & 15) || ((uintptr_t)out & 7) || ((uintptr_t)info & 7))
         return HV_ERR_ARG;
     GlArgs a;
-    for (int i = 0; i < 256; ++i) a.slot[i] = 0xFF;
-    for (int s = 0; s < S; ++s) {
-        if (labels[s] < 0 || labels[s] > 255 || a.slot[labels[s]] != 0xFF) return HV_ERR_ARG;
-        a.slot[labels[s]] = (unsigned char)s;
-    }
+    if (!hv_slot_table(a.slot, labels, S)) return HV_ERR_ARG;
     int reach[3] = {0, 0, 0};
     for (int d = 0; d < HV_GLCM_MAX_OFFSETS; ++d)
         for (int c = 0; c < 3; ++c) {
@@ -236,18 +231,14 @@ extern "C" int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s
     for (int d = 1; d < D; ++d)
         for (int e = 0; e < d; ++e)
             if (a.off[d][0] == a.off[e][0] && a.off[d][1] == a.off[e][1] && a.off[d][2] == a.off[e][2]) return HV_ERR_ARG;
-    if ((long long)A0 * A1 * A2 > (1LL << 30) || V > 65535) return HV_ERR_UNSUPPORTED;
-    if (workspace_bytes < gl_up16((size_t)V * 8)) return HV_ERR_ARG;
-    a.vol.p = vol; a.vol.dt = vol_dtype; a.vol.sv = sv; a.vol.s0 = s0; a.vol.s1 = s1; a.vol.s2 = s2;
-    a.lab.p = label; a.lab.dt = label_dtype; a.lab.sv = lsv; a.lab.s0 = ls0; a.lab.s1 = ls1; a.lab.s2 = ls2;
-    a.msk.p = mask; a.msk.dt = HV_DT_U8; a.msk.sv = msv; a.msk.s0 = ms0; a.msk.s1 = ms1; a.msk.s2 = ms2;
+    if (hv_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
+    if (workspace_bytes < hv_up16((size_t)V * 8)) return HV_ERR_ARG;
+    a.vol = hv_vol(vol, vol_dtype, sv, s0, s1, s2);
+    a.lab = hv_vol(label, label_dtype, lsv, ls0, ls1, ls2);
+    a.msk = hv_vol(mask, HV_DT_U8, msv, ms0, ms1, ms2);
     a.V = V; a.A0 = A0; a.A1 = A1; a.A2 = A2; a.S = S; a.D = D; a.G = G; a.symmetric = (flags & HV_GLCM_SYMMETRIC) ? 1 : 0;
     a.lo = lo; a.width = width;
-    const long long str[3] = {s0, s1, s2};
-    const int dims[3] = {A0, A1, A2};
-    int ord[3];
-    gl_axis_order(str, dims, ord);
-    a.ax_in = ord[0]; a.ax_mid = ord[1]; a.ax_out = ord[2];
+    hv_axis_order(a.vol, A0, A1, A2, a.ax_in, a.ax_mid, a.ax_out);
     const int n0 = hv_cdiv(A0, GL_T);
     a.n1 = hv_cdiv(A1, GL_T); a.n2 = hv_cdiv(A2, GL_T);
     const long long nt = (long long)n0 * a.n1 * a.n2;               // <= 2^30 voxels: fits an int
@@ -257,7 +248,7 @@ extern "C" int hv_glcm(const void* vol, int vol_dtype, long long sv, long long s
     a.r0 = reach[0]; a.r1 = reach[1]; a.r2 = reach[2];
     a.E0 = GL_T + 2 * a.r0; a.E1 = GL_T + 2 * a.r1; a.E2 = GL_T + 2 * a.r2;
     a.P2 = (a.E2 / 2) % 2 ? a.E2 : a.E2 + 2;
-    a.stage_bytes = (unsigned)gl_up16((size_t)a.E0 * a.E1 * a.P2 * 2);
+    a.stage_bytes = (unsigned)hv_up16((size_t)a.E0 * a.E1 * a.P2 * 2);
     const size_t fixed = a.stage_bytes + (size_t)S * HV_GLCM_INFO * 4 + 16, table = (size_t)G * G * 4;
     const int fit = (int)((GL_LDS_BYTES - fixed) / table);           // >= 2: 24 * 24 * 26 codes and 64 slots leave 34 KiB, a table takes 16 at most
     a.DC = fit < D ? fit : D;

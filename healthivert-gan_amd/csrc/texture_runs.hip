@@ -26,7 +26,7 @@
 #define TR_NB HV_GLDM_NEIGHBOURS              // 0 .. 26 neighbours
 
 struct TrArgs {
-    GlVol vol, lab, msk;                      // msk.p == NULL: no mask
+    HvVol vol, lab, msk;                      // msk.p == NULL: no mask
     int V, A0, A1, A2, N, S, D, G, R, RB, alpha;   // N voxels per volume; RB = min(R, TR_MAX_BINS)
     double lo, width;
     int ax_in, ax_mid;                        // logical axes by ascending stride of vol (the third is the outermost)
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_quant_kernel(TrArgs a, unsigned
         const int u = e % e_in, m = (e / e_in) % e_mid, o = e / (e_in * e_mid);
         const int i = a.ax_in == 0 ? u : (a.ax_mid == 0 ? m : o), j = a.ax_in == 1 ? u : (a.ax_mid == 1 ? m : o),
                   k = a.ax_in == 2 ? u : (a.ax_mid == 2 ? m : o);
-        const int s = gl_slot(a, v, i, j, k, bad);
+        const int s = hv_slot(a, v, i, j, k, bad);
         if (s != run.slot) {
             gl_run_flush(run, s_info);
             run.slot = s; run.n = run.low = run.high = run.flag = 0u;
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_quant_kernel(TrArgs a, unsigned
         unsigned code = GL_NONE;
         if (s != 0xFF) {
             const double x = (double)((const T*)a.vol.p)[v * a.vol.sv + i * a.vol.s0 + j * a.vol.s1 + k * a.vol.s2];
-            if (gl_finite(x)) {
+            if (hv_finite(x)) {
                 const double t = (x - a.lo) / a.width;
                 const int lev = t < 0.0 ? 0 : (t >= (double)G ? G - 1 : (int)t);
                 code = (unsigned)(s << 6 | lev);
@@ -243,20 +243,18 @@ __global__ __launch_bounds__(64) void tr_final_kernel(int V, int S, int info_wor
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline size_t tr_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool tr_sizes_ok(int V, int A0, int A1, int A2, int S, int G) {
     return V > 0 && A0 > 0 && A1 > 0 && A2 > 0 && S >= 1 && S <= HV_LS_MAX_LABELS && G >= 2 && G <= HV_GLCM_MAX_LEVELS;
 }
-static inline bool tr_too_large(int V, int A0, int A1, int A2) { return (long long)A0 * A1 * A2 > (1LL << 30) || V > 65535; }
 // the per-volume bad-label words, then the code volumes
-static inline size_t tr_workspace(int V, int A0, int A1, int A2) { return tr_up16((size_t)V * 8) + tr_up16((size_t)V * A0 * A1 * A2 * 2); }
+static inline size_t tr_workspace(int V, int A0, int A1, int A2) { return hv_up16((size_t)V * 8) + hv_up16((size_t)V * A0 * A1 * A2 * 2); }
 
 extern "C" size_t hv_glrlm_workspace_bytes(int V, int A0, int A1, int A2, int S, int D, int G, int R) {
-    if (!tr_sizes_ok(V, A0, A1, A2, S, G) || D < 1 || D > HV_GLRLM_MAX_OFFSETS || R < 1 || tr_too_large(V, A0, A1, A2)) return 0;
+    if (!tr_sizes_ok(V, A0, A1, A2, S, G) || D < 1 || D > HV_GLRLM_MAX_OFFSETS || R < 1 || hv_too_large(V, A0, A1, A2)) return 0;
     return tr_workspace(V, A0, A1, A2);
 }
 extern "C" size_t hv_gldm_workspace_bytes(int V, int A0, int A1, int A2, int S, int G) {
-    if (!tr_sizes_ok(V, A0, A1, A2, S, G) || tr_too_large(V, A0, A1, A2)) return 0;
+    if (!tr_sizes_ok(V, A0, A1, A2, S, G) || hv_too_large(V, A0, A1, A2)) return 0;
     return tr_workspace(V, A0, A1, A2);
 }
 
@@ -270,14 +268,10 @@ static int tr_prepare(TrArgs& a, const void* vol, int vol_dtype, long long sv, l
         label_dtype > HV_DT_F64 || !std::isfinite(lo) || !std::isfinite(width) || !(width > 0.0) || ((uintptr_t)workspace & 15) ||
         ((uintptr_t)info & 7))
         return HV_ERR_ARG;
-    for (int i = 0; i < 256; ++i) a.slot[i] = 0xFF;
-    for (int s = 0; s < S; ++s) {
-        if (labels[s] < 0 || labels[s] > 255 || a.slot[labels[s]] != 0xFF) return HV_ERR_ARG;
-        a.slot[labels[s]] = (unsigned char)s;
-    }
-    a.vol.p = vol; a.vol.dt = vol_dtype; a.vol.sv = sv; a.vol.s0 = s0; a.vol.s1 = s1; a.vol.s2 = s2;
-    a.lab.p = label; a.lab.dt = label_dtype; a.lab.sv = lsv; a.lab.s0 = ls0; a.lab.s1 = ls1; a.lab.s2 = ls2;
-    a.msk.p = mask; a.msk.dt = HV_DT_U8; a.msk.sv = msv; a.msk.s0 = ms0; a.msk.s1 = ms1; a.msk.s2 = ms2;
+    if (!hv_slot_table(a.slot, labels, S)) return HV_ERR_ARG;
+    a.vol = hv_vol(vol, vol_dtype, sv, s0, s1, s2);
+    a.lab = hv_vol(label, label_dtype, lsv, ls0, ls1, ls2);
+    a.msk = hv_vol(mask, HV_DT_U8, msv, ms0, ms1, ms2);
     a.V = V; a.A0 = A0; a.A1 = A1; a.A2 = A2; a.S = S; a.G = G; a.D = 0; a.R = a.RB = 1; a.alpha = 0;
     a.lo = lo; a.width = width;
     for (int d = 0; d < HV_GLRLM_MAX_OFFSETS; ++d) a.off[d][0] = a.off[d][1] = a.off[d][2] = 0;
@@ -287,11 +281,8 @@ static int tr_prepare(TrArgs& a, const void* vol, int vol_dtype, long long sv, l
 // the sizes that need at most 2^30 voxels: N, the quantising loop's axes, the partition.  -> workgroups per volume
 static int tr_partition(TrArgs& a) {
     a.N = a.A0 * a.A1 * a.A2;
-    const long long str[3] = {a.vol.s0, a.vol.s1, a.vol.s2};
-    const int dims[3] = {a.A0, a.A1, a.A2};
-    int ord[3];
-    gl_axis_order(str, dims, ord);
-    a.ax_in = ord[0]; a.ax_mid = ord[1];
+    int ax_out;
+    hv_axis_order(a.vol, a.A0, a.A1, a.A2, a.ax_in, a.ax_mid, ax_out);
     const int per = hv_cdiv(a.N, TR_MAX_PART);
     a.vpb = hv_cdiv(per > TR_MIN_VPB ? per : TR_MIN_VPB, TR_THREADS) * TR_THREADS;
     return hv_cdiv(a.N, a.vpb);
@@ -333,13 +324,13 @@ extern "C" int hv_glrlm(const void* vol, int vol_dtype, long long sv, long long 
             if (same || neg) return HV_ERR_ARG;
         }
     }
-    if (tr_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
+    if (hv_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
     if (workspace_bytes < tr_workspace(V, A0, A1, A2)) return HV_ERR_ARG;
     a.D = D; a.R = R; a.RB = R < TR_MAX_BINS ? R : TR_MAX_BINS;
     const int P = tr_partition(a);
     hipStream_t st = (hipStream_t)stream;
     u64* vbad = (u64*)workspace;
-    unsigned short* codes = (unsigned short*)((char*)workspace + tr_up16((size_t)V * 8));
+    unsigned short* codes = (unsigned short*)((char*)workspace + hv_up16((size_t)V * 8));
     const long long nout = (long long)V * S * D * G * R, ninfo = (long long)V * S * HV_GLRLM_INFO;
     hipLaunchKernelGGL(tr_init_kernel, dim3(min(hv_cdiv(nout, TR_THREADS * 4), 2048)), dim3(TR_THREADS), 0, st, (u64*)out, nout, (u64*)info, ninfo,
                        (u64*)nullptr, 0LL, vbad, V);
@@ -364,13 +355,13 @@ extern "C" int hv_gldm(const void* vol, int vol_dtype, long long sv, long long s
                               labels, S, lo, width, G, info, workspace);
     if (rc != HV_OK) return rc;
     if (alpha < 0 || alpha > G - 1) return HV_ERR_ARG;
-    if (tr_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
+    if (hv_too_large(V, A0, A1, A2)) return HV_ERR_UNSUPPORTED;
     if (workspace_bytes < tr_workspace(V, A0, A1, A2)) return HV_ERR_ARG;
     a.alpha = alpha;
     const int P = tr_partition(a);
     hipStream_t st = (hipStream_t)stream;
     u64* vbad = (u64*)workspace;
-    unsigned short* codes = (unsigned short*)((char*)workspace + tr_up16((size_t)V * 8));
+    unsigned short* codes = (unsigned short*)((char*)workspace + hv_up16((size_t)V * 8));
     const long long ndep = (long long)V * S * G * TR_NB, ninfo = (long long)V * S * HV_GLCM_INFO;
     hipLaunchKernelGGL(tr_init_kernel, dim3(min(hv_cdiv(ndep * 2, TR_THREADS * 4), 2048)), dim3(TR_THREADS), 0, st, (u64*)dep, ndep, (u64*)ngt,
                        ndep * 2, (u64*)info, ninfo, vbad, V);

@@ -34,7 +34,8 @@ import torch
 from . import lib as _lib
 from . import resample as _rs
 from .components import _device, _ll
-from .label_statistics import NONFINITE, EMPTY, _check_spacing  # noqa: F401  (the status bits of info[:, 0])
+from .label_statistics import NONFINITE, EMPTY  # noqa: F401  (the status bits of info[:, 0])
+from .labelled import check_spacing
 from .similarity import _check_poses, rotation_matrix
 from .straighten import _DT as _LABEL_DT
 
@@ -85,7 +86,7 @@ def view_pose(shape, spacing, view, det_spacing=None, step_mm=None, det_shape=No
     A named view with the volume's own pitches and extents samples every voxel once, at whole indices.  Host only, float64.
     -> ViewPose(matrix, offset, det_shape, steps, det_spacing, step_mm)"""
     n = np.array(_rs._check_shape(shape, 'shape'), dtype=np.float64)
-    sp = np.array(_check_spacing(spacing), dtype=np.float64)
+    sp = np.array(check_spacing(spacing), dtype=np.float64)
     f = view_frame(view)
     if det_spacing is None:
         ds = np.array([sp.min(), sp.min()])

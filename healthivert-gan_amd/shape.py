@@ -13,7 +13,6 @@ directions as exact integers; everything floating is numpy float64 on the host, 
   shape_comparison(label_original, label_synth, vert_id, neighbours=(), spacing=(1, 1, 1))
 label and mask are what label_statistics takes (device tensors [A0][A1][A2] or stacked [V][A0][A1][A2], any strides); a numpy array is uploaded
 first.  Nothing is counted on the host: a CPU tensor is a ValueError."""
-import ctypes
 import functools
 import math
 
@@ -21,10 +20,9 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from . import ops
-from . import label_statistics as _ls
-from .label_statistics import BAD_LABEL, EMPTY, MAX_LABELS  # noqa: F401  (the status bits of 'status')
-from .texture import directions, _resident
+from . import labelled as _lb
+from .label_statistics import BAD_LABEL, EMPTY, MAX_LABELS, present  # noqa: F401  (the status bits of 'status')
+from .texture import directions
 
 REC, COUNT, SUM, SUM2, EXTENT, STATUS = 320, 256, 257, 260, 266, 292      # HV_SHAPE_* of include/hvgan.h
 QUADRATURE_POINTS = 200000
@@ -34,38 +32,19 @@ _PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 
 
 # ------------------------------------------------------------------------------------------------ the device half
-def _check_label(label, mask):
-    _ls._check_tensor(label, 'label', _ls._LABEL_DT)
-    if mask is not None:
-        _ls._check_tensor(mask, 'mask', (torch.uint8, torch.bool), label.shape)
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        if mask.device != label.device:
-            raise ValueError('label and mask must lie on one device')
-    return _ls._as4(label), None if mask is None else _ls._as4(mask)
-
-
 def _launch(label, mask, labels, out):
     """Queue one hv_shape on the current stream: 4-D device tensors (mask may be None), out int64 [V][S][REC]."""
-    L = _lib.get()
-    V, A0, A1, A2 = (int(s) for s in label.shape)
-    S = len(labels)
-    need = L.size('hv_shape_workspace_bytes', V, A0, A1, A2, S)
-    if need == 0:
-        raise ValueError('shape: at most 2^30 voxels per volume, 65535 volumes per call and voxels * (largest extent - 1)^2 < 2^62, got shape %s'
-                         % (tuple(label.shape),))
-    ws, wsz = ops._ws(need, label.device, slot=3)
-    mst = mask.stride() if mask is not None else (0, 0, 0, 0)
-    L.call('hv_shape', _lib.ptr(label), _ls._LABEL_DT[label.dtype], *_ls._ll(label.stride()), _lib.ptr(mask), *_ls._ll(mst), V, A0, A1, A2,
-           (ctypes.c_int * S)(*labels), S, _lib.ptr(out), _lib.ptr(ws), wsz, _lib.stream())
+    ws, wsz = _lb.workspace('shape', label, len(labels), limit='at most 2^30 voxels per volume, 65535 volumes per call and voxels * (largest extent '
+                            '- 1)^2 < 2^62')
+    _lib.get().call('hv_shape', *_lb.volume_args(None, label, mask, labels), _lib.ptr(out), _lib.ptr(ws), wsz, _lib.stream())
 
 
 def _present(l4, m4):
     """The non-zero label values with a counted voxel in any volume: label_statistics' count-only passes with the label as its own volume."""
-    if l4.dtype in _ls._VOL_DT:
-        return _ls._present(l4, l4, m4)
+    if l4.dtype in _lb.VOL_DT:
+        return present(l4, l4, m4)
     vol = torch.empty((1,) + tuple(l4.shape[1:]), dtype=torch.uint8, device=l4.device).expand(l4.shape)   # never summed: the counts only
-    return _ls._present(vol, l4, m4)
+    return present(vol, l4, m4)
 
 
 def _split(rec, labels):
@@ -77,15 +56,8 @@ def _split(rec, labels):
 
 def _records(label, labels, mask):
     """-> (records int64 [V][S][REC] on the host, the label list, whether the caller gave one volume): one launch sequence, one readback."""
-    label, mask = _resident(label), _resident(mask)
-    single = isinstance(label, torch.Tensor) and label.dim() == 3
-    l4, m4 = _check_label(label, mask)
-    if labels is None:
-        ids = _present(l4, m4)
-        if not 1 <= len(ids) <= MAX_LABELS:
-            raise ValueError('labels=None: 1 to %d non-zero label values expected in the volumes, found %d' % (MAX_LABELS, len(ids)))
-    else:
-        ids = _ls._check_labels(labels)
+    single, _, l4, m4 = _lb.check_inputs(None, label, mask, upload=True)
+    ids = _lb.resolve_labels(labels, lambda: _present(l4, m4))
     out = torch.empty((int(l4.shape[0]), len(ids), REC), dtype=torch.int64, device=l4.device)
     _launch(l4, m4, ids, out)
     return out.cpu().numpy(), ids, single
@@ -101,7 +73,7 @@ def configurations(label, labels=None, mask=None):
     labels=None: the non-zero label values present, as label_statistics finds them."""
     rec, ids, single = _records(label, labels, mask)
     res = _split(rec, ids)
-    return {k: (v if k == 'labels' else v[0]) for k, v in res.items()} if single else res
+    return _lb.squeeze(res) if single else res
 
 
 # ------------------------------------------------------------------------------------------------ the host half
@@ -148,7 +120,7 @@ def direction_weights(spacing=(1, 1, 1)):
     z_i = 1 - 2 (i + 1/2) / N, phi_i = (i + 1/2) pi (3 - sqrt 5), P_i = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), each assigned to
     the direction with the largest |P . u| (the first on a tie).  Isotropic: 0.0916, 0.0740, 0.0704 for axes, face and space diagonals (Ohser
     and Muecklich: 0.091556, 0.073961, 0.070391).  -> float64 [13], summing to 1."""
-    return _weights(_ls._check_spacing(spacing)).copy()
+    return _weights(_lb.check_spacing(spacing)).copy()
 
 
 def minkowski(histogram, spacing=(1, 1, 1)):
@@ -164,7 +136,7 @@ def minkowski(histogram, spacing=(1, 1, 1)):
     h = np.asarray(histogram)
     if h.ndim < 1 or h.shape[-1] != 256 or h.dtype.kind not in 'iu':
         raise ValueError('histogram: an integer array [...][256] expected, got %s' % (getattr(h, 'shape', None),))
-    sp = np.asarray(_ls._check_spacing(spacing), dtype=np.float64)
+    sp = np.asarray(_lb.check_spacing(spacing), dtype=np.float64)
     h = h.astype(np.int64)
     pop, chi6, chi26, hits, shared = _config_tables()
     out = {'count': (h @ pop) // 8, 'euler_6': (h @ chi6) // 8, 'euler_26': (h @ chi26) // 8}
@@ -182,7 +154,7 @@ def minkowski(histogram, spacing=(1, 1, 1)):
 def descriptors_from_records(rec, labels, spacing=(1, 1, 1)):
     """The host half of shape_descriptors: records int64 [V][S][REC] -> the dict of arrays [V][S][...]."""
     rec = np.ascontiguousarray(rec, dtype=np.int64)
-    sp = np.asarray(_ls._check_spacing(spacing), dtype=np.float64)
+    sp = np.asarray(_lb.check_spacing(spacing), dtype=np.float64)
     V, S = rec.shape[:2]
     mk = minkowski(rec[..., :256], spacing)
     nan = float('nan')
@@ -232,28 +204,22 @@ def shape_descriptors(label, labels=None, spacing=(1, 1, 1), mask=None):
     caliper_widths [..][13] ((max - min of d . p) / |d / s|: the centre-to-centre width along the physical direction d / s, mm) and their
     max_caliper_width, min_caliper_width.  A label without a voxel, or without a surface, gives NaN where nothing is defined; nothing raises.
     One launch sequence and one readback."""
-    sp = _ls._check_spacing(spacing)
+    sp = _lb.check_spacing(spacing)
     rec, ids, single = _records(label, labels, mask)
     res = descriptors_from_records(rec, ids, sp)
-    return _ls._squeeze(res) if single else res
+    return _lb.squeeze(res) if single else res
 
 
 def _one(res, v, s):
     return {k: (int(res[k][s]) if k == 'labels' else res[k][v][s]) for k in res}
 
 
-def _check_one(label, name, shape=None):
-    label = _resident(label)
-    _ls._check_3d(label, name, _ls._LABEL_DT, shape)
-    return label
-
-
 def vertebra_shape(label, vert_id, spacing=(1, 1, 1), largest_component=False):
     """The shape of one vertebra: shape_descriptors of label == vert_id as scalars / small arrays.  largest_component=True: of its largest
     6-connected component (components.keep_largest_component runs first; the caller's volume is not changed)."""
-    sp = _ls._check_spacing(spacing)
-    vid = _ls._check_labels([vert_id])[0]
-    label = _check_one(label, 'label')
+    sp = _lb.check_spacing(spacing)
+    vid = _lb.check_labels([vert_id])[0]
+    label = _lb.check_3d(_lb.resident(label), 'label', _lb.LABEL_DT)
     if largest_component:
         from . import components
         label = components.keep_largest_component(label, vid, fill=0 if vid != 0 else 255)
@@ -268,19 +234,10 @@ def shape_comparison(label_original, label_synth, vert_id, neighbours=(), spacin
     'neighbour_ratio': {scalar: synthesized / the mean over the neighbours}} for the scalars of SCALARS (no neighbours: NaN).
     The two labels run as ONE batch (V = 2, the second volume addressed through the batch stride, no copy) when they agree in dtype and
     strides, else as two calls into one result buffer; one readback either way."""
-    sp = _ls._check_spacing(spacing)
-    ids = _ls._check_labels([vert_id] + list(neighbours))
-    label_original = _check_one(label_original, 'label_original')
-    label_synth = _check_one(label_synth, 'label_synth', label_original.shape)
-    if label_synth.device != label_original.device:
-        raise ValueError('label_original and label_synth must lie on one device')
-    out = torch.empty((2, len(ids), REC), dtype=torch.int64, device=label_original.device)
-    d = label_synth.data_ptr() - label_original.data_ptr()
-    if label_synth.dtype == label_original.dtype and label_synth.stride() == label_original.stride() and d % label_original.element_size() == 0:
-        _launch(_ls._Strided(label_original, d // label_original.element_size()), None, ids, out)
-    else:
-        _launch(label_original[None], None, ids, out[0:1])
-        _launch(label_synth[None], None, ids, out[1:2])
+    pair = _lb.Pair(label_original, label_synth, [vert_id] + list(neighbours), spacing=spacing)
+    ids, sp = pair.ids, pair.spacing
+    out = torch.empty((2, len(ids), REC), dtype=torch.int64, device=pair.device)
+    pair.launch(lambda _, label, mask, sel: _launch(label, mask, ids, out[sel]))
     res = descriptors_from_records(out.cpu().numpy(), ids, sp)
     ori, syn = _one(res, 0, 0), _one(res, 1, 0)
     nb = {i: _one(res, 0, s) for s, i in enumerate(ids) if s > 0}

@@ -21,9 +21,8 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from . import ops
-from . import label_statistics as _ls
-from .label_statistics import BAD_LABEL, NONFINITE, EMPTY, MAX_LABELS  # noqa: F401  (the status bits of 'status')
+from . import labelled as _lb
+from .label_statistics import BAD_LABEL, NONFINITE, EMPTY, MAX_LABELS, present  # noqa: F401  (the status bits of 'status')
 
 MAX_LEVELS, MAX_OFFSETS, MAX_REACH, INFO = 64, 26, 4, 4                # HV_GLCM_* of include/hvgan.h
 SYMMETRIC = 1
@@ -41,7 +40,7 @@ def directions(distance=1):
     return np.asarray([[int(d) * x for x in u] for d in ds for u in unit], dtype=np.int64)
 
 
-def _check_offsets(offsets):
+def check_offsets(offsets):
     try:
         off = np.asarray(offsets)
         same = off.ndim == 2 and off.shape[1] == 3 and bool((off == np.floor(off)).all())
@@ -54,7 +53,7 @@ def _check_offsets(offsets):
     return off
 
 
-def _check_levels(levels, lo, width):
+def check_levels(levels, lo, width):
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 2 <= levels <= MAX_LEVELS:
         raise ValueError('levels: an integer in [2, %d] expected, got %r' % (MAX_LEVELS, levels))
     try:
@@ -66,13 +65,6 @@ def _check_levels(levels, lo, width):
     return int(levels), lo, width
 
 
-def _resident(x):
-    """A numpy array uploaded to the current device; anything else as it is (the checks of label_statistics refuse what is no device tensor)."""
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    return x
-
-
 def _buffers(V, S, D, G, device):
     """One int64 allocation for out [V][S][D][G][G] and info [V][S][INFO]: one readback brings both."""
     nout = V * S * D * G * G
@@ -82,19 +74,11 @@ def _buffers(V, S, D, G, device):
 
 def _launch(vol, label, mask, labels, offsets, levels, lo, width, symmetric, out, info):
     """Queue one hv_glcm on the current stream: 4-D device tensors (mask may be None), out int64 [V][S][D][G][G], info int64 [V][S][INFO]."""
-    L = _lib.get()
-    V, A0, A1, A2 = (int(s) for s in vol.shape)
-    S, D = len(labels), len(offsets)
-    need = L.size('hv_glcm_workspace_bytes', V, A0, A1, A2, S, D, levels)
-    if need == 0:
-        raise ValueError('glcm: at most 2^30 voxels per volume and 65535 volumes per call, got shape %s' % (tuple(vol.shape),))
-    ws, wsz = ops._ws(need, vol.device, slot=3)
-    mst = mask.stride() if mask is not None else (0, 0, 0, 0)
+    D = len(offsets)
+    ws, wsz = _lb.workspace('glcm', vol, len(labels), D, levels)
     flat = [int(x) for x in np.asarray(offsets).reshape(-1)]
-    L.call('hv_glcm', _lib.ptr(vol), _ls._VOL_DT[vol.dtype], *_ls._ll(vol.stride()), _lib.ptr(label), _ls._LABEL_DT[label.dtype],
-           *_ls._ll(label.stride()), _lib.ptr(mask), *_ls._ll(mst), V, A0, A1, A2, (ctypes.c_int * S)(*labels), S, (ctypes.c_int * (3 * D))(*flat), D,
-           ctypes.c_double(lo), ctypes.c_double(width), levels, SYMMETRIC if symmetric else 0, _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws), wsz,
-           _lib.stream())
+    _lib.get().call('hv_glcm', *_lb.volume_args(vol, label, mask, labels), (ctypes.c_int * (3 * D))(*flat), D, ctypes.c_double(lo),
+                    ctypes.c_double(width), levels, SYMMETRIC if symmetric else 0, _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws), wsz, _lib.stream())
 
 
 def _result(buf, V, S, D, G, labels, offsets):
@@ -120,22 +104,15 @@ def glcm(vol, label, labels=None, offsets=None, levels=32, lo=-200.0, width=25.0
     'clamped_low', 'clamped_high' (how many of them lay below lo / at or above lo + levels * width), 'status' (label_statistics' bits: 1 the
     volume holds a label that is no integer in [0, 255], 2 a NaN or infinity inside the label -- it is in no pair --, 4 no voxel)}, the last four
     [V][S] ([S]).  One launch sequence and one readback.  labels=None: the non-zero label values present, as label_statistics finds them."""
-    G, lo, width = _check_levels(levels, lo, width)
-    off = directions(1) if offsets is None else _check_offsets(offsets)
-    vol, label, mask = _resident(vol), _resident(label), _resident(mask)
-    single = isinstance(vol, torch.Tensor) and vol.dim() == 3
-    v4, l4, m4 = _ls._check_inputs(vol, label, mask)
-    if labels is None:
-        ids = _ls._present(v4, l4, m4)
-        if not 1 <= len(ids) <= MAX_LABELS:
-            raise ValueError('labels=None: 1 to %d non-zero label values expected in the volumes, found %d' % (MAX_LABELS, len(ids)))
-    else:
-        ids = _ls._check_labels(labels)
+    G, lo, width = check_levels(levels, lo, width)
+    off = directions(1) if offsets is None else check_offsets(offsets)
+    single, v4, l4, m4 = _lb.check_inputs(vol, label, mask, upload=True)
+    ids = _lb.resolve_labels(labels, lambda: present(v4, l4, m4))
     V, S, D = int(v4.shape[0]), len(ids), len(off)
     buf, out, info = _buffers(V, S, D, G, v4.device)
     _launch(v4, l4, m4, ids, off, G, lo, width, bool(symmetric), out, info)
     res = _result(buf, V, S, D, G, ids, off)
-    return {k: (v if k in _PER_CALL else v[0]) for k, v in res.items()} if single else res
+    return _lb.squeeze(res, _PER_CALL) if single else res
 
 
 def haralick_features(matrices):
@@ -171,7 +148,7 @@ def haralick_features(matrices):
 
 
 def _offsets_of(offsets, distance):
-    return directions(distance) if offsets is None else _check_offsets(offsets)
+    return directions(distance) if offsets is None else check_offsets(offsets)
 
 
 def _one(res, feats, v, s):
@@ -191,20 +168,9 @@ def vertebra_texture(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), levels
     directions(distance) unless `offsets` lists them.
     -> {'label', 'offsets', 'matrices' [D][G][G], 'count', 'clamped_low', 'clamped_high', 'status', 'features': haralick_features of the
     matrices ([D] each, and 'mean')}."""
-    sp = _ls._check_spacing(spacing)
-    r = _ls._check_erode(erode_mm)
-    vid = _ls._check_labels([vert_id])[0]
     off = _offsets_of(offsets, distance)
-    _check_levels(levels, lo, width)
-    ct, label = _resident(ct), _resident(label)
-    _ls._check_3d(ct, 'ct', _ls._VOL_DT)
-    _ls._check_3d(label, 'label', _ls._LABEL_DT, ct.shape)
-    if median_size is not None:
-        from . import rank_filters
-        ct = rank_filters.median_filter(ct, size=median_size)
-    mask = None
-    if r > 0.0:
-        mask = _ls._core_mask(label, [vid], r, sp, torch.empty(tuple(label.shape), dtype=torch.uint8, device=label.device))
+    check_levels(levels, lo, width)
+    ct, label, mask, vid, _ = _lb.vertebra_inputs(ct, label, vert_id, erode_mm, spacing, median_size)
     res = glcm(ct[None], label[None], [vid], off, levels, lo, width, symmetric, None if mask is None else mask[None])
     return _one(res, haralick_features(res['matrices']), 0, 0)
 
@@ -218,40 +184,13 @@ def texture_comparison(ct_original, ct_synth, label_original, label_synth, vert_
     'neighbour_difference': {id: {feature: synthesized - neighbour}}}, the differences those of the features' means over the offsets.
     The two pairs run as ONE batch (V = 2, the second volume addressed through the batch stride, no copy) when the CTs agree in dtype and
     strides and the labels do, else as two calls into one result buffer; one readback either way."""
-    sp = _ls._check_spacing(spacing)
-    r = _ls._check_erode(erode_mm)
-    ids = _ls._check_labels([vert_id] + list(neighbours))
     off = _offsets_of(offsets, distance)
-    G, lo, width = _check_levels(levels, lo, width)
-    ct_original, ct_synth, label_original, label_synth = (_resident(t) for t in (ct_original, ct_synth, label_original, label_synth))
-    _ls._check_3d(ct_original, 'ct_original', _ls._VOL_DT)
-    _ls._check_3d(ct_synth, 'ct_synth', _ls._VOL_DT, ct_original.shape)
-    _ls._check_3d(label_original, 'label_original', _ls._LABEL_DT, ct_original.shape)
-    _ls._check_3d(label_synth, 'label_synth', _ls._LABEL_DT, ct_original.shape)
-    if ct_synth.dtype != ct_original.dtype:
-        raise TypeError('ct_synth: the dtype of ct_original (%s) expected, got %s' % (ct_original.dtype, ct_synth.dtype))
-    dev, shape = ct_original.device, tuple(ct_original.shape)
-    masks = None
-    if r > 0.0:
-        masks = torch.empty((2,) + shape, dtype=torch.uint8, device=dev)
-        _ls._core_mask(label_original, ids, r, sp, masks[0])
-        _ls._core_mask(label_synth, ids[:1], r, sp, masks[1])
+    G, lo, width = check_levels(levels, lo, width)
+    pair = _lb.Pair(label_original, label_synth, [vert_id] + list(neighbours), ct_original, ct_synth, erode_mm, spacing)
+    ids, sym = pair.ids, bool(symmetric)
     S, D = len(ids), len(off)
-    buf, out, info = _buffers(2, S, D, G, dev)
-
-    def batch_stride(a, b):
-        """b's distance from a in elements if the pair can be addressed as a [2][...] batch, else None."""
-        d = b.data_ptr() - a.data_ptr()
-        ok = a.dtype == b.dtype and a.stride() == b.stride() and d % a.element_size() == 0
-        return d // a.element_size() if ok else None
-
-    cs, lsd = batch_stride(ct_original, ct_synth), batch_stride(label_original, label_synth)
-    sym = bool(symmetric)
-    if cs is not None and lsd is not None:
-        _launch(_ls._Strided(ct_original, cs), _ls._Strided(label_original, lsd), masks, ids, off, G, lo, width, sym, out, info)
-    else:
-        _launch(ct_original[None], label_original[None], None if masks is None else masks[0:1], ids, off, G, lo, width, sym, out[0:1], info[0:1])
-        _launch(ct_synth[None], label_synth[None], None if masks is None else masks[1:2], ids, off, G, lo, width, sym, out[1:2], info[1:2])
+    buf, out, info = _buffers(2, S, D, G, pair.device)
+    pair.launch(lambda vol, label, mask, sel: _launch(vol, label, mask, ids, off, G, lo, width, sym, out[sel], info[sel]))
     res = _result(buf, 2, S, D, G, ids, off)
     feats = haralick_features(res['matrices'])
     ori, syn = _one(res, feats, 0, 0), _one(res, feats, 1, 0)

@@ -22,10 +22,9 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from . import ops
-from . import label_statistics as _ls
-from .label_statistics import BAD_LABEL, NONFINITE, EMPTY, MAX_LABELS  # noqa: F401  (the status bits of 'status')
-from .texture import INFO, directions, _check_levels, _resident
+from . import labelled as _lb
+from .label_statistics import BAD_LABEL, NONFINITE, EMPTY, MAX_LABELS, present  # noqa: F401  (the status bits of 'status')
+from .texture import INFO, directions, check_levels
 
 MAX_OFFSETS, RLM_INFO, NEIGHBOURS = 13, 17, 27                           # HV_GLRLM_MAX_OFFSETS, HV_GLRLM_INFO, HV_GLDM_NEIGHBOURS of include/hvgan.h
 GLRLM_FEATURES = ('SRE', 'LRE', 'GLN', 'GLNN', 'RLN', 'RLNN', 'RP', 'GLV', 'RV', 'RE', 'LGLRE', 'HGLRE', 'SRLGLE', 'SRHGLE', 'LRLGLE', 'LRHGLE')
@@ -58,47 +57,23 @@ def _check_int(x, name, lo, hi):
 
 def _inputs(vol, label, mask, labels):
     """The resident 4-D tensors and the label ids of glrlm and gldm -> (single, vol, label, mask, ids)."""
-    vol, label, mask = _resident(vol), _resident(label), _resident(mask)
-    single = isinstance(vol, torch.Tensor) and vol.dim() == 3
-    v4, l4, m4 = _ls._check_inputs(vol, label, mask)
-    if labels is None:
-        ids = _ls._present(v4, l4, m4)
-        if not 1 <= len(ids) <= MAX_LABELS:
-            raise ValueError('labels=None: 1 to %d non-zero label values expected in the volumes, found %d' % (MAX_LABELS, len(ids)))
-    else:
-        ids = _ls._check_labels(labels)
-    return single, v4, l4, m4, ids
-
-
-def _common_args(vol, label, mask, labels):
-    """The arguments hv_glrlm and hv_gldm share with hv_glcm, up to S."""
-    V, A0, A1, A2 = (int(s) for s in vol.shape)
-    S = len(labels)
-    mst = mask.stride() if mask is not None else (0, 0, 0, 0)
-    return [_lib.ptr(vol), _ls._VOL_DT[vol.dtype], *_ls._ll(vol.stride()), _lib.ptr(label), _ls._LABEL_DT[label.dtype], *_ls._ll(label.stride()),
-            _lib.ptr(mask), *_ls._ll(mst), V, A0, A1, A2, (ctypes.c_int * S)(*labels), S]
-
-
-def _workspace(name, vol, *sizes):
-    need = _lib.get().size(name, *(int(s) for s in vol.shape), *sizes)
-    if need == 0:
-        raise ValueError('%s: at most 2^30 voxels per volume and 65535 volumes per call, got shape %s' % (name[3:-16], tuple(vol.shape)))
-    return ops._ws(need, vol.device, slot=3)
+    single, v4, l4, m4 = _lb.check_inputs(vol, label, mask, upload=True)
+    return single, v4, l4, m4, _lb.resolve_labels(labels, lambda: present(v4, l4, m4))
 
 
 def _launch_glrlm(vol, label, mask, labels, offsets, levels, lo, width, R, out, info):
     """Queue one hv_glrlm on the current stream: 4-D device tensors (mask may be None), out int64 [V][S][D][G][R], info int64 [V][S][RLM_INFO]."""
     D = len(offsets)
-    ws, wsz = _workspace('hv_glrlm_workspace_bytes', vol, len(labels), D, levels, R)
+    ws, wsz = _lb.workspace('glrlm', vol, len(labels), D, levels, R)
     flat = [int(x) for x in np.asarray(offsets).reshape(-1)]
-    _lib.get().call('hv_glrlm', *_common_args(vol, label, mask, labels), (ctypes.c_int * (3 * D))(*flat), D, ctypes.c_double(lo),
+    _lib.get().call('hv_glrlm', *_lb.volume_args(vol, label, mask, labels), (ctypes.c_int * (3 * D))(*flat), D, ctypes.c_double(lo),
                     ctypes.c_double(width), levels, R, _lib.ptr(out), _lib.ptr(info), _lib.ptr(ws), wsz, _lib.stream())
 
 
 def _launch_gldm(vol, label, mask, labels, levels, lo, width, alpha, dep, ngt, info):
     """Queue one hv_gldm on the current stream: dep int64 [V][S][G][27], ngt int64 [V][S][G][27][2], info int64 [V][S][INFO]."""
-    ws, wsz = _workspace('hv_gldm_workspace_bytes', vol, len(labels), levels)
-    _lib.get().call('hv_gldm', *_common_args(vol, label, mask, labels), ctypes.c_double(lo), ctypes.c_double(width), levels, alpha, _lib.ptr(dep),
+    ws, wsz = _lb.workspace('gldm', vol, len(labels), levels)
+    _lib.get().call('hv_gldm', *_lb.volume_args(vol, label, mask, labels), ctypes.c_double(lo), ctypes.c_double(width), levels, alpha, _lib.ptr(dep),
                     _lib.ptr(ngt), _lib.ptr(info), _lib.ptr(ws), wsz, _lib.stream())
 
 
@@ -144,10 +119,6 @@ def _gldm_result(host, labels):
     return res
 
 
-def _first(res):
-    return {k: (v if k in _PER_CALL else v[0]) for k, v in res.items()}
-
-
 def glrlm(vol, label, labels=None, offsets=None, levels=32, lo=-200.0, width=25.0, max_run=None, mask=None):
     """The run-length matrices of `vol` inside every listed label value (up to 64) of `label`, restricted to mask != 0.  A run along offset d
     (default: directions(1), the 13 unique 3-D directions; components in {-1, 0, 1}, d and -d give the same runs and may not both be listed) is a
@@ -155,7 +126,7 @@ def glrlm(vol, label, labels=None, offsets=None, levels=32, lo=-200.0, width=25.
     max_run (default: the longest axis, so nothing is capped) is the number of length bins; 'capped' counts the runs longer than that.
     -> {'labels' [S], 'offsets' [D][3], 'matrices' int64 [V][S][D][G][R] ([S][D][G][R] for one volume), 'count', 'clamped_low', 'clamped_high',
     'status' as texture.glcm's [V][S] ([S]), 'capped' [V][S][D] ([S][D])}.  One launch sequence and one readback."""
-    G, lo, width = _check_levels(levels, lo, width)
+    G, lo, width = check_levels(levels, lo, width)
     off = directions(1) if offsets is None else _check_run_offsets(offsets)
     R = None if max_run is None else _check_int(max_run, 'max_run', 1, 1 << 30)
     single, v4, l4, m4, ids = _inputs(vol, label, mask, labels)
@@ -163,7 +134,7 @@ def glrlm(vol, label, labels=None, offsets=None, levels=32, lo=-200.0, width=25.
     b = _Buffers(int(v4.shape[0]), len(ids), G, v4.device, D=len(off), R=R, neighbours=False)
     _launch_glrlm(v4, l4, m4, ids, off, G, lo, width, R, b.dev('out'), b.dev('info_r'))
     res = _glrlm_result(b.read(), ids, off)
-    return _first(res) if single else res
+    return _lb.squeeze(res, _PER_CALL) if single else res
 
 
 def gldm(vol, label, labels=None, alpha=0, levels=32, lo=-200.0, width=25.0, mask=None):
@@ -173,13 +144,13 @@ def gldm(vol, label, labels=None, alpha=0, levels=32, lo=-200.0, width=25.0, mas
     ngtdm[.., s, i, n, 0] += 1 and ngtdm[.., s, i, n, 1] += |i n - A| (ngtdm_features divides by n on the host: exact in any order).
     -> {'labels' [S], 'dependence' int64 [V][S][G][27], 'ngtdm' int64 [V][S][G][27][2], 'count', 'clamped_low', 'clamped_high', 'status'}, without
     the leading axis for one volume.  One launch sequence and one readback."""
-    G, lo, width = _check_levels(levels, lo, width)
+    G, lo, width = check_levels(levels, lo, width)
     alpha = _check_int(alpha, 'alpha', 0, G - 1)
     single, v4, l4, m4, ids = _inputs(vol, label, mask, labels)
     b = _Buffers(int(v4.shape[0]), len(ids), G, v4.device, runs=False)
     _launch_gldm(v4, l4, m4, ids, G, lo, width, alpha, b.dev('dep'), b.dev('ngt'), b.dev('info_d'))
     res = _gldm_result(b.read(), ids)
-    return _first(res) if single else res
+    return _lb.squeeze(res, _PER_CALL) if single else res
 
 
 # ------------------------------------------------------------------------------------------------ host features
@@ -332,24 +303,13 @@ def vertebra_run_texture(ct, label, vert_id, erode_mm=0.0, spacing=(1, 1, 1), le
     -> {'label', 'offsets', 'glrlm' [13][G][R], 'dependence' [G][27], 'ngtdm' [G][27][2], 'capped', 'count', 'clamped_low', 'clamped_high',
     'status', 'features': {'glrlm': glrlm_features ([13] each, 'mean_run' and 'mean'), 'gldm': gldm_features, 'ngtdm': ngtdm_features},
     'run_anisotropy': the mean run length along the unit offset of `slice_axis` over the mean of the other two axis-aligned ones}."""
-    sp = _ls._check_spacing(spacing)
-    r = _ls._check_erode(erode_mm)
-    vid = _ls._check_labels([vert_id])[0]
-    G, lo, width = _check_levels(levels, lo, width)
+    G, lo, width = check_levels(levels, lo, width)
     alpha = _check_int(alpha, 'alpha', 0, G - 1)
     _axis_offsets(slice_axis)
-    ct, label = _resident(ct), _resident(label)
-    _ls._check_3d(ct, 'ct', _ls._VOL_DT)
-    _ls._check_3d(label, 'label', _ls._LABEL_DT, ct.shape)
-    if median_size is not None:
-        from . import rank_filters
-        ct = rank_filters.median_filter(ct, size=median_size)
-    mask = None
-    if r > 0.0:
-        mask = _ls._core_mask(label, [vid], r, sp, torch.empty(tuple(label.shape), dtype=torch.uint8, device=label.device))[None]
+    ct, label, mask, vid, _ = _lb.vertebra_inputs(ct, label, vert_id, erode_mm, spacing, median_size)
     off, R = directions(1), max(int(s) for s in ct.shape)
     b = _Buffers(1, 1, G, ct.device, D=len(off), R=R)
-    _launch_both(ct[None], label[None], mask, [vid], off, G, lo, width, alpha, R, b)
+    _launch_both(ct[None], label[None], None if mask is None else mask[None], [vid], off, G, lo, width, alpha, R, b)
     host = b.read()
     return _one(host, _features(host), [vid], off, 0, 0, slice_axis)
 
@@ -362,40 +322,13 @@ def run_texture_comparison(ct_original, ct_synth, label_original, label_synth, v
     {'glrlm': {feature: mean over the directions}, 'gldm': {feature}, 'ngtdm': {feature}, 'run_anisotropy'}, 'neighbour_difference': {id: the same,
     synthesized - neighbour}}.  The two pairs run as ONE batch (V = 2, the second volume addressed through the batch stride, no copy) when the
     CTs agree in dtype and strides and the labels do, else as two calls into one result buffer; one readback either way."""
-    sp = _ls._check_spacing(spacing)
-    r = _ls._check_erode(erode_mm)
-    ids = _ls._check_labels([vert_id] + list(neighbours))
-    G, lo, width = _check_levels(levels, lo, width)
+    G, lo, width = check_levels(levels, lo, width)
     alpha = _check_int(alpha, 'alpha', 0, G - 1)
     _axis_offsets(slice_axis)
-    ct_original, ct_synth, label_original, label_synth = (_resident(t) for t in (ct_original, ct_synth, label_original, label_synth))
-    _ls._check_3d(ct_original, 'ct_original', _ls._VOL_DT)
-    _ls._check_3d(ct_synth, 'ct_synth', _ls._VOL_DT, ct_original.shape)
-    _ls._check_3d(label_original, 'label_original', _ls._LABEL_DT, ct_original.shape)
-    _ls._check_3d(label_synth, 'label_synth', _ls._LABEL_DT, ct_original.shape)
-    if ct_synth.dtype != ct_original.dtype:
-        raise TypeError('ct_synth: the dtype of ct_original (%s) expected, got %s' % (ct_original.dtype, ct_synth.dtype))
-    dev, shape = ct_original.device, tuple(ct_original.shape)
-    masks = None
-    if r > 0.0:
-        masks = torch.empty((2,) + shape, dtype=torch.uint8, device=dev)
-        _ls._core_mask(label_original, ids, r, sp, masks[0])
-        _ls._core_mask(label_synth, ids[:1], r, sp, masks[1])
-    off, R = directions(1), max(shape)
-    b = _Buffers(2, len(ids), G, dev, D=len(off), R=R)
-
-    def batch_stride(x, y):
-        """y's distance from x in elements if the pair can be addressed as a [2][...] batch, else None."""
-        d = y.data_ptr() - x.data_ptr()
-        ok = x.dtype == y.dtype and x.stride() == y.stride() and d % x.element_size() == 0
-        return d // x.element_size() if ok else None
-
-    cs, lsd = batch_stride(ct_original, ct_synth), batch_stride(label_original, label_synth)
-    if cs is not None and lsd is not None:
-        _launch_both(_ls._Strided(ct_original, cs), _ls._Strided(label_original, lsd), masks, ids, off, G, lo, width, alpha, R, b)
-    else:
-        _launch_both(ct_original[None], label_original[None], None if masks is None else masks[0:1], ids, off, G, lo, width, alpha, R, b, slice(0, 1))
-        _launch_both(ct_synth[None], label_synth[None], None if masks is None else masks[1:2], ids, off, G, lo, width, alpha, R, b, slice(1, 2))
+    pair = _lb.Pair(label_original, label_synth, [vert_id] + list(neighbours), ct_original, ct_synth, erode_mm, spacing)
+    ids, off, R = pair.ids, directions(1), max(pair.shape)
+    b = _Buffers(2, len(ids), G, pair.device, D=len(off), R=R)
+    pair.launch(lambda vol, label, mask, sel: _launch_both(vol, label, mask, ids, off, G, lo, width, alpha, R, b, sel))
     host = b.read()
     feats = _features(host)
     ori, syn = _one(host, feats, ids, off, 0, 0, slice_axis), _one(host, feats, ids, off, 1, 0, slice_axis)
